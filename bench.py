@@ -22,8 +22,12 @@ frame and exchanged, each rank warps / stacks / stretches its row band, statisti
 total work is fixed, so scaling is "strong".
 
 Prints ONE JSON line (rank 0).  `value` = input MPix/s = frames x pixels / second for the whole
-step; `roofline` prices the stacking kernel alone against HBM; `cpu_baseline` times the CPU
-oracle (a C restatement of the reference's Rust path, "port") on a bounded crop of the same frames.
+step; `roofline` prices the stacking kernel alone against HBM from the library's events inside the timed steps.
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds what takes runs of its own:
+the stack launch back to back (`roofline.frac_sustained`), the warp kernel alone (`roofline_warp`), the streaming-copy
+probe (`config.measured_copy_GBs`) and `cpu_baseline`, which times the CPU oracle (a C restatement of the reference's
+Rust path, "port") on a bounded crop of the same frames.
+`--dump-outputs DIR` writes what the last timed step computed to DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -50,7 +54,7 @@ def parse():
     ap.add_argument("--no-register", action="store_true", help="skip registration (stack + stretch only)")
     ap.add_argument("--known-transforms", action="store_true",
                     help="warp with the generating transforms instead of estimating them (diagnostic, not the metric)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline duration")
     ap.add_argument("--cpu-reg-frames", type=int, default=4, help="frame pairs the CPU baseline registers (each ~2 s on 8 threads)")
     ap.add_argument("--force-sharded", action="store_true",
@@ -64,7 +68,16 @@ def parse():
                          "communicator instead of RCCL (which refuses two ranks per device).  The line says so (config.transport); not a scaling figure")
     ap.add_argument("--host-planes", action="store_true",
                     help="also time the step with the 64 frames starting in pinned HOST memory (uploads pipelined with registration): config.host_resident_mpix_s")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take runs of their own: CPU baseline, stack back to back, warp kernel alone, copy probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.config and args.dump_outputs:
+        ap.error("--dump-outputs writes the headline step's outputs: not with --config")
+    return args
 
 
 class stdout_to_stderr:
@@ -119,6 +132,52 @@ def rigid_transforms(n, rows, cols, seed=7):
         dx, dy = rnd.uniform(-8, 8), rnd.uniform(-8, 8)
         ts.append((c, -s_, cx - c * cx + s_ * cy + dx, s_, c, cy - s_ * cx - c * cy + dy))
     return ts
+
+
+DUMP_PLANE_PIXELS = 1 << 21    # pixels of the stacked and preview planes --dump-outputs writes (8 MB each as float32)
+DUMP_WARPED_VALUES = 1 << 21   # values of all registered frames together (8 MB)
+
+
+def dump_outputs(out_dir, dev, stacked, u8, warped, estimated, st, stf, rejected):
+    """What the last timed step handed its caller, as out_dir/<name>.npy in float32 / float64 (about 40 MB at any size).
+    A plane larger than its budget is read at a fixed, seeded set of pixel indices, the same in every run of the same arguments:
+      stacked     float32  the stacked image                     preview_u8  float32  the auto-STF u8 preview (same pixels)
+      warped      float32  (frames - 1, k) registered frames      transforms  float64  (frames - 1, 6) estimated transforms
+      registration float64 (frames - 1, 4): matched stars, inliers, residual px, method (index into core.AFFINE_METHODS)
+      image_stats float64  min, max, median, mad, sigma, mean, valid count of the stack
+      stf_params  float64  shadow, midtone, highlight             rejected_pixels  float64  the stack's rejection count
+    Every file holds finite numbers only: the frames' NaN patches reach the registered frames (and could reach any other array),
+    so beside each array but the preview and the count, <name>_nonfinite.npy (same shape and type) holds 0 where <name> is finite
+    and 1 / 2 / 3 where the value was NaN / +inf / -inf, and <name>.npy holds 0 there."""
+    import numpy as np
+    import torch
+    from astroburst_amd.core import AFFINE_METHODS
+    rng = np.random.default_rng(20240601)
+
+    def sample(n, k):
+        idx = np.arange(n) if k >= n else np.sort(rng.choice(n, size=k, replace=False))
+        return torch.from_numpy(idx).to(dev)
+
+    idx = sample(stacked.numel(), DUMP_PLANE_PIXELS)
+    arrays = {"stacked": stacked.reshape(-1)[idx].float(), "preview_u8": u8.reshape(-1)[idx].float(),
+              "image_stats": np.array([st.min, st.max, st.median, st.mad, st.sigma, st.mean, st.valid_count], np.float64),
+              "stf_params": np.array([stf.shadow, stf.midtone, stf.highlight], np.float64),
+              "rejected_pixels": np.array([rejected], np.float64)}
+    if warped is not None and len(warped) > 1:
+        idx = sample(warped[1].numel(), max(1, DUMP_WARPED_VALUES // (len(warped) - 1)))
+        arrays["warped"] = torch.stack([w.reshape(-1)[idx] for w in warped[1:]]).float()
+    if estimated:
+        arrays["transforms"] = np.array([r.transform for r in estimated], np.float64)
+        arrays["registration"] = np.array([(r.matched_stars, r.inliers, r.residual_px, AFFINE_METHODS.index(r.method))
+                                           for r in estimated], np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if torch.is_tensor(a) else a
+        if name not in ("preview_u8", "rejected_pixels"):   # (u8 values and a count are finite by type)
+            code = np.isnan(a) * 1 + np.isposinf(a) * 2 + np.isneginf(a) * 3
+            np.save(os.path.join(out_dir, f"{name}_nonfinite.npy"), code.astype(a.dtype))
+            a = np.where(code > 0, 0, a).astype(a.dtype)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def main():
@@ -218,6 +277,10 @@ def main():
     band0 = max(0, row0 - kHalo)
     band1 = min(R, row0 + nrows + kHalo)
     raw_band = [None] * N
+    # the PSF patches overlap: render_stars' index_add_ on the device sums them with atomics, in an order that changes from run to
+    # run, unless torch's deterministic algorithms are on -- the inputs are identical in every run of the same arguments
+    deterministic = torch.are_deterministic_algorithms_enabled()
+    torch.use_deterministic_algorithms(True)
     for k in range(N):
         # frame k sees the field through its own pointing error: a star at reference (x, y) lands at T_k(x, y)
         a_, b_, tx_, c_, d_, ty_ = transforms[k] if register else transforms[0]
@@ -232,6 +295,7 @@ def main():
             raw.append(frame)
         del frame
     del truth
+    torch.use_deterministic_algorithms(deterministic)
     resident_bytes = sum(t.numel() * 4 for t in raw) + sum(t.numel() * 4 for t in raw_band if t is not None)
     if rowband:   # this rank's rows of every registered frame; frame 0 (the reference) needs no warp: a view of its rows
         warped = [raw[0][row0:row0 + nrows]] + [torch.empty((nrows, Cc), dtype=torch.float32, device=dev) for _ in range(1, N)]
@@ -282,11 +346,11 @@ def main():
                 ctx.stack_sigma_clip_sharded(comm, warped, stacked, 3.0, 3.0, 5, want_rejected=False)
             e[2].record()
         # auto_stretch_preview (cmd/common.rs:18-22): statistics -> auto_stf -> apply_stf, one device chain, one sync
-        _, st, _ = ctx.auto_stretch_preview(stacked, out=u8, comm=comm if rowband else None, total_rows=R)
+        _, st, stf = ctx.auto_stretch_preview(stacked, out=u8, comm=comm if rowband else None, total_rows=R)
         e[3].record()
         if i >= args.warmup:
             kern_ms.append(ctx.stack_last_kernel_ms())  # HIP events the library records right around its stack kernels
-        return st
+        return st, stf
 
     for i in range(args.warmup):
         step(i)
@@ -297,7 +361,7 @@ def main():
     wall_mark("generate_frames_and_warmup_s")
     t0 = time.perf_counter()
     for i in range(args.warmup, args.warmup + args.steps):
-        st = step(i)
+        st, stf = step(i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -314,6 +378,9 @@ def main():
         stack_ms.append(ev[i][1].elapsed_time(ev[i][2]))
         tail_ms.append(ev[i][2].elapsed_time(ev[i][3]))
     rejected = ctx.last_rejected()
+    if args.dump_outputs and rank == 0:   # before anything below launches the stack again on these buffers
+        dump_outputs(args.dump_outputs, dev, stacked, u8, warped if register else None, estimated[0], st, stf, rejected)
+        wall_mark("dump_outputs_s")
 
     ms_per_step = elapsed * 1e3 / args.steps
     job_frames = N if rowband else world * N               # rowband: the same N frames, split by rows (strong scaling)
@@ -385,7 +452,7 @@ def main():
     # 16 cvt f32->f64, 2 floor, 2 cvt ->i32, 1.5 cvt i32->f64, 1 cvt ->f32: the ISA of csrc/resample.hip's warp_kernel, round 4;
     # the kernel's time does not change when its loads are taken away, tools/time_warp.py with AB_ABLATE_WARP=2)
     warp_roofline = None
-    if register and not rowband:
+    if args.full and register and not rowband:
         if args.known_transforms:
             per = warp_avg_ms / (N - 1)
         else:  # the warps ran inside align_pairs_affine, overlapped with detection: time the kernel on its own here
@@ -407,7 +474,7 @@ def main():
     # the same stack launch back to back on the registered frames (no warps in between): isolates the kernel from the
     # clock / cache state the f64-heavy registration leaves behind
     iso_ms = None
-    if world == 1 and not sharded:
+    if args.full and world == 1 and not sharded:
         i0, i1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ctx.stack_sigma_clip(warped_pl, 3.0, 3.0, 5, out=stacked, want_rejected=False)
         i0.record()
@@ -469,19 +536,22 @@ def main():
     roofline["achieved"] = round(achieved, 1)
     roofline["frac"] = roofline["frac_in_step"]
     roofline["frac_basis"] = ("this run: HIP events on the library's stream around the stack launch (fast + general pass) inside the timed steps; "
-                              "frac_sustained = the same launch back to back in this run, frac_profile = rocprofv3 average of the committed profile")
+                              "frac_sustained = the same launch back to back in this run (--full only, else null), "
+                              "frac_profile = rocprofv3 average of the committed profile")
     # measured streaming ceiling of this GPU (float4 copy), for context
-    a = torch.empty(64 * 1024 * 1024, dtype=torch.float32, device=dev)
-    b = torch.empty_like(a)
-    ctx.bench_copy(a, b)
-    c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    c0.record()
-    for _ in range(10):
+    copy_gbs = None
+    if args.full:
+        a = torch.empty(64 * 1024 * 1024, dtype=torch.float32, device=dev)
+        b = torch.empty_like(a)
         ctx.bench_copy(a, b)
-    c1.record()
-    torch.cuda.synchronize()
-    copy_gbs = 10 * 2 * a.numel() * 4 / (c0.elapsed_time(c1) * 1e-3) / 1e9
-    del a, b
+        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        c0.record()
+        for _ in range(10):
+            ctx.bench_copy(a, b)
+        c1.record()
+        torch.cuda.synchronize()
+        copy_gbs = round(10 * 2 * a.numel() * 4 / (c0.elapsed_time(c1) * 1e-3) / 1e9, 1)
+        del a, b
 
     # how well the estimated transforms reproduce the generating ones (registration sanity, not a parity claim)
     reg_info = None
@@ -503,7 +573,7 @@ def main():
     wall_mark("roofline_extras_s")
     # ---- CPU baseline: the oracle (C restatement of the reference, OpenMP) on a bounded crop ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import pyoracle
         import numpy as np
         threads = pyoracle.max_threads()
@@ -604,7 +674,7 @@ def main():
                                         "the launch line and the sharded code path executed end to end, not a scaling measurement"} if args.host_staged else {}),
                        "output_mpix_per_s": round((1 if rowband else world) * P / 1e6 / (elapsed / args.steps), 1),
                        "rejected_pixels": rejected, "median": st.median,
-                       "measured_copy_GBs": round(copy_gbs, 1), "stage_ms": stage_ms, "registration": reg_info,
+                       "measured_copy_GBs": copy_gbs, "stage_ms": stage_ms, "registration": reg_info,
                        "fallbacks": ctx.fallback_counts(), "library": ab.version() if hasattr(ab, "version") else None,
                        **({"host_resident_mpix_s": host_info["host_resident_mpix_s"], "host_planes": host_info} if host_info else {})},
             "roofline": roofline,
