@@ -687,7 +687,8 @@ __device__ __forceinline__ ClipResult clip_fast_tail(float (&v)[NP], int n, floa
     } else {
         r.value = mean_f;
     }
-    r.sum = (len > 0) ? S : 0.0;
+    // (n == 1: the lane never walked its ends, so the chunks summed as interior above may hold its pads; its one sample is med)
+    r.sum = (n == 1) ? (double)med : (len > 0) ? S : 0.0;
     r.len = len > 0 ? len : 0;
     r.rej = rej;
     r.defer = defer;
@@ -737,6 +738,12 @@ __device__ __forceinline__ ClipResult clip_fast(float (&v)[NP], int n, float med
             }
         }
         s.active = go && (removed != 0) && !defer;
+    }
+    if constexpr (DEFER) {
+        // max_iter 0: no end walk has run, and it is the walk that hands over a lane whose finite samples stop short of the chunks
+        // clip_fast_tail sums as interior (the non-finite pads above n would be summed).  (n < 2: the value is 0 or the sample.)
+        constexpr int CH = NP >= 4 ? 4 : NP;
+        if (max_iter == 0 && n >= 2 && n < NP - CH * kDeferChunks) defer = true;
     }
     s.defer = defer;
 

@@ -26,7 +26,8 @@
  *  None changes a result: every engine they select is held to the same oracle by the tests.
  *    AB_TRACE=1              stage stamps, deferred-pixel and redone-frame notes on stderr (also fills AB_FB_STACK_GENERAL_PIXELS)
  *    AB_STACK_EXACT=1        ab_stack_*: the direct two-pass clipping engine instead of the running-sum one (bit-exact cross-check
- *                            of the default engine's 1e-5 contract; ~1.3x slower)
+ *                            of the default engine's contract -- rejected count exact, every value within 1e-5 relative, see
+ *                            ab_stack_sigma_clip; this engine: bit for bit on every pixel; ~1.3x slower)
  *    AB_STATS_CHAIN=1        ab_compute_image_stats*: the histogram chain instead of the register-resident kernel (identical results;
  *                            what a resident launch falls back to by itself when its grid barrier times out)
  *    AB_REGISTER_WORKERS=n   host threads (= frame groups in flight) of ab_register_frames / ab_align_pairs_affine (default 12)
@@ -154,10 +155,17 @@ typedef struct {
  *   - DEFAULT ENGINE (2 .. 64 frames): within 1e-5 relative of that definition on every pixel -- north_star's tolerance.  Its
  *     iterations >= 1 take mean and variance from running sums about the median (E = sum(x - c0), Q = sum(x - c0)^2 in f64: mean =
  *     (n c0 + E) / n, sum(x - mean)^2 = Q - n (mean - c0)^2), a few ulp(f64) away from the two-pass sums; an ulp can flip the
- *     clipping decision of a sample that sits exactly on a bound.  MEASURED bit-identical: 0 of 16.7 M pixels of the bench stack
- *     differ from the oracle; the GPU tests allow at most 1e-4 of the pixels to differ at all (tests/test_gpu_stack.py:28-39).
+ *     clipping decision of a sample that sits exactly on a bound.  The same contract holds from 129 to 4096 frames (fast multi-lane
+ *     passes with running moments; above 512 frames the survivors are summed as a tree).  Guaranteed: the rejected count equals the
+ *     oracle's exactly; every value within 1e-5 relative; pixels whose arithmetic is exact (samples exactly on a threshold, sums exact
+ *     in f64) bit for bit -- tests/test_gpu_stack_adversarial.py holds all three on adversarial pixels at 3 .. 4100 frames.  Outside
+ *     any relative bound: a kept sample whose deviation from the median overflows f32 (sigma inf): every route but AB_STACK_EXACT=1
+ *     holds only its rejected count.  MEASURED: 0 of 16.7 M pixels of
+ *     the bench stack differ; the older tests allow 1e-4 of the pixels of natural data to differ at all (tests/test_gpu_stack.py).
  *   - AB_STACK_EXACT=1 when the context is created: the direct two-pass engine, bit-identical BY CONSTRUCTION (the tests run both).
- *   - more than 64 frames, median combine, partial sums: always bit-identical by construction. */
+ *   - 65 .. 128 frames and row bands (ab_stack_sigma_clip_rows / _rowband) run the same fast engine under the same contract.
+ *   - more than 4096 frames (or AB_STACK_DEEP_FROM: the workgroup-per-pixel kernel, ascending sums): bit-identical but for the
+ *     sigma-inf pixels above; median combine: bit-identical. */
 AB_API int ab_stack_sigma_clip(ab_ctx *ctx, const ab_plane *planes, size_t n, const ab_stack_config *cfg,
                                ab_plane_mut *out, uint64_t *out_rejected);
 
