@@ -165,6 +165,15 @@ class SubframeWeightConfigC(C.Structure):  # subframe.rs:24-49
                 ("min_snr", C.c_double), ("min_stars", C.c_uint64)]
 
 
+class RLConfigC(C.Structure):  # RLConfig (types/stacking.rs) without the PSF's own size / sigma
+    _fields_ = [("iterations", C.c_size_t), ("regularization", C.c_double), ("deringing", C.c_int32),
+                ("deringing_threshold", C.c_float)]
+
+
+class RLResultC(C.Structure):  # RLResult's scalars (deconvolution.rs:214-219)
+    _fields_ = [("iterations_run", C.c_size_t), ("convergence", C.c_double)]
+
+
 class SubframeMetricsC(C.Structure):  # subframe.rs:9-22
     _fields_ = [("star_count", C.c_uint64), ("median_fwhm", C.c_double), ("median_eccentricity", C.c_double),
                 ("median_snr", C.c_double), ("background_median", C.c_double), ("background_sigma", C.c_double),
@@ -372,6 +381,8 @@ def lib() -> C.CDLL:
                                        i64p, i64p]
     L.ab_auto_stretch_preview.argtypes = [vp, vp, pp, C.c_int64, C.POINTER(AutoStfConfigC), vp, C.POINTER(ImageStatsC),
                                           C.POINTER(StfParamsC)]
+    L.ab_generate_gaussian_psf.argtypes = [C.c_size_t, C.c_float, C.POINTER(C.c_float)]
+    L.ab_richardson_lucy.argtypes = [vp, pp, pp, C.POINTER(RLConfigC), pp, C.POINTER(RLResultC)]
     for name in declared_symbols():
         fn = getattr(L, name)  # AttributeError here = header / library drift
         if fn.restype is C.c_int and name not in ("ab_last_error", "ab_version", "ab_ctx_get_stream", "ab_comm_collectives_issued"):

@@ -194,6 +194,15 @@ def _is_torch(x) -> bool:
     return torch is not None and isinstance(x, torch.Tensor)
 
 
+def generate_gaussian_psf(size: int, sigma: float) -> np.ndarray:
+    """generate_gaussian_psf (deconvolution.rs:12-33) -> size x size f32, normalised (host scalar maths in the library: no GPU)."""
+    out = np.zeros((int(size), int(size)), np.float32)
+    rc = _lib.lib().ab_generate_gaussian_psf(int(size), float(sigma), out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != _lib.AB_OK:
+        raise AstroBurstError(rc, "ab_generate_gaussian_psf: bad arguments")
+    return out
+
+
 class Comm:
     """One RCCL rank bound to a Context's GPU (include/astroburst_hip.h section (e)).  Multi-process: rank 0 calls
     Comm.unique_id(), the host carries the 128 bytes to the other ranks, every rank constructs Comm(ctx, id, nranks, rank)."""
@@ -1515,6 +1524,23 @@ class Context:
                                                          *[C.byref(p) for p in pos], res, C.byref(shared)))
         return (*[self._ms_result(o, x) for o, x in zip(outs, res)],
                 StarMaskResult(None, int(shared.stars_masked), float(shared.coverage_fraction)))
+
+    # ---- core/analysis/deconvolution.rs ----------------------------------------------------------------
+    generate_gaussian_psf = staticmethod(generate_gaussian_psf)
+
+    def richardson_lucy(self, image, psf, iterations=20, regularization=0.001, deringing=True, deringing_threshold=0.1, out=None):
+        """richardson_lucy (deconvolution.rs:141-221) -> (image, iterations_run, convergence).  image, psf and out: numpy (host)
+        or CUDA tensors (device); the result is of the image's kind unless `out` is given."""
+        keep = []
+        pi = self._plane(image, keep)
+        pk = self._plane(psf, keep)
+        if out is None:
+            out = self._new_like(image, pi.rows, pi.cols)
+        po = self._out_plane(out, keep, pi.rows, pi.cols)
+        cfg = _lib.RLConfigC(int(iterations), float(regularization), 1 if deringing else 0, float(deringing_threshold))
+        res = _lib.RLResultC()
+        self._check(self._L.ab_richardson_lucy(self._h, C.byref(pi), C.byref(pk), C.byref(cfg), C.byref(po), C.byref(res)))
+        return out, int(res.iterations_run), float(res.convergence)
 
     # ---- bench support -----------------------------------------------------------------------------
     def bench_copy(self, src, dst):

@@ -45,7 +45,7 @@ use crate::core::stacking::calibration::CalibrationConfig;
 use crate::infra::progress::ProgressHandle;
 use crate::types::compose::{AlignMethod, ChannelStats, DimensionHarmonize, RgbComposeConfig, WhiteBalance};
 use crate::types::image::{AutoStfConfig, ImageStats, ScnrConfig, ScnrMethod, StfParams};
-use crate::types::stacking::{StackConfig, StackResult};
+use crate::types::stacking::{RLConfig, RLResult, StackConfig, StackResult};
 
 pub struct Hip {
     pub(crate) ctx: *mut sys::ab_ctx,
@@ -682,6 +682,31 @@ pub fn extract_background(hip: &Hip, image: &impl PlaneSrc, config: &BackgroundC
         p.emit_complete(); // background.rs:105-107
     }
     Ok(BackgroundResult { model, corrected, sample_count: info.sample_count, rms_residual: info.rms_residual, elapsed_ms: start.elapsed().as_millis() as u64 })
+}
+
+// ---- core/analysis/deconvolution.rs (deconvolve_rl_cmd) -------------------------------------------------------------------------------------------------
+/// drop-in for generate_gaussian_psf (deconvolution.rs:12-33): host maths in the library, bit-identical on glibc
+pub fn generate_gaussian_psf(size: usize, sigma: f32) -> Array2<f32> {
+    let mut psf = Array2::<f32>::zeros((size, size));
+    if size > 0 {
+        unsafe { sys::ab_generate_gaussian_psf(size, sigma, psf.as_mut_ptr()) };
+    }
+    psf
+}
+/// drop-in for richardson_lucy (deconvolution.rs:141-221), progress and cancel included (one tick per chunk of iterations)
+pub fn richardson_lucy(hip: &Hip, image: &impl PlaneSrc, psf: &impl PlaneSrc, config: &RLConfig, progress: Option<&ProgressHandle>) -> Result<RLResult> {
+    let start = std::time::Instant::now();
+    let mut out = Array2::<f32>::zeros(image.dims());
+    let cfg = sys::ab_rl_config {
+        iterations: config.iterations,
+        regularization: config.regularization,
+        deringing: config.deringing as i32,
+        deringing_threshold: config.deringing_threshold,
+    };
+    let mut res: sys::ab_rl_result = unsafe { std::mem::zeroed() };
+    let mut po = out.ab_mut();
+    hip.with_progress(progress, || hip.check(unsafe { sys::ab_richardson_lucy(hip.ctx, &image.ab(), &psf.ab(), &cfg, &mut po, &mut res) }))?;
+    Ok(RLResult { image: out, iterations_run: res.iterations_run, convergence: res.convergence, elapsed_ms: start.elapsed().as_millis() as u64 })
 }
 
 // ---- a13  core/imaging/star_mask.rs, masked_stretch.rs -------------------------------------------------------------------------------------------------

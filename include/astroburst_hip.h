@@ -647,6 +647,32 @@ AB_API int ab_generate_tile_pyramid_rgb(ab_ctx *ctx, const ab_plane *r, const ab
                                         const ab_stf_params *stf, const ab_image_stats *stats, uint8_t *tiles, int32_t tiles_on_device,
                                         ab_tile_level *levels, int32_t *num_levels);
 
+/* ---- Richardson-Lucy deconvolution, core/analysis/deconvolution.rs (deconvolve_rl_cmd) ------------------------------- */
+typedef struct { /* RLConfig (types/stacking.rs) without the PSF's own size / sigma: the PSF is passed as a plane */
+    size_t iterations;
+    double regularization;
+    int32_t deringing; /* bool */
+    float deringing_threshold;
+} ab_rl_config;
+typedef struct { /* RLResult's scalars; elapsed_ms is the host's to measure */
+    size_t iterations_run;
+    double convergence;
+} ab_rl_result;
+/* generate_gaussian_psf (deconvolution.rs:12-33): size x size f32, row-major, exp = libm expf in the reference's order and
+ * f32 running sum (bit-identical to the reference on glibc).  Host-only; size 0 -> AB_ERR_INVALID. */
+AB_API int ab_generate_gaussian_psf(size_t size, float sigma, float *out_host);
+/* richardson_lucy (:141-221) with apply_deringing (:223-245); img, psf and out host or device, out = img's dims and not
+ * overlapping it; an empty PSF -> AB_ERR_INVALID.  The reference's FFT convolution over the padded power-of-two buffer equals
+ * the linear convolution with a zero boundary on the kept window, computed here directly in f32 (not bit-identical to the
+ * reference's FFTs: ~1e-5 relative, as its own f32 FFT against f64).  The iteration stops early once convergence < 1e-6 after
+ * >= 3 iterations: near that threshold a stop may differ from the reference's by one iteration.  iterations = 0 returns
+ * the image with iterations_run = 0 and convergence = DBL_MAX.  A NaN / inf pixel or PSF tap poisons the whole convolution as
+ * in the reference; |x| >= 1e30 (FFT overflow in the reference) is outside the contract.  PSFs up to 63 x 63 take the LDS-tiled
+ * kernels, larger ones a plain direct kernel (correct, slower).  Iterations are enqueued in chunks of <= ~25 ms of GPU work:
+ * cancellation is seen, and the progress callback ticked ("iteration k/n"), once per chunk. */
+AB_API int ab_richardson_lucy(ab_ctx *ctx, const ab_plane *img, const ab_plane *psf, const ab_rl_config *cfg, ab_plane_mut *out,
+                              ab_rl_result *res);
+
 /* ---- bench support: a plain float4 device copy, the measured HBM ceiling ---- */
 AB_API int ab_bench_copy(ab_ctx *ctx, const float *src_dev, float *dst_dev, size_t n_floats);
 
