@@ -174,6 +174,16 @@ class RLResultC(C.Structure):  # RLResult's scalars (deconvolution.rs:214-219)
     _fields_ = [("iterations_run", C.c_size_t), ("convergence", C.c_double)]
 
 
+class DrizzleConfigC(C.Structure):  # DrizzleConfig (types/stacking.rs) + the affine estimate's num_threads
+    _fields_ = [("scale", C.c_double), ("pixfrac", C.c_double), ("kernel", C.c_int32), ("sigma_low", C.c_float), ("sigma_high", C.c_float),
+                ("sigma_iterations", C.c_size_t), ("align", C.c_int32), ("alignment_method", C.c_int32), ("num_threads", C.c_int32)]
+
+
+class DrizzleResultC(C.Structure):  # DrizzleResult's scalars (drizzle.rs:335-344)
+    _fields_ = [("frame_count", C.c_size_t), ("output_scale", C.c_double), ("in_rows", C.c_int64), ("in_cols", C.c_int64),
+                ("out_rows", C.c_int64), ("out_cols", C.c_int64), ("rejected_pixels", C.c_uint64)]
+
+
 class SubframeMetricsC(C.Structure):  # subframe.rs:9-22
     _fields_ = [("star_count", C.c_uint64), ("median_fwhm", C.c_double), ("median_eccentricity", C.c_double),
                 ("median_snr", C.c_double), ("background_median", C.c_double), ("background_sigma", C.c_double),
@@ -383,6 +393,9 @@ def lib() -> C.CDLL:
                                           C.POINTER(StfParamsC)]
     L.ab_generate_gaussian_psf.argtypes = [C.c_size_t, C.c_float, C.POINTER(C.c_float)]
     L.ab_richardson_lucy.argtypes = [vp, pp, pp, C.POINTER(RLConfigC), pp, C.POINTER(RLResultC)]
+    L.ab_drizzle_output_dims.argtypes = [pp, C.c_size_t, C.POINTER(DrizzleConfigC), i64p, i64p, i64p, i64p]
+    L.ab_drizzle_frames.argtypes = [vp, pp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(DrizzleConfigC), pp, pp, C.POINTER(DrizzleResultC)]
+    L.ab_drizzle_stack.argtypes = [vp, pp, C.c_size_t, C.POINTER(DrizzleConfigC), pp, pp, C.POINTER(C.c_double), C.POINTER(DrizzleResultC)]
     for name in declared_symbols():
         fn = getattr(L, name)  # AttributeError here = header / library drift
         if fn.restype is C.c_int and name not in ("ab_last_error", "ab_version", "ab_ctx_get_stream", "ab_comm_collectives_issued"):

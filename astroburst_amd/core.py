@@ -108,6 +108,22 @@ class StackResult:  # types/stacking.rs:22-28
 
 
 @dataclass
+class DrizzleResult:  # types/stacking.rs DrizzleResult (drizzle.rs:335-344)
+    image: object
+    weight_map: object
+    frame_count: int
+    output_scale: float
+    input_dims: tuple
+    output_dims: tuple
+    offsets: list  # (dx, dy) per frame
+    rejected_pixels: int
+
+
+DRIZZLE_KERNELS = {"square": 0, "gaussian": 1, "lanczos3": 2}
+DRIZZLE_ALIGNMENT = {"phase_correlation": 0, "zncc": 1}
+
+
+@dataclass
 class DetectedStar:  # star_detection.rs:10-20
     x: float
     y: float
@@ -201,6 +217,35 @@ def generate_gaussian_psf(size: int, sigma: float) -> np.ndarray:
     if rc != _lib.AB_OK:
         raise AstroBurstError(rc, "ab_generate_gaussian_psf: bad arguments")
     return out
+
+
+def _drizzle_config(scale, pixfrac, kernel, sigma_low, sigma_high, sigma_iterations, align=False, alignment_method=0, num_threads=8):
+    kernel = DRIZZLE_KERNELS[kernel.lower()] if isinstance(kernel, str) else int(kernel)
+    alignment_method = DRIZZLE_ALIGNMENT[alignment_method.lower()] if isinstance(alignment_method, str) else int(alignment_method)
+    return _lib.DrizzleConfigC(float(scale), float(pixfrac), kernel, float(sigma_low), float(sigma_high), int(sigma_iterations),
+                               1 if align else 0, alignment_method, int(num_threads))
+
+
+def _host_shapes(frames):
+    """ab_plane descriptors carrying only the dims (the host-only entry point never reads the data)"""
+    return (Plane * max(len(frames), 1))(*[Plane(None, int(f.shape[0]), int(f.shape[1]), 0) for f in frames])
+
+
+def drizzle_output_dims(frames, scale=2.0, pixfrac=0.7):
+    """the checks and dims of drizzle_stack (drizzle.rs:231-279) -> (in_rows, in_cols, out_rows, out_cols); frames: arrays / tensors
+    or (rows, cols) shapes.  Host-only: no GPU.  AstroBurstError for no frames, one frame, dims that vary too much, > 32 767 frames."""
+    class _S:
+        def __init__(self, shape):
+            self.shape = shape
+    fr = [f if hasattr(f, "shape") else _S(tuple(f)) for f in frames]
+    cfg = _drizzle_config(scale, pixfrac, 0, 3.0, 3.0, 5)
+    v = [C.c_int64(0) for _ in range(4)]
+    rc = _lib.lib().ab_drizzle_output_dims(_host_shapes(fr), len(fr), C.byref(cfg), *[C.byref(x) for x in v])
+    if rc != _lib.AB_OK:
+        n = len(fr)
+        raise AstroBurstError(rc, "No images to drizzle" if n == 0 else "Drizzle requires at least 2 frames for sub-pixel reconstruction" if n < 2
+                              else "ab_drizzle_output_dims: frame dimensions vary too much, too many frames or a NaN scale / pixfrac")
+    return tuple(int(x.value) for x in v)
 
 
 class Comm:
@@ -1541,6 +1586,61 @@ class Context:
         res = _lib.RLResultC()
         self._check(self._L.ab_richardson_lucy(self._h, C.byref(pi), C.byref(pk), C.byref(cfg), C.byref(po), C.byref(res)))
         return out, int(res.iterations_run), float(res.convergence)
+
+    # ---- core/stacking/drizzle.rs -------------------------------------------------------------------------
+    drizzle_output_dims = staticmethod(drizzle_output_dims)
+
+    def _drizzle(self, frames, offsets, cfg, out, out_weight, want_weight):
+        n = len(frames)
+        if n == 0:
+            raise AstroBurstError(_lib.AB_ERR_INVALID, "No images to drizzle")
+        keep = []
+        planes = self._planes(frames, keep)
+        dims = [C.c_int64(0) for _ in range(4)]
+        self._check_noctx(self._L.ab_drizzle_output_dims(planes, n, C.byref(cfg), *[C.byref(x) for x in dims]), n)
+        orows, ocols = int(dims[2].value), int(dims[3].value)
+        if out is None:
+            out = self._new_like(frames[0], orows, ocols)
+        if out_weight is None and want_weight:
+            out_weight = self._new_like(frames[0], orows, ocols)
+        for o in (out, out_weight):
+            if o is not None and not _is_torch(o) and (o.shape != (orows, ocols) or o.dtype != np.float32 or not o.flags.c_contiguous):
+                raise AstroBurstError(_lib.AB_ERR_INVALID, f"output must be a contiguous float32 array of {orows}x{ocols}")
+        po = self._out_plane(out, keep, orows, ocols)
+        pw = self._out_plane(out_weight, keep, orows, ocols) if out_weight is not None else None
+        res = _lib.DrizzleResultC()
+        off = (C.c_double * (2 * n))()
+        if offsets is not None:
+            flat = [float(v) for pair in offsets for v in pair]
+            assert len(flat) == 2 * n, "one (dx, dy) pair per frame"
+            off[:] = flat
+            self._check(self._L.ab_drizzle_frames(self._h, planes, n, off, C.byref(cfg), C.byref(po), C.byref(pw) if pw is not None else None,
+                                                  C.byref(res)))
+        else:
+            self._check(self._L.ab_drizzle_stack(self._h, planes, n, C.byref(cfg), C.byref(po), C.byref(pw) if pw is not None else None, off,
+                                                 C.byref(res)))
+        return DrizzleResult(out, out_weight, int(res.frame_count), float(res.output_scale), (int(res.in_rows), int(res.in_cols)),
+                             (int(res.out_rows), int(res.out_cols)), [(off[2 * i], off[2 * i + 1]) for i in range(n)], int(res.rejected_pixels))
+
+    def _check_noctx(self, rc, n):
+        if rc != _lib.AB_OK:
+            raise AstroBurstError(rc, "No images to drizzle" if n == 0 else "Drizzle requires at least 2 frames for sub-pixel reconstruction" if n < 2
+                                  else "Frame dimensions vary too much, too many frames or a NaN scale / pixfrac")
+
+    def drizzle_frames(self, frames, offsets, scale=2.0, pixfrac=0.7, kernel="square", sigma_low=3.0, sigma_high=3.0, sigma_iterations=5,
+                       out=None, out_weight=None, want_weight=True) -> DrizzleResult:
+        """drizzle_frame per frame + finalize (drizzle.rs:46-199) with the caller's offsets: one (dx, dy) per frame as
+        DrizzleResult.offsets reports them.  frames: numpy (host) or CUDA tensors (device), dims within the reference's tolerance;
+        the image and weight map are of the first frame's kind unless out / out_weight are given."""
+        cfg = _drizzle_config(scale, pixfrac, kernel, sigma_low, sigma_high, sigma_iterations)
+        return self._drizzle(frames, offsets, cfg, out, out_weight, want_weight)
+
+    def drizzle_stack(self, frames, scale=2.0, pixfrac=0.7, kernel="square", sigma_low=3.0, sigma_high=3.0, sigma_iterations=5, align=True,
+                      alignment_method="phase_correlation", num_threads=8, out=None, out_weight=None, want_weight=True) -> DrizzleResult:
+        """drizzle_stack (drizzle.rs:227-346): offsets against frame 0 by phase correlation (the affine estimate where its confidence is
+        low; always for "zncc"), then drizzle_frames."""
+        cfg = _drizzle_config(scale, pixfrac, kernel, sigma_low, sigma_high, sigma_iterations, align, alignment_method, num_threads)
+        return self._drizzle(frames, None, cfg, out, out_weight, want_weight)
 
     # ---- bench support -----------------------------------------------------------------------------
     def bench_copy(self, src, dst):

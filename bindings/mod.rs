@@ -45,7 +45,7 @@ use crate::core::stacking::calibration::CalibrationConfig;
 use crate::infra::progress::ProgressHandle;
 use crate::types::compose::{AlignMethod, ChannelStats, DimensionHarmonize, RgbComposeConfig, WhiteBalance};
 use crate::types::image::{AutoStfConfig, ImageStats, ScnrConfig, ScnrMethod, StfParams};
-use crate::types::stacking::{RLConfig, RLResult, StackConfig, StackResult};
+use crate::types::stacking::{AlignmentMethod, DrizzleConfig, DrizzleKernel, DrizzleResult, RLConfig, RLResult, StackConfig, StackResult};
 
 pub struct Hip {
     pub(crate) ctx: *mut sys::ab_ctx,
@@ -707,6 +707,80 @@ pub fn richardson_lucy(hip: &Hip, image: &impl PlaneSrc, psf: &impl PlaneSrc, co
     let mut po = out.ab_mut();
     hip.with_progress(progress, || hip.check(unsafe { sys::ab_richardson_lucy(hip.ctx, &image.ab(), &psf.ab(), &cfg, &mut po, &mut res) }))?;
     Ok(RLResult { image: out, iterations_run: res.iterations_run, convergence: res.convergence, elapsed_ms: start.elapsed().as_millis() as u64 })
+}
+
+// ---- core/stacking/drizzle.rs (calibration.rs:320 drizzle_from_paths, drizzle_rgb_cmd) ----------------------------------------------------------------------
+fn drizzle_cfg(config: &DrizzleConfig) -> sys::ab_drizzle_config {
+    sys::ab_drizzle_config {
+        scale: config.scale,
+        pixfrac: config.pixfrac,
+        kernel: match config.kernel { DrizzleKernel::Square => 0, DrizzleKernel::Gaussian => 1, DrizzleKernel::Lanczos3 => 2 },
+        sigma_low: config.sigma_low,
+        sigma_high: config.sigma_high,
+        sigma_iterations: config.sigma_iterations,
+        align: config.align as i32,
+        alignment_method: match config.alignment_method { AlignmentMethod::PhaseCorrelation => 0, AlignmentMethod::Zncc => 1 },
+        num_threads: rayon::current_num_threads() as i32,
+    }
+}
+fn drizzle_fail(n: usize) -> anyhow::Error {
+    // (the host-only entry point has no context to carry the message: the reference's own strings, drizzle.rs:231-254)
+    match n {
+        0 => anyhow::anyhow!("No images to drizzle"),
+        1 => anyhow::anyhow!("Drizzle requires at least 2 frames for sub-pixel reconstruction"),
+        _ => anyhow::anyhow!("Frame dimensions vary too much"),
+    }
+}
+/// the checks and dims of drizzle_stack (drizzle.rs:231-279): ((in_rows, in_cols), (out_rows, out_cols)); host-only
+pub fn drizzle_output_dims<P: PlaneSrc>(images: &[P], config: &DrizzleConfig) -> Result<((usize, usize), (usize, usize))> {
+    let planes: Vec<_> = images.iter().map(|i| i.ab()).collect();
+    let (mut ir, mut ic, mut or, mut oc) = (0i64, 0i64, 0i64, 0i64);
+    if unsafe { sys::ab_drizzle_output_dims(planes.as_ptr(), planes.len(), &drizzle_cfg(config), &mut ir, &mut ic, &mut or, &mut oc) } != 0 {
+        return Err(drizzle_fail(images.len()));
+    }
+    Ok(((ir as usize, ic as usize), (or as usize, oc as usize)))
+}
+fn drizzle_run<P: PlaneSrc>(hip: &Hip, images: &[P], offsets: Option<&[(f64, f64)]>, config: &DrizzleConfig) -> Result<DrizzleResult> {
+    let (_, (out_rows, out_cols)) = drizzle_output_dims(images, config)?;
+    let planes: Vec<_> = images.iter().map(|i| i.ab()).collect();
+    let mut image = Array2::<f32>::zeros((out_rows, out_cols));
+    let mut weight_map = Array2::<f32>::zeros((out_rows, out_cols));
+    let (mut pi, mut pw) = (image.ab_mut(), weight_map.ab_mut());
+    let mut res: sys::ab_drizzle_result = unsafe { std::mem::zeroed() };
+    let mut off = vec![0f64; 2 * images.len()];
+    let cfg = drizzle_cfg(config);
+    match offsets {
+        Some(o) => {
+            if o.len() != images.len() {
+                bail!("drizzle_frames: one (dx, dy) per frame");
+            }
+            for (k, (dx, dy)) in o.iter().enumerate() {
+                off[2 * k] = *dx;
+                off[2 * k + 1] = *dy;
+            }
+            hip.check(unsafe { sys::ab_drizzle_frames(hip.ctx, planes.as_ptr(), planes.len(), off.as_ptr(), &cfg, &mut pi, &mut pw, &mut res) })?
+        }
+        None => hip.check(unsafe { sys::ab_drizzle_stack(hip.ctx, planes.as_ptr(), planes.len(), &cfg, &mut pi, &mut pw, off.as_mut_ptr(), &mut res) })?,
+    }
+    Ok(DrizzleResult {
+        image,
+        weight_map,
+        frame_count: res.frame_count,
+        output_scale: res.output_scale,
+        input_dims: (res.in_rows as usize, res.in_cols as usize),
+        output_dims: (res.out_rows as usize, res.out_cols as usize),
+        offsets: off.chunks(2).map(|c| (c[0], c[1])).collect(),
+        rejected_pixels: res.rejected_pixels,
+    })
+}
+/// drop-in for core::stacking::drizzle::drizzle_stack (drizzle.rs:227-346); frames host or device
+pub fn drizzle_stack<P: PlaneSrc>(hip: &Hip, images: &[P], config: &DrizzleConfig) -> Result<DrizzleResult> {
+    drizzle_run(hip, images, None, config)
+}
+/// drizzle_stack with offsets the caller already has (one (dx, dy) per frame, as DrizzleResult.offsets reports them): the
+/// registration of an earlier run, a plate solution, a dither log
+pub fn drizzle_frames<P: PlaneSrc>(hip: &Hip, images: &[P], offsets: &[(f64, f64)], config: &DrizzleConfig) -> Result<DrizzleResult> {
+    drizzle_run(hip, images, Some(offsets), config)
 }
 
 // ---- a13  core/imaging/star_mask.rs, masked_stretch.rs -------------------------------------------------------------------------------------------------

@@ -673,6 +673,50 @@ AB_API int ab_generate_gaussian_psf(size_t size, float sigma, float *out_host);
 AB_API int ab_richardson_lucy(ab_ctx *ctx, const ab_plane *img, const ab_plane *psf, const ab_rl_config *cfg, ab_plane_mut *out,
                               ab_rl_result *res);
 
+/* ---- drizzle stacking, core/stacking/drizzle.rs (calibration.rs:320 drizzle_from_paths, drizzle_rgb_cmd) ------------------- */
+typedef struct { /* DrizzleConfig (types/stacking.rs) */
+    double scale;   /* clamped to [1, 4] (drizzle.rs:274) */
+    double pixfrac; /* clamped to [0.1, 1] (:275) */
+    int32_t kernel; /* DrizzleKernel: 0 Square, 1 Gaussian, 2 Lanczos3 */
+    float sigma_low, sigma_high;
+    size_t sigma_iterations;
+    int32_t align;            /* bool */
+    int32_t alignment_method; /* AlignmentMethod: 0 PhaseCorrelation, 1 Zncc (routed to the affine estimate, :300-313) */
+    int32_t num_threads;      /* what the affine estimate takes from rayon::current_num_threads() (ab_align_channel_affine); <= 0: 8 */
+} ab_drizzle_config;
+typedef struct { /* DrizzleResult's scalars (:335-344); the offsets are an argument of their own */
+    size_t frame_count;
+    double output_scale;
+    int64_t in_rows, in_cols, out_rows, out_cols;
+    uint64_t rejected_pixels;
+} ab_drizzle_result;
+/* drizzle_stack's checks and dims (:231-279), host-only: n = 0 ("No images to drizzle"), n < 2 ("Drizzle requires at least 2
+ * frames ..."), rows or cols varying by more than (max(min_rows, min_cols) as f64 * 0.05) as usize ("Frame dimensions vary too
+ * much ..."), n > 32 767 (the reference counts 2 n samples per pixel in a u16) or a NaN scale / pixfrac -> AB_ERR_INVALID;
+ * otherwise the cropped input dims and out = ceil(in * clamp(scale, 1, 4)) per axis.  Any output pointer may be NULL. */
+AB_API int ab_drizzle_output_dims(const ab_plane *planes, size_t n, const ab_drizzle_config *cfg, int64_t *in_rows, int64_t *in_cols,
+                                  int64_t *out_rows, int64_t *out_cols);
+/* The checks above, then drizzle_frame (:46-122) per frame and finalize (:124-199) with the caller's offsets: n (dx, dy) pairs
+ * as DrizzleResult.offsets reports them (the negation of :323 happens inside; all finite, else AB_ERR_INVALID); cfg->align and
+ * alignment_method are not read.  Frames host or device, of differing dims within the tolerance (cropped by stride, not
+ * copied); out_image and out_weight host or device, ab_drizzle_output_dims' out dims; out_weight NULL (or with NULL data) = not
+ * wanted.  The reference's scatter is computed as a gather, one lane per output pixel, which rebuilds each pixel's sample list in
+ * the reference's order (frame, input row, input column) with its cap of max(2 n, 4) samples and its `w > 1e-12` test in the
+ * reference's f64 operations.  Square: weight map and rejected_pixels bit for bit; image bit for bit where the survivors' f64 sum
+ * is exact, else within 1 f32 ulp (the sum runs in ascending order of value; the reference's order after select_nth_unstable is
+ * unspecified).  Gaussian / Lanczos3: the device's f64 exp / sin are not glibc's, so a weight may differ in its last bits (the
+ * f32 weight map: 1e-6 relative) and a candidate whose weight lies within that of 1e-12 may fall on the other side.  Up to 32
+ * frames the lists stay on chip; 33 .. 32 767 frames take a general path (correct, slower).  Not asynchronous: rejected_pixels is
+ * read back.  The output is enqueued in bands: cancellation is seen, and the progress callback ticked ("drizzle k/n"), per band. */
+AB_API int ab_drizzle_frames(ab_ctx *ctx, const ab_plane *planes, size_t n, const double *offsets_dx_dy, const ab_drizzle_config *cfg,
+                             ab_plane_mut *out_image, ab_plane_mut *out_weight, ab_drizzle_result *res);
+/* drizzle_stack whole (:227-346): offsets of frames 1 .. n - 1 against frame 0 (:281-318) -- align = 0: zeros; PhaseCorrelation:
+ * ab_phase_correlate's (dx, dy), and where its confidence < 2.0 (phase_correlation.rs:163) the affine estimate's (tx, ty)
+ * (align.rs:73-80 = ab_align_channel_affine's transform[2], [5]); Zncc: always the affine estimate -- then ab_drizzle_frames.
+ * offsets_dx_dy (nullable) receives the n pairs. */
+AB_API int ab_drizzle_stack(ab_ctx *ctx, const ab_plane *planes, size_t n, const ab_drizzle_config *cfg, ab_plane_mut *out_image,
+                            ab_plane_mut *out_weight, double *offsets_dx_dy, ab_drizzle_result *res);
+
 /* ---- bench support: a plain float4 device copy, the measured HBM ceiling ---- */
 AB_API int ab_bench_copy(ab_ctx *ctx, const float *src_dev, float *dst_dev, size_t n_floats);
 
