@@ -82,13 +82,20 @@ __device__ __forceinline__ float bicubic_taps_interior(const float *__restrict__
 }
 
 // `inside` (wave-uniform): every active lane's footprint [ix-1, ix+2] x [iy-1, iy+2] lies inside the image
+// GUARD: a coordinate may be NaN.  The reference's `as i64` turns it into index 0 and both compares of catmull_rom fail on the NaN
+// fraction, so all four weights of that axis are 0.0 (sampling.rs:4-14) -- the statically split polynomials would give NaN.
+template <bool GUARD = false>
 __device__ __forceinline__ float bicubic_sample(const float *__restrict__ src, int rows, int cols, int ld, double y, double x,
                                                 bool sample = true) {
     const double xf = floor(x), yf = floor(y);
     double wx0, wx1, wx2, wx3, wy0, wy1, wy2, wy3;
     catmull_weights(x - xf, wx0, wx1, wx2, wx3);
     catmull_weights(y - yf, wy0, wy1, wy2, wy3);
-    const int ix = (int)xf, iy = (int)yf;
+    int ix = (int)xf, iy = (int)yf;
+    if constexpr (GUARD) {
+        if (x != x) ix = 0, wx0 = wx1 = wx2 = wx3 = 0.0;
+        if (y != y) iy = 0, wy0 = wy1 = wy2 = wy3 = 0.0;
+    }
     const bool interior = ix >= 1 && ix + 2 < cols && iy >= 1 && iy + 2 < rows;
     if (__all(interior || !sample)) {  // the usual case away from the frame edges
         if (!sample) return 0.0f;
@@ -123,7 +130,8 @@ __device__ __forceinline__ void xcd_band_piece(unsigned int &piece_x, unsigned i
 #endif
 }
 
-// align.rs:46-55
+// align.rs:46-55.  GUARD: dy or dx is not finite (a NaN passes both the copy test and the four range compares, and is sampled)
+template <bool GUARD>
 __global__ __launch_bounds__(256) void shift_kernel(const float *__restrict__ src, int rows, int cols, int ld, double dy,
                                                     double dx, float *__restrict__ out) {
     unsigned int piece_x, piece_y;
@@ -135,7 +143,7 @@ __global__ __launch_bounds__(256) void shift_kernel(const float *__restrict__ sr
     const double sx = (double)x + dx;
     float r = 0.0f;
     if (!(sy < -0.5 || sy > (double)rows - 0.5 || sx < -0.5 || sx > (double)cols - 0.5))
-        r = bicubic_sample(src, rows, cols, ld, sy, sx);
+        r = bicubic_sample<GUARD>(src, rows, cols, ld, sy, sx);
     out[(size_t)y * cols + x] = r;
 }
 
@@ -275,7 +283,10 @@ int ab_shift_device(ab_ctx *ctx, const float *src, int64_t rows, int64_t cols, i
     AB_CHECK(ctx, rows <= 65535 && rows * src_ld < (int64_t(1) << 31),
              "image of %lld x %lld needs a tiled launch (not in this build)", (long long)rows, (long long)cols);
     const dim3 grid((unsigned)((cols + 255) / 256), (unsigned)rows), block(256);
-    hipLaunchKernelGGL(shift_kernel, grid, block, 0, ctx->stream, src, (int)rows, (int)cols, (int)src_ld, dy, dx, out);
+    if (std::isfinite(dy) && std::isfinite(dx))
+        hipLaunchKernelGGL(shift_kernel<false>, grid, block, 0, ctx->stream, src, (int)rows, (int)cols, (int)src_ld, dy, dx, out);
+    else
+        hipLaunchKernelGGL(shift_kernel<true>, grid, block, 0, ctx->stream, src, (int)rows, (int)cols, (int)src_ld, dy, dx, out);
     AB_HIP(ctx, hipGetLastError());
     return AB_OK;
 }

@@ -1,5 +1,7 @@
-"""BASELINE.json's other configurations at their FULL sizes, through size-independent properties (the oracle
-would need minutes at these sizes; parity at oracle-sized inputs lives in the per-function test files).
+"""BASELINE.json's other configurations at their FULL sizes, through size-independent properties.  Only the 64-frame stack's
+oracle needs minutes at these sizes (it is compared on crops here and full-frame by the bench's checker); everything else -- warp,
+shift, resample, registration, statistics, the C5 maps -- is held to the oracle at full size in test_gpu_full_size_parity.py, and at
+oracle-sized inputs in the per-function test files.
 
   C2  64 x 4096 x 4096 stack: permutation invariance, outlier rejection, checksum against a frame-order shuffle
   C3  JWST NIRCam shape 16 x 13759 x 12451: identical frames -> the frame; tone-curve identity; SHO blend linearity
