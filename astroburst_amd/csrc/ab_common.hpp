@@ -17,6 +17,7 @@
 #include "../../include/astroburst_hip.h"
 
 #define AB_REJ_SLOTS 2048
+#define AB_STACK_LIST_SLOTS 2048  // lists of the pixels a stacking fast pass hands over, by wave index (no hot atomic address)
 
 enum {
     AB_WS_DETECT_PARENT = 0,  // int[P] union-find forest (defined at labelled pixels only)
@@ -407,19 +408,37 @@ int ab_resample_device(ab_ctx *ctx, const float *src, int64_t src_rows, int64_t 
 // communicators: a plain hipStreamSynchronize.
 int ab_comm_stream_wait(ab_ctx *ctx, ab_comm *comm);
 
-// stack_wide.hip: 65 .. 512 frames, one wave per pixel (host tables of n plane pointers / strides; counters pre-cleared)
-int ab_stack_wide_device(ab_ctx *ctx, const float *const *dplanes, const int64_t *ld, size_t n, int64_t rows, int64_t cols,
+// ---- the stacking engines: stack_plan.hpp chooses the route, ab_stack_device (stack_sigma_clip.hip) plans and dispatches ----
+struct StackPlan;
+int ab_stack_device(ab_ctx *ctx, const float *const *dplanes, const int64_t *ld, size_t n, int64_t rows, int64_t cols, const ab_stack_config *cfg,
+                    float *out_dev, double *out_sum_dev, uint32_t *out_cnt_dev, uint64_t *out_rejected, bool median_only);
+// stack_wide.hip: 65 .. 4096 frames, one wave per pixel (HOST tables of n plane pointers / strides; counters pre-cleared)
+int ab_stack_wide_device(ab_ctx *ctx, const StackPlan &plan, const float *const *dplanes, const int64_t *ld, bool contiguous, size_t n, int64_t rows, int64_t cols,
                          const ab_stack_config *cfg, float *out_dev, double *out_sum_dev, uint32_t *out_cnt_dev, bool median_only);
-// 257 .. 512 contiguous frames, two lanes per pixel (stack_pair.hip); dplanes is a HOST array of n device pointers
-// more than 4096 frames (any count): one workgroup per pixel, samples in global scratch (stack_deep.hip)
+// stack_deep.hip: more than ctx->stack_deep_from frames (any count): one workgroup per pixel, samples in global scratch
 int ab_stack_deep_device(ab_ctx *ctx, const float *const *dplanes, const int64_t *ld, size_t n, int64_t rows, int64_t cols,
                          const ab_stack_config *cfg, float *out_dev, double *out_sum_dev, uint32_t *out_cnt_dev, bool median_only);
-int ab_stack_pair_device(ab_ctx *ctx, const float *const *dplanes, size_t n, int64_t rows, int64_t cols, const ab_stack_config *cfg,
-                         float *out_dev, bool median_only);
+// stack_pair.hip (+ stack_duo.hip, stack_quad.hip): 129 .. 1024 contiguous frames, two to eight lanes per pixel; dplanes is a HOST array
+int ab_stack_pair_device(ab_ctx *ctx, const StackPlan &plan, const float *const *dplanes, size_t n, int64_t rows, int64_t cols,
+                         const ab_stack_config *cfg, float *out_dev, bool median_only);
 // stack_wide.hip: the pixels a 513 .. 1024-frame fast pass (stack_quad.hip, eight lanes per pixel) handed over -- 2048 lists of `cap`
 // pixel indices each -- one wave per pixel, the oracle's arithmetic; leaves the lists empty.  table_dev: DEVICE array of >= n plane pointers
 int ab_stack_wide_list_device(ab_ctx *ctx, const float *const *table_dev, size_t n, int64_t rows, int64_t cols, const ab_stack_config *cfg, float *out_dev,
                               bool median_only, unsigned int *list_count, const int *list, unsigned int cap);
+// Host blocks the engines share (stack_sigma_clip.hip).  One plane of +inf of at least `total` pixels stands in for the frames a pointer
+// table is short of (a non-finite sample is what the algorithm ignores, combine.rs:170-175): filled when allocated and when it grows.
+int ab_stack_inf_plane(ab_ctx *ctx, int64_t total, const float **plane);
+// AB_STACK_LIST_SLOTS lists of pixel indices in workspace `ws_slot`: a fast pass of `waves` waves of `px_wave` pixels each appends to
+// list (wave index & (slots - 1)), rotated, so a list holds at most ceil(waves / slots) waves' worth.  The list pass leaves every
+// counter at zero again: always_clear = false clears a fresh workspace only.
+struct ab_stack_lists {
+    unsigned int *count, *ticket;
+    int *list;
+    unsigned int cap;
+};
+int ab_stack_lists_setup(ab_ctx *ctx, int ws_slot, int64_t waves, int64_t px_wave, bool always_clear, ab_stack_lists *out);
+// under AB_TRACE (developer aid): how many pixels the fast pass handed over -- on stderr and in AB_FB_STACK_GENERAL_PIXELS
+int ab_stack_lists_trace(ab_ctx *ctx, const ab_stack_lists &lists, int64_t total);
 
 static inline int ab_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 

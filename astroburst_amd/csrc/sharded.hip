@@ -14,10 +14,6 @@
 
 #include <algorithm>
 
-int ab_stack_device(ab_ctx *ctx, const float *const *dplanes, const int64_t *ld, size_t n, int64_t rows, int64_t cols,
-                    const ab_stack_config *cfg, float *out_dev, double *out_sum_dev, uint32_t *out_cnt_dev, uint64_t *out_rejected,
-                    bool median_only);
-
 namespace {
 
 __global__ void sum_counters_kernel(const unsigned long long *__restrict__ counters, int n, unsigned long long *__restrict__ out) {

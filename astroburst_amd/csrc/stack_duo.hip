@@ -1,13 +1,13 @@
-// The FAST pass of a 129 .. 512-frame kappa-sigma stack on gfx950: two lanes per pixel, the default engine's running sums.
+// The FAST pass of a 129 .. 256-frame kappa-sigma stack on gfx950: two lanes per pixel, the default engine's running sums.
 //
 // sigma_clip_combine (core/stacking/combine.rs:14-92) for the frame counts of deep light stacks and master calibration stacks.
 // Round 5 kept 129 .. 256 samples in ONE lane's registers (VGPRs + AGPRs: one wave per SIMD, 8 .. 9 cycles per instruction because a
 // lone wave cannot issue back to back, and nothing to hide the 256 loads behind: 10.6 ms for 256 x 4096^2) and ran 257 .. 512 through
 // stack_pair.hip's oracle arithmetic (two f64 chains of 512 additions per iteration: 58 ms).  Here, as in stack_pair.hip, lanes 2k
-// and 2k + 1 share pixel k of the wave's 32 and hold H = 128 (129 .. 256 frames: 256 registers, TWO waves per SIMD) or H = 256
-// (257 .. 512 frames) samples each:
-//   * gather: the even lane takes frames 0 .. R - 1, the odd lane frames R .. 2R - 1 (R = the frame-count class, a multiple of 16 or
-//     32: wires R .. H - 1 are +inf pads known at compile time -- no loads, and SortNet<H>::sort_fused_n<R> drops their operations;
+// and 2k + 1 share pixel k of the wave's 32 and hold H = 128 samples each (256 registers, TWO waves per SIMD; 257 .. 512 frames take
+// four lanes of 128, stack_quad.hip -- two lanes of H = 256 took 36 ms against 15 for 512 x 4096^2 and are retired):
+//   * gather: the even lane takes frames 0 .. R - 1, the odd lane frames R .. 2R - 1 (R = the frame-count class, a multiple of 16:
+//     wires R .. H - 1 are +inf pads known at compile time -- no loads, and SortNet<H>::sort_fused_n<R> drops their operations;
 //     frames n .. 2R - 1 read a plane of +inf); each lane sorts its samples, one cross step + an in-lane bitonic merge leave sorted
 //     ranks 0 .. H - 1 in the even lane and H .. 2H - 1 in the odd lane (stack_pair.hpp);
 //   * median and MAD at a compile-time position: every pixel of this kernel holds all n samples finite (the others are handed over,
@@ -31,30 +31,6 @@
 using namespace abpair;
 
 namespace {
-
-template <int OP>  // 1 min, 2 max (signed)
-__device__ __forceinline__ int wave_reduce_i32(int x) {
-    constexpr int id = OP == 1 ? 0x7fffffff : (int)0x80000000;
-    auto op = [](int a, int b) { return OP == 1 ? min(a, b) : max(a, b); };
-    x = op(x, __builtin_amdgcn_update_dpp(id, x, 0x111, 0xf, 0xf, false));
-    x = op(x, __builtin_amdgcn_update_dpp(id, x, 0x112, 0xf, 0xf, false));
-    x = op(x, __builtin_amdgcn_update_dpp(id, x, 0x114, 0xf, 0xf, false));
-    x = op(x, __builtin_amdgcn_update_dpp(id, x, 0x118, 0xf, 0xf, false));
-    x = op(x, __builtin_amdgcn_update_dpp(id, x, 0x142, 0xa, 0xf, false));
-    x = op(x, __builtin_amdgcn_update_dpp(id, x, 0x143, 0xc, 0xf, false));
-    return __builtin_amdgcn_readlane(x, 63);
-}
-
-// sqrt(v) for the iteration's sigma, of which only the f32 rounding is used (stack_sigma_clip.hip: sqrt_for_sigma)
-__device__ __forceinline__ double sqrt_for_sigma(double v) {
-    const double y = __builtin_amdgcn_rsq(v);
-    const double g = v * y;
-    const double e = __builtin_fma(-g, g, v);
-    const double r = __builtin_fma(e, 0.5 * y, g);
-    return v > 0.0 ? r : 0.0;
-}
-
-__device__ __forceinline__ void nop_fence(float &x) { asm volatile("s_nop 1" : "+v"(x)); }
 
 // median (combine.rs:38-40) and MAD (combine.rs:42-46) of a pair that holds n finite samples with n / 2 = M: ranks 0 .. H - 1 in the
 // even lane, H .. n - 1 in the odd lane.  MAD = the (M + 1)-th smallest deviation = min over the windows [p, p + M] of sorted samples
@@ -122,20 +98,6 @@ __device__ __forceinline__ float median_dispatch(const float (&v)[H], bool odd, 
     } else {
         constexpr int MID = (LO + HI) / 2;
         return M <= MID ? median_dispatch<H, LO, MID>(v, odd, M) : median_dispatch<H, MID + 1, HI>(v, odd, M);
-    }
-}
-
-// hand the pixel to the list pass: one atomic per wave, kListSlots counters (stack_sigma_clip.hip)
-__device__ __forceinline__ void hand_over(const PairArgs &a, bool d, int lane, int64_t g) {
-    const unsigned long long m = __ballot(d);
-    if (m) {
-        const int leader = (int)__builtin_ctzll(m);
-        const unsigned int w = blockIdx.x;
-        const unsigned int slot = (w + (w / kListSlots) * 977u) & (kListSlots - 1);
-        unsigned int base = 0;
-        if (lane == leader) base = atomicAdd(&a.list_count[slot], (unsigned int)__builtin_popcountll(m));
-        base = __shfl(base, leader, 64);
-        if (d) a.list[(size_t)slot * a.list_cap + base + (unsigned int)__builtin_popcountll(m & ((1ull << lane) - 1ull))] = (int)g;
     }
 }
 
@@ -373,38 +335,28 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(H == 128 ? 2
 
     hand_over(a, writer && defer, lane, g);
 
-    // rejection count: one atomic per wave, spread over kRejSlots counters (summed by the host)
-    int r = (writer && !defer) ? (int)rej : 0;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) r += __shfl_xor(r, off, 64);
-    if (lane == 0 && r != 0) atomicAdd(&a.rejected[blockIdx.x & (kRejSlots - 1)], (unsigned long long)r);
+    AB_TALLY_REJECTED(a.rejected, (writer && !defer) ? (int)rej : 0);
 }
 
 }  // namespace
 
-int ab_stack_duo_launch(ab_ctx *ctx, int H, int R, const PairArgs &args) {
+int ab_stack_duo_launch(ab_ctx *ctx, int R, const PairArgs &args) {
     const dim3 grid((unsigned)((args.total + 31) / 32)), block(64);
-#define AB_DUO_CASE(HV, RV)                                                                              \
-    if (H == HV && R == RV) {                                                                            \
-        if (args.median_only)                                                                            \
-            hipLaunchKernelGGL((stack_duo_fast_kernel<HV, RV, true>), grid, block, 0, ctx->stream, args); \
-        else                                                                                             \
-            hipLaunchKernelGGL((stack_duo_fast_kernel<HV, RV>), grid, block, 0, ctx->stream, args);       \
-        AB_HIP(ctx, hipGetLastError());                                                                  \
-        return AB_OK;                                                                                    \
+#define AB_DUO_CASE(RV)                                                                                   \
+    if (R == RV) {                                                                                        \
+        if (args.median_only)                                                                             \
+            hipLaunchKernelGGL((stack_duo_fast_kernel<128, RV, true>), grid, block, 0, ctx->stream, args); \
+        else                                                                                              \
+            hipLaunchKernelGGL((stack_duo_fast_kernel<128, RV>), grid, block, 0, ctx->stream, args);       \
+        AB_HIP(ctx, hipGetLastError());                                                                   \
+        return AB_OK;                                                                                     \
     }
 #ifndef AB_DUO_ONE_CLASS  // (tests/test_abi_cpu.py walks the listing of ONE instance: the others are the same code at other constants)
-    AB_DUO_CASE(128, 80)
-    AB_DUO_CASE(128, 96)
-    AB_DUO_CASE(128, 128)
-#ifdef AB_DEV_ABLATION  // (257 .. 512 frames take four lanes per pixel, stack_quad.hip; AB_STACK_NO_QUAD=1 on a developer build: 36 ms against 15 for 512 frames)
-    AB_DUO_CASE(256, 160)
-    AB_DUO_CASE(256, 192)
-    AB_DUO_CASE(256, 224)
-    AB_DUO_CASE(256, 256)
+    AB_DUO_CASE(80)
+    AB_DUO_CASE(96)
+    AB_DUO_CASE(128)
 #endif
-#endif
-    AB_DUO_CASE(128, 112)
+    AB_DUO_CASE(112)
 #undef AB_DUO_CASE
-    return ab_set_error(ctx, AB_ERR_INVALID, "internal: no two-lane kernel for %d samples per lane in class %d", H, R);
+    return ab_set_error(ctx, AB_ERR_INVALID, "internal: no two-lane kernel for class %d", R);
 }

@@ -28,6 +28,7 @@
 // workgroup (70.7 ms: the instruction cache was not the limit).  What would help is two waves per SIMD: four lanes per pixel
 // with 128 samples each.
 #include "stack_pair.hpp"
+#include "stack_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -301,50 +302,41 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(H == 128 ? 2
         if (!valid) g = a.total - 1;
         r = (int)pair_pixel<H, MEDIAN_ONLY>(a, buf, g, valid);
     }
-    // rejection count: one atomic per wave, spread over kRejSlots counters (summed by the host)
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) r += __shfl_xor(r, off, 64);
-    if (threadIdx.x == 0 && r != 0) atomicAdd(&a.rejected[blockIdx.x & (kRejSlots - 1)], (unsigned long long)r);
+    AB_TALLY_REJECTED(a.rejected, r);
+}
+
+// H = samples per lane; grid: one wave per 32 pixels, or kListSlots * kListWaves waves in list mode
+void launch_pair_kernel(ab_ctx *ctx, int H, bool median_only, dim3 grid, const PairArgs &a) {
+    const dim3 block(64);
+    if (H == 128 && median_only)
+        hipLaunchKernelGGL((stack_pair_kernel<128, true>), grid, block, 0, ctx->stream, a);
+    else if (H == 128)
+        hipLaunchKernelGGL((stack_pair_kernel<128, false>), grid, block, 0, ctx->stream, a);
+    else if (median_only)
+        hipLaunchKernelGGL((stack_pair_kernel<256, true>), grid, block, 0, ctx->stream, a);
+    else
+        hipLaunchKernelGGL((stack_pair_kernel<256, false>), grid, block, 0, ctx->stream, a);
 }
 
 }  // namespace
 
 // dplanes: HOST array of n device pointers (128 < n <= 1024), contiguous planes of rows x cols; counters already cleared by the caller.
-// The default engine (and its median combine): a fast multi-lane pass -- two lanes per pixel for 129 .. 256 frames (stack_duo.hip), four
-// for 257 .. 512, eight for 513 .. 1024 (stack_quad.hip) -- then the oracle's arithmetic over the pixels it handed over (this file's
-// kernel in list mode up to 512 frames, stack_wide.hip's wave-per-pixel kernel beyond).  AB_STACK_EXACT=1 (129 .. 512 frames): this
-// file's kernel over all pixels.
-int ab_stack_pair_device(ab_ctx *ctx, const float *const *dplanes, size_t n, int64_t rows, int64_t cols, const ab_stack_config *cfg,
-                         float *out_dev, bool median_only) {
+// plan (stack_plan.hpp): kEnginePair -- this file's kernel over all pixels (AB_STACK_EXACT=1); kEngineDuo / kEngineQuad -- a fast multi-lane
+// pass, then the oracle's arithmetic over the pixels it handed over (this file's kernel in list mode, stack_wide.hip's beyond 512 frames).
+int ab_stack_pair_device(ab_ctx *ctx, const StackPlan &plan, const float *const *dplanes, size_t n, int64_t rows, int64_t cols,
+                         const ab_stack_config *cfg, float *out_dev, bool median_only) {
     AB_CHECK(ctx, n > 128 && n <= 1024, "the multi-lane stack takes 129 .. 1024 frames (got %zu)", n);
-    const int H = n > 256 ? 256 : 128;  // samples per lane of THIS file's kernel (129 .. 512 frames)
-    const bool fast = !ctx->stack_exact;  // (the median combine too: a pixel with every sample finite needs the sort and one register)
-    AB_CHECK(ctx, fast || n <= 512, "internal: the exact engine of %zu frames is the wave-per-pixel kernel's", n);
+    AB_CHECK(ctx, plan.engine == kEnginePair || plan.engine == kEngineDuo || plan.engine == kEngineQuad, "internal: not a multi-lane plan");
+    const int H = plan.h;  // samples per lane of THIS file's kernel (129 .. 512 frames)
     constexpr size_t kTab = 1024;  // [0, kTab): the fast pass's table (frames, then the +inf plane); [kTab, kTab + 512): this file's kernel's
     void *ws = nullptr;
     AB_TRY(ab_workspace(ctx, AB_WS_STACK_WIDE, (kTab + 512) * sizeof(float *), &ws));
     // the tables are tiny; a blocking copy keeps the host array's lifetime out of the picture
     AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    // frames the stack is short of: ONE plane of +inf stands in for all of them (a non-finite sample is exactly what the
-    // algorithm ignores, combine.rs:170-175; the pad reads stay in L2) -- every load of the kernel is unconditional
+    // frames the stack is short of: the plane of +inf stands in for all of them -- every load of the kernels is unconditional
     const int64_t total = rows * cols;
     const float *inf_plane = nullptr;
-    {
-        float *ip = nullptr;
-        const void *before = ctx->ws[AB_WS_STACK_INF];
-        const size_t had = ctx->ws_bytes[AB_WS_STACK_INF];
-        AB_TRY(ab_workspace(ctx, AB_WS_STACK_INF, (size_t)total * sizeof(float), (void **)&ip));
-        if (ip != before || had < (size_t)total * sizeof(float))
-            AB_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)ip, 0x7f800000, ctx->ws_bytes[AB_WS_STACK_INF] / sizeof(float), ctx->stream));
-        inf_plane = ip;
-    }
-    // frame-count classes of the fast pass: R frames per lane, a multiple of 16 (H / 8 with two lanes): the pads' loads and network
-    // operations vanish.  (AB_STACK_NO_QUAD=1 on a developer build: 257 .. 512 frames on two lanes with 256 samples each.)
-    static const bool no_quad = ab_dev_env("AB_STACK_NO_QUAD") != nullptr;
-    const bool quad = fast && n > 256 && (n > 512 || !no_quad);
-    const size_t lanes = n > 512 ? 8 : (quad ? 4 : 2);
-    const int cw = quad ? 16 : H / 8;
-    const int R = fast ? (int)(((n + lanes - 1) / lanes + (size_t)cw - 1) / (size_t)cw) * cw : H;
+    AB_TRY(ab_stack_inf_plane(ctx, total, &inf_plane));
     std::vector<const float *> table(kTab + 512);
     for (size_t i = 0; i < kTab; ++i) table[i] = i < n ? dplanes[i] : inf_plane;
     for (size_t i = 0; i < 512; ++i) table[kTab + i] = table[i];
@@ -361,64 +353,33 @@ int ab_stack_pair_device(ab_ctx *ctx, const float *const *dplanes, size_t n, int
     a.out = out_dev;
     a.rejected = ctx->counters;
     a.median_only = median_only ? 1 : 0;
-    const dim3 grid((unsigned)((a.total + 31) / 32)), block(64);
-    if (!fast) {  // the exact engine (AB_STACK_EXACT=1) and the median combine: every pixel through the oracle's arithmetic
-        if (H == 128 && median_only)
-            hipLaunchKernelGGL((stack_pair_kernel<128, true>), grid, block, 0, ctx->stream, a);
-        else if (H == 128)
-            hipLaunchKernelGGL((stack_pair_kernel<128, false>), grid, block, 0, ctx->stream, a);
-        else if (median_only)
-            hipLaunchKernelGGL((stack_pair_kernel<256, true>), grid, block, 0, ctx->stream, a);
-        else
-            hipLaunchKernelGGL((stack_pair_kernel<256, false>), grid, block, 0, ctx->stream, a);
+    if (plan.engine == kEnginePair) {  // every pixel through the oracle's arithmetic
+        launch_pair_kernel(ctx, H, median_only, dim3((unsigned)((a.total + 31) / 32)), a);
         AB_HIP(ctx, hipGetLastError());
         return AB_OK;
     }
-    // the lists: slot = wave index & (kListSlots - 1) (rotated), so a slot holds at most ceil(waves / kListSlots) waves' worth of pixels
-    // (the fast pass's waves: 32 pixels each with two lanes per pixel, 16 with four and the grid rounded up to a multiple of 8)
-    const int64_t px_wave = 64 / (int64_t)lanes;
-    const int64_t waves = quad ? ((total + px_wave - 1) / px_wave + 7) / 8 * 8 : (total + 31) / 32;
-    const unsigned int cap = (unsigned int)(((waves + kListSlots - 1) / kListSlots) * px_wave);
-    char *lw = nullptr;
-    const void *before = ctx->ws[AB_WS_STACK_PAIR_LISTS];
-    AB_TRY(ab_workspace(ctx, AB_WS_STACK_PAIR_LISTS, (size_t)2 * kListSlots * sizeof(unsigned int) + (size_t)kListSlots * cap * sizeof(int), (void **)&lw));
-    a.list_count = (unsigned int *)lw;
-    a.list_ticket = a.list_count + kListSlots;
-    a.list = (int *)(lw + (size_t)2 * kListSlots * sizeof(unsigned int));
-    a.list_cap = cap;
-    // (the list pass leaves every counter at zero again, but a call that failed between the two passes would not have: 16 KB, in
-    // stream order, in front of a kernel of milliseconds)
-    (void)before;
-    AB_HIP(ctx, hipMemsetAsync(a.list_count, 0, 2 * kListSlots * sizeof(unsigned int), ctx->stream));
+    // the lists (the fast pass's waves: 32 pixels each with two lanes per pixel, 16 / 8 with four / eight and the grid a multiple of 8).
+    // Always cleared (16 KB, in stream order): a call that failed between the two passes would not have left the counters at zero
+    const int64_t px_wave = 64 / plan.lanes;
+    const int64_t waves = plan.engine == kEngineQuad ? ((total + px_wave - 1) / px_wave + 7) / 8 * 8 : (total + 31) / 32;
+    ab_stack_lists lists;
+    AB_TRY(ab_stack_lists_setup(ctx, AB_WS_STACK_PAIR_LISTS, waves, px_wave, true, &lists));
+    a.list_count = lists.count;
+    a.list_ticket = lists.ticket;
+    a.list = lists.list;
+    a.list_cap = lists.cap;
     PairArgs f = a;
     f.p = (const float *const *)ws;
-    f.half = R;
-    if (quad)
-        AB_TRY(ab_stack_quad_launch(ctx, (int)lanes, R, f));
+    f.half = plan.r;
+    if (plan.engine == kEngineQuad)
+        AB_TRY(ab_stack_quad_launch(ctx, plan.lanes, plan.r, f));
     else
-        AB_TRY(ab_stack_duo_launch(ctx, H, R, f));
-    if (ab_env("AB_TRACE")) {  // developer aid: how many pixels the fast pass handed over
-        std::vector<unsigned int> cnt(kListSlots, 0);
-        AB_HIP(ctx, hipMemcpyAsync(cnt.data(), a.list_count, kListSlots * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
-        AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        unsigned long long tot = 0, mx = 0;
-        for (unsigned int c : cnt) tot += c, mx = c > mx ? c : mx;
-        ab_count_fallback(ctx, AB_FB_STACK_GENERAL_PIXELS, tot);
-        fprintf(stderr, "[ab_trace] two-lane stack: %llu of %lld pixels handed to the list pass (%.2f %%), fullest list %llu of %u\n", tot, (long long)total,
-                100.0 * (double)tot / (double)total, mx, cap);
-    }
-    if (n > 512)  // the wave-per-pixel kernel walks the lists
-        return ab_stack_wide_list_device(ctx, (const float *const *)ws, n, rows, cols, cfg, out_dev, median_only, a.list_count, a.list, cap);
+        AB_TRY(ab_stack_duo_launch(ctx, plan.r, f));
+    AB_TRY(ab_stack_lists_trace(ctx, lists, total));
+    if (plan.list == kListWide16)  // the wave-per-pixel kernel walks the lists
+        return ab_stack_wide_list_device(ctx, (const float *const *)ws, n, rows, cols, cfg, out_dev, median_only, a.list_count, a.list, lists.cap);
     a.walk_lists = 1;
-    const dim3 lgrid(kListSlots * kListWaves);
-    if (H == 128 && median_only)
-        hipLaunchKernelGGL((stack_pair_kernel<128, true>), lgrid, block, 0, ctx->stream, a);
-    else if (H == 128)
-        hipLaunchKernelGGL((stack_pair_kernel<128, false>), lgrid, block, 0, ctx->stream, a);
-    else if (median_only)
-        hipLaunchKernelGGL((stack_pair_kernel<256, true>), lgrid, block, 0, ctx->stream, a);
-    else
-        hipLaunchKernelGGL((stack_pair_kernel<256, false>), lgrid, block, 0, ctx->stream, a);
+    launch_pair_kernel(ctx, plan.list == kListPair128 ? 128 : 256, median_only, dim3(kListSlots * kListWaves), a);
     AB_HIP(ctx, hipGetLastError());
     return AB_OK;
 }

@@ -1,7 +1,8 @@
-// Shared by the two-lanes-per-pixel stacking kernels (stack_pair.hip: the oracle's arithmetic word for word; stack_duo.hip: the fast
-// engine's running sums): H samples per lane, lanes 2k and 2k + 1 share pixel k of the wave's 32.
+// Shared by the multi-lane stacking kernels (stack_pair.hip: two lanes per pixel, the oracle's arithmetic word for word; stack_duo.hip
+// and stack_quad.hip: two, four or eight lanes per pixel, the fast engine's running sums): H samples per lane, lanes 2k and 2k + 1
+// share pixel k of the wave's 32.
 #pragma once
-#include "ab_common.hpp"
+#include "stack_shared.hpp"
 
 #include "sort_ops.hpp"
 #define AB_CE(a, b)                       \
@@ -24,11 +25,12 @@
 
 namespace abpair {
 
+using namespace abstack;
+
 constexpr double kMadToSigma = 1.4826;  // types/constants.rs:7
-constexpr int kRejSlots = AB_REJ_SLOTS;
 // pixels the fast kernel hands to the oracle-arithmetic kernel: lists by wave index (one same-address atomic per deferring wave
 // would serialise at ~12 ns each: stack_sigma_clip.hip), kListWaves one-wave workgroups walking each list
-constexpr int kListSlots = 2048;
+constexpr int kListSlots = AB_STACK_LIST_SLOTS;
 constexpr int kListWaves = 2;
 
 struct PairArgs {
@@ -71,16 +73,19 @@ __device__ __forceinline__ void dpp_fence(float (&v)[H]) {
                      "+v"(v[i + 7]));
 }
 
-// Compiler fence (no instructions): the sample vector looks rewritten, so LLVM does not hoist H f32->f64 conversions out of
-// the clipping loop (stack_sigma_clip.hip: launder)
-template <int H>
-__device__ __forceinline__ void launder(float (&v)[H]) {
-#pragma unroll
-    for (int i = 0; i < H; i += 8)
-        asm volatile("" : "+v"(v[i]), "+v"(v[i + 1]), "+v"(v[i + 2]), "+v"(v[i + 3]), "+v"(v[i + 4]), "+v"(v[i + 5]), "+v"(v[i + 6]),
-                     "+v"(v[i + 7]));
+// hand the pixel to the list pass: one atomic per wave, kListSlots counters (here, not in stack_shared.hpp: it writes through PairArgs)
+__device__ __forceinline__ void hand_over(const PairArgs &a, bool d, int lane, int64_t g) {
+    const unsigned long long m = __ballot(d);
+    if (m) {
+        const int leader = (int)__builtin_ctzll(m);
+        const unsigned int w = blockIdx.x;
+        const unsigned int slot = (w + (w / kListSlots) * 977u) & (kListSlots - 1);
+        unsigned int base = 0;
+        if (lane == leader) base = atomicAdd(&a.list_count[slot], (unsigned int)__builtin_popcountll(m));
+        base = __shfl(base, leader, 64);
+        if (d) a.list[(size_t)slot * a.list_cap + base + (unsigned int)__builtin_popcountll(m & ((1ull << lane) - 1ull))] = (int)g;
+    }
 }
-__device__ __forceinline__ void opaque(int &a, int &b) { asm volatile("" : "+v"(a), "+v"(b)); }
 
 // in-lane bitonic merge of a bitonic sequence of H (ascending result): log2 H half-cleaner stages.  (One function per stage: as
 // two nested `#pragma unroll` loops the body exceeds the pragma's size limit, the outer loop stays a loop, and the samples live
@@ -123,9 +128,8 @@ __device__ __forceinline__ void cross_step(float (&v)[H], bool odd) {
 
 }  // namespace abpair
 
-// stack_duo.hip: the fast pass of a 129 .. 512-frame stack (H = 128 or 256 samples per lane, the class R of frames per lane);
-// the arguments' table holds 2 R pointers
-int ab_stack_duo_launch(ab_ctx *ctx, int H, int R, const abpair::PairArgs &args);
+// stack_duo.hip: the fast pass of a 129 .. 256-frame stack (128 samples per lane, class R); the arguments' table holds 2 R pointers
+int ab_stack_duo_launch(ab_ctx *ctx, int R, const abpair::PairArgs &args);
 // stack_quad.hip: the fast pass of a 257 .. 512-frame (L = 4 lanes per pixel) or 513 .. 1024-frame (L = 8) stack, 128 samples per lane
 // (class R of frames per lane); the table holds L R pointers
 int ab_stack_quad_launch(ab_ctx *ctx, int L, int R, const abpair::PairArgs &args);

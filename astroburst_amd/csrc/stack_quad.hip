@@ -92,15 +92,6 @@ __device__ __forceinline__ float grp_bcast(float x, int lane) {
     }
 }
 
-__device__ __forceinline__ double sqrt_for_sigma(double v) {  // stack_sigma_clip.hip
-    const double y = __builtin_amdgcn_rsq(v);
-    const double g = v * y;
-    const double e = __builtin_fma(-g, g, v);
-    const double r = __builtin_fma(e, 0.5 * y, g);
-    return v > 0.0 ? r : 0.0;
-}
-__device__ __forceinline__ void nop_fence(float &x) { asm volatile("s_nop 1" : "+v"(x)); }
-
 // v[i] against the partner lane's v[127 - i]: a lane keeps the smaller (sel = -inf) or the larger (sel = +inf) of each pair
 template <int CTRL>
 __device__ __forceinline__ void cross_rev(float (&v)[HQ], float sel) {
@@ -176,20 +167,6 @@ __device__ __forceinline__ float median_dispatch(const float (&v)[HQ], int lane,
     } else {
         constexpr int MID = (LO + HI) / 2;
         return M <= MID ? median_dispatch<L, LO, MID>(v, lane, M) : median_dispatch<L, MID + 1, HI>(v, lane, M);
-    }
-}
-
-// hand the pixel to the list pass: one atomic per wave, kListSlots counters (stack_sigma_clip.hip)
-__device__ __forceinline__ void hand_over(const PairArgs &a, bool d, int lane, int64_t g) {
-    const unsigned long long m = __ballot(d);
-    if (m) {
-        const int leader = (int)__builtin_ctzll(m);
-        const unsigned int w = blockIdx.x;
-        const unsigned int slot = (w + (w / kListSlots) * 977u) & (kListSlots - 1);
-        unsigned int base = 0;
-        if (lane == leader) base = atomicAdd(&a.list_count[slot], (unsigned int)__builtin_popcountll(m));
-        base = __shfl(base, leader, 64);
-        if (d) a.list[(size_t)slot * a.list_cap + base + (unsigned int)__builtin_popcountll(m & ((1ull << lane) - 1ull))] = (int)g;
     }
 }
 
@@ -431,11 +408,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 
     hand_over(a, writer && defer, lane, g);
 
-    // rejection count: one atomic per wave, spread over kRejSlots counters (summed by the host)
-    int r = (writer && !defer) ? (int)rej : 0;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) r += __shfl_xor(r, off, 64);
-    if (lane == 0 && r != 0) atomicAdd(&a.rejected[blockIdx.x & (kRejSlots - 1)], (unsigned long long)r);
+    AB_TALLY_REJECTED(a.rejected, (writer && !defer) ? (int)rej : 0);
 }
 
 }  // namespace

@@ -26,7 +26,8 @@
 //     per wave                                                  (combine.rs:158,181)
 //
 // HBM traffic is the algorithmic minimum: 4*N*P bytes read once, 4*P written.
-#include "ab_common.hpp"
+#include "stack_plan.hpp"
+#include "stack_shared.hpp"
 
 #include <cmath>
 
@@ -99,10 +100,12 @@ __device__ __forceinline__ float ab_pinf() {
 
 namespace {
 
-constexpr int kMaxFrames = 256;  // 65 .. 256: 2 / 4 registers of plane pointers, one wave per SIMD (see launch of NP = 128 / 256)
+using namespace abstack;  // launder, opaque, wave_reduce_i32, sqrt_for_sigma
+
+constexpr int kMaxFrames = 256;  // (the table's size is part of the kernarg layout; the deepest kernel, NP = 128, reads 2 registers of plane pointers)
 constexpr int kMaxStrided = 64;  // ragged row strides only exist for the <= 64-frame kernels (deeper stacks are DIRECT or wide)
 constexpr int kRejSlots = AB_REJ_SLOTS;  // rejection counters (see the kernel epilogue)
-constexpr int kDeferSlots = 2048;        // deferred-pixel lists (same reason: no hot atomic address)
+constexpr int kDeferSlots = AB_STACK_LIST_SLOTS;  // deferred-pixel lists (same reason: no hot atomic address)
 constexpr unsigned int kGenWaves = 2;    // general pass: single-wave workgroups per deferred-pixel list (a list holds ~65 pixels on the bench stack, 109 at most)
 #ifndef AB_STACK_DEFER_CHUNKS
 #define AB_STACK_DEFER_CHUNKS 2
@@ -135,23 +138,6 @@ struct StackArgs {
     int identity;                    // is_identity_scaling(bscale, bzero) (reader.rs:36-39)
     double bscale, bzero;
 };
-
-// Compiler fences (no instructions).  launder() makes the sample vector look rewritten so LLVM
-// does not hoist 64 f32->f64 conversions (128 VGPRs) out of the clipping loop; opaque() stops it
-// from keeping 64 interval masks alive in SGPRs across the passes of one iteration.
-template <int NP>
-__device__ __forceinline__ void launder(float (&v)[NP]) {
-    if constexpr (NP >= 8) {
-#pragma unroll
-        for (int i = 0; i < NP; i += 8)
-            asm volatile("" : "+v"(v[i]), "+v"(v[i + 1]), "+v"(v[i + 2]), "+v"(v[i + 3]), "+v"(v[i + 4]),
-                         "+v"(v[i + 5]), "+v"(v[i + 6]), "+v"(v[i + 7]));
-    } else {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) asm volatile("" : "+v"(v[i]));
-    }
-}
-__device__ __forceinline__ void opaque(int &a, int &b) { asm volatile("" : "+v"(a), "+v"(b)); }
 
 // sum over sorted positions a..b of (double)v[i], ascending, one f64 add per element; the f32
 // select happens before the conversion (x + 0.0 is exact).
@@ -325,20 +311,6 @@ __device__ __forceinline__ ClipResult clip_exact(float (&v)[NP], int n, float me
 // variance differs from the two-pass value by a few ulp(f64), i.e. the f32 sigma is identical
 // except with probability ~1e-8 per pixel -- far inside the 1e-5 contract, and measured in
 // tests/ against engine A and the oracle.
-// wave reductions on DPP moves (row_shr 1/2/4/8, row_bcast 15 / 31; lanes without a source take the identity) and one v_readlane:
-// VALU only, where the __shfl_xor butterfly is six dependent ds_bpermute round trips
-template <int OP>  // 0 sum, 1 min, 2 max (signed)
-__device__ __forceinline__ int wave_reduce_i32(int x) {
-    constexpr int id = OP == 1 ? 0x7fffffff : (OP == 2 ? (int)0x80000000 : 0);
-    auto op = [](int a, int b) { return OP == 0 ? a + b : (OP == 1 ? min(a, b) : max(a, b)); };
-    x = op(x, __builtin_amdgcn_update_dpp(id, x, 0x111, 0xf, 0xf, false));
-    x = op(x, __builtin_amdgcn_update_dpp(id, x, 0x112, 0xf, 0xf, false));
-    x = op(x, __builtin_amdgcn_update_dpp(id, x, 0x114, 0xf, 0xf, false));
-    x = op(x, __builtin_amdgcn_update_dpp(id, x, 0x118, 0xf, 0xf, false));
-    x = op(x, __builtin_amdgcn_update_dpp(id, x, 0x142, 0xa, 0xf, false));
-    x = op(x, __builtin_amdgcn_update_dpp(id, x, 0x143, 0xc, 0xf, false));
-    return __builtin_amdgcn_readlane(x, 63);
-}
 template <int NP>
 __device__ __forceinline__ int wave_max_i32(int x) {
     return wave_reduce_i32<2>(x);
@@ -522,24 +494,6 @@ __device__ __forceinline__ double div_by_count(double x, double nn, int n, doubl
     } else {
         return x / nn;
     }
-}
-
-// sqrt(v) for the iteration's sigma, which only its f32 rounding is used of.  v_rsq_f64 is good to ~2^-27; g = v y, one residual
-// step g + (v - g^2) y / 2 brings it to ~2^-52 -- a few ulp(f64) short of the correctly rounded root, which the compiler's 15-
-// instruction expansion (scaling, three refinement pairs, class fix-up) delivers.  That is the same order as the fast engine's
-// running-sum variance itself (a few ulp(f64) from the two-pass value, see above), 28 binary orders below the f32 the result is
-// rounded to: the f32 sigma differs from the oracle's with probability ~1e-8 per pixel, as before.  No scaling: a variance of f32
-// samples lies between 2^-298 and 2^+262 or is 0 (-> 0: the caller's max with 1e-10 takes over).  (AB_STACK_IEEE_SQRT: the library call.)
-__device__ __forceinline__ double sqrt_for_sigma(double v) {
-#ifdef AB_STACK_IEEE_SQRT
-    return sqrt(v);
-#else
-    const double y = __builtin_amdgcn_rsq(v);
-    const double g = v * y;
-    const double e = __builtin_fma(-g, g, v);
-    const double r = __builtin_fma(e, 0.5 * y, g);
-    return v > 0.0 ? r : 0.0;
-#endif
 }
 
 // Per-lane state of the fast engine between the median/MAD clip and the iterations on running sums.
@@ -783,13 +737,9 @@ __device__ __forceinline__ ClipResult clip_fast(float (&v)[NP], int n, float med
 // need more appends its pixel to one of kDeferSlots lists and writes nothing.  kGeneralPass re-runs the complete
 // algorithm for exactly those pixels (a few percent), densely packed into waves.  kPlain is the single-pass kernel
 // (partial frame sets, ragged strides, the exact engine).  All three produce bit-identical pixels.
-// NREAL (<= NP): a frame-count CLASS of a padded stack -- slots NREAL .. NP - 1 are +inf pads known at compile time: their loads are
-// not issued and the sorting network runs as SortNet<NP>::sort_fused_n<NREAL> (operations on pad wires vanish).  129 .. 256 frames
-// in classes of 32: 200 frames sort 224 wires' worth of the 256-wire network instead of all of it.
-template <int NP, bool PARTIAL, bool EXACT, int STAGE, bool DIRECT, int MODE, int INPUT = kInNative, int NREAL = NP>
+template <int NP, bool PARTIAL, bool EXACT, int STAGE, bool DIRECT, int MODE, int INPUT = kInNative>
 __device__ __forceinline__ void stack_pixel(const StackArgs &args, int64_t g, const bool valid) {
     static_assert(INPUT == kInNative || DIRECT, "raw FITS planes are only read through the DIRECT gather");
-    static_assert(NREAL == NP || (DIRECT && INPUT == kInNative && NP > 64 && MODE == kPlain && NREAL < NP && NREAL % 8 == 0), "frame-count classes: the deep direct-gather kernels only");
     const int64_t total = args.rows * args.cols;
 
     int64_t y = 0, x = g;
@@ -840,7 +790,7 @@ __device__ __forceinline__ void stack_pixel(const StackArgs &args, int64_t g, co
             for (int f = 0; f < NP; ++f) nf = __builtin_fmaf(v[f], 0.0f, nf);
         }
     } else if constexpr (DIRECT) {
-        // deeper stacks (128 / 256 samples per lane) and raw FITS planes: the pointer table does not fit the scalar registers
+        // deeper stacks (128 samples per lane) and raw FITS planes: the pointer table does not fit the scalar registers
         // All NP frames present, contiguous, < 2^30 px: one vector load fetches the 64 plane pointers
         // (lane f reads p[f] straight from the kernarg segment), v_readlane broadcasts each into an
         // SGPR pair, and every sample load is `global_load_dword v, voffset, s[base]` -- no per-frame
@@ -863,12 +813,6 @@ __device__ __forceinline__ void stack_pixel(const StackArgs &args, int64_t g, co
         const uint32_t plane_bytes = ((uint32_t)total * kSampleBytes + 3u) & ~3u;
 #pragma unroll
         for (int f = 0; f < NP; ++f) {
-            if constexpr (NREAL < NP) {
-                if (f >= NREAL) {  // (compile time: the loop is unrolled) a pad of the frame-count class: no load
-                    v[f] = __builtin_inff();
-                    continue;
-                }
-            }
             const uint64_t base = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)phi[f >> 6], f & 63) << 32) |
                                   (uint32_t)__builtin_amdgcn_readlane((int)plo[f >> 6], f & 63);
             // buffer descriptor in 4 SGPRs -> `buffer_load_dword v, voffset, s[rsrc], 0 offen`
@@ -996,8 +940,6 @@ __device__ __forceinline__ void stack_pixel(const StackArgs &args, int64_t g, co
         };
         SortNet<NP>::sort_fused(v, hook);
         n -= lost;
-    } else if constexpr (NREAL < NP) {
-        SortNet<NP>::template sort_fused_n<NREAL>(v, [](auto) {});
     } else if constexpr (NP >= 8 && NP <= 256) {
         SortNet<NP>::sort_fused(v);
     } else {
@@ -1020,7 +962,7 @@ __device__ __forceinline__ void stack_pixel(const StackArgs &args, int64_t g, co
         med_mad_at<NP, NP / 2>(v, med, mad);  // the common case: every lane has all NP samples
     } else if (__all(m == __builtin_amdgcn_readfirstlane(m))) {
         // one position for the whole wave (a padded stack): no loop -- with the samples live around a back edge the
-        // 128 / 256-sample kernels lose ~4 ms per 4096^2 launch to register shuffling
+        // 128-sample kernel loses ~4 ms per 4096^2 launch to register shuffling
         med_mad_dispatch<NP, 0, NP / 2>(v, m, __builtin_amdgcn_readfirstlane(m), med, mad);
     } else {
         // (on a COPY of the samples: launder() makes the vector look rewritten, and if that were v itself the common path
@@ -1097,8 +1039,8 @@ __device__ __forceinline__ void stack_pixel(const StackArgs &args, int64_t g, co
         atomicAdd(&args.rejected[(blockIdx.x * 4u + (threadIdx.x >> 6)) & (kRejSlots - 1)], (unsigned long long)rej);
 }
 
-template <int NP, bool PARTIAL, bool EXACT, int STAGE = 99, bool DIRECT = false, int MODE = kPlain, int INPUT = kInNative, int NREAL = NP>
-__global__ __launch_bounds__(256, (EXACT || NP > 128) ? 1 : (NP > 64 ? 2 : AB_STACK_WAVES_PER_SIMD)) void stack_sigma_clip_kernel(const StackArgs args) {
+template <int NP, bool PARTIAL, bool EXACT, int STAGE = 99, bool DIRECT = false, int MODE = kPlain, int INPUT = kInNative>
+__global__ __launch_bounds__(256, EXACT ? 1 : (NP > 64 ? 2 : AB_STACK_WAVES_PER_SIMD)) void stack_sigma_clip_kernel(const StackArgs args) {
     if constexpr (MODE == kGeneralPass) {
         // ONE wave per workgroup, kGenWaves workgroups per list (launched with 64 threads).  With one 4-wave workgroup per list
         // (round 2) a list of ~65 pixels kept one wave busy and three wave slots empty until it finished: 2048 workgroups went
@@ -1109,7 +1051,7 @@ __global__ __launch_bounds__(256, (EXACT || NP > 128) ? 1 : (NP > 64 ? 2 : AB_ST
         for (unsigned int base = sub * 64u; base < cnt; base += 64u * kGenWaves) {
             const unsigned int k = base + threadIdx.x;
             const bool valid = k < cnt;
-            stack_pixel<NP, PARTIAL, EXACT, STAGE, DIRECT, MODE, INPUT, NREAL>(args, (int64_t)list[valid ? k : cnt - 1], valid);
+            stack_pixel<NP, PARTIAL, EXACT, STAGE, DIRECT, MODE, INPUT>(args, (int64_t)list[valid ? k : cnt - 1], valid);
         }
         // the last of the list's workgroups to get here leaves the list empty for the next launch.  (No fence: each workgroup's
         // own read of the count has returned before its ticket is taken -- the loop bound depends on it -- and a device-scope
@@ -1125,7 +1067,7 @@ __global__ __launch_bounds__(256, (EXACT || NP > 128) ? 1 : (NP > 64 ? 2 : AB_ST
         int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
         const bool valid = g < total;
         if (!valid) g = total - 1;
-        stack_pixel<NP, PARTIAL, EXACT, STAGE, DIRECT, MODE, INPUT, NREAL>(args, g, valid);
+        stack_pixel<NP, PARTIAL, EXACT, STAGE, DIRECT, MODE, INPUT>(args, g, valid);
     }
 }
 
@@ -1160,35 +1102,41 @@ void launch_raw(ab_ctx *ctx, const StackArgs &args, dim3 grid, dim3 block) {
 }
 
 template <int NP, bool PARTIAL, bool EXACT, int STAGE>
-void launch_np(ab_ctx *ctx, const StackArgs &args, dim3 grid, dim3 block) {
-    // DIRECT gather: no absent-frame slots, one row stride, byte offsets fit 32 bits
-    const bool direct = args.n == NP && args.contiguous && args.rows * args.cols < (int64_t(1) << 30);
+void launch_np(ab_ctx *ctx, const StackPlan &plan, const StackArgs &args, dim3 grid, dim3 block) {
     if constexpr (!EXACT && STAGE == 99 && NP >= 8) {
-        if (direct && args.defer_list) {  // two-pass mode: fast pass over every pixel, general pass over the deferred ones
+        if (plan.direct && args.defer_list) {  // two-pass mode: fast pass over every pixel, general pass over the deferred ones
             hipLaunchKernelGGL((stack_sigma_clip_kernel<NP, PARTIAL, EXACT, STAGE, true, kFastPass>), grid, block, 0, ctx->stream, args);
             hipLaunchKernelGGL((stack_sigma_clip_kernel<NP, PARTIAL, EXACT, STAGE, true, kGeneralPass>), dim3(kDeferSlots * kGenWaves), dim3(64), 0,
                                ctx->stream, args);
             return;
         }
     }
-    if (direct)
+    if (plan.direct)
         hipLaunchKernelGGL((stack_sigma_clip_kernel<NP, PARTIAL, EXACT, STAGE, true>), grid, block, 0, ctx->stream, args);
-    else
+    else if constexpr (NP <= 64)  // (NP = 128: launch_stack has checked plan.direct)
         hipLaunchKernelGGL((stack_sigma_clip_kernel<NP, PARTIAL, EXACT, STAGE, false>), grid, block, 0, ctx->stream, args);
 }
 
 template <bool PARTIAL, bool EXACT, int STAGE = 99>
-int launch_stack(ab_ctx *ctx, const StackArgs &args, int np) {
+int launch_stack(ab_ctx *ctx, const StackPlan &plan, const StackArgs &args) {
     const int64_t total = args.rows * args.cols;
     const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    switch (np) {
-        case 2: launch_np<2, PARTIAL, EXACT, STAGE>(ctx, args, grid, block); break;
-        case 4: launch_np<4, PARTIAL, EXACT, STAGE>(ctx, args, grid, block); break;
-        case 8: launch_np<8, PARTIAL, EXACT, STAGE>(ctx, args, grid, block); break;
-        case 16: launch_np<16, PARTIAL, EXACT, STAGE>(ctx, args, grid, block); break;
-        case 32: launch_np<32, PARTIAL, EXACT, STAGE>(ctx, args, grid, block); break;
-        case 64: launch_np<64, PARTIAL, EXACT, STAGE>(ctx, args, grid, block); break;
-        default: return ab_set_error(ctx, AB_ERR_INVALID, "internal: bad padded frame count %d", np);
+    switch (plan.np) {
+        case 2: launch_np<2, PARTIAL, EXACT, STAGE>(ctx, plan, args, grid, block); break;
+        case 4: launch_np<4, PARTIAL, EXACT, STAGE>(ctx, plan, args, grid, block); break;
+        case 8: launch_np<8, PARTIAL, EXACT, STAGE>(ctx, plan, args, grid, block); break;
+        case 16: launch_np<16, PARTIAL, EXACT, STAGE>(ctx, plan, args, grid, block); break;
+        case 32: launch_np<32, PARTIAL, EXACT, STAGE>(ctx, plan, args, grid, block); break;
+        case 64: launch_np<64, PARTIAL, EXACT, STAGE>(ctx, plan, args, grid, block); break;
+        case 128:  // 65 .. 128 plain frames, default engine or median
+            if constexpr (!PARTIAL && !EXACT) {
+                if (plan.direct) {  // (only the direct-gather kernels exist for 128 samples per lane)
+                    launch_np<128, PARTIAL, EXACT, STAGE>(ctx, plan, args, grid, block);
+                    break;
+                }
+            }
+            [[fallthrough]];
+        default: return ab_set_error(ctx, AB_ERR_INVALID, "internal: bad padded frame count %d", plan.np);
     }
     AB_HIP(ctx, hipGetLastError());
     return AB_OK;
@@ -1207,25 +1155,101 @@ static int read_rejected(ab_ctx *ctx, uint64_t *out) {
     return AB_OK;
 }
 
-// deferred-pixel lists of the two-pass mode: slot = wave index & 2047 (rotated), so a slot holds at most
-// ceil(waves / 2048) waves' worth of pixels
-static int setup_defer(ab_ctx *ctx, StackArgs *args, int64_t total) {
-    const int64_t waves = ((total + 255) / 256) * 4;
-    const unsigned int cap = (unsigned int)(((waves + kDeferSlots - 1) / kDeferSlots) * 64);
-    char *ws = nullptr;
-    const void *before = ctx->ws[AB_WS_STACK_DEFER];
-    AB_TRY(ab_workspace(ctx, AB_WS_STACK_DEFER, (size_t)2 * kDeferSlots * sizeof(unsigned int) + (size_t)kDeferSlots * cap * sizeof(int), (void **)&ws));
-    args->defer_count = (unsigned int *)ws;
-    args->defer_ticket = args->defer_count + kDeferSlots;
-    args->defer_list = (int *)(ws + (size_t)2 * kDeferSlots * sizeof(unsigned int));
-    args->defer_cap = cap;
-    // the general pass leaves every counter at zero again, so only a fresh workspace needs clearing
-    args->keep_counts = ab_env("AB_TRACE") ? 1 : 0;
-    if (ws != before || args->keep_counts) AB_HIP(ctx, hipMemsetAsync(args->defer_count, 0, 2 * kDeferSlots * sizeof(unsigned int), ctx->stream));
+int ab_stack_inf_plane(ab_ctx *ctx, int64_t total, const float **plane) {
+    float *ip = nullptr;
+    const void *before = ctx->ws[AB_WS_STACK_INF];
+    const size_t had = ctx->ws_bytes[AB_WS_STACK_INF];
+    AB_TRY(ab_workspace(ctx, AB_WS_STACK_INF, (size_t)total * sizeof(float), (void **)&ip));
+    if (ip != before || had < (size_t)total * sizeof(float))
+        AB_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)ip, 0x7f800000, ctx->ws_bytes[AB_WS_STACK_INF] / sizeof(float), ctx->stream));
+    *plane = ip;
     return AB_OK;
 }
 
-// Shared implementation.  dplanes: device pointers + row strides of the n frames.
+int ab_stack_lists_setup(ab_ctx *ctx, int ws_slot, int64_t waves, int64_t px_wave, bool always_clear, ab_stack_lists *out) {
+    constexpr int64_t kSlots = AB_STACK_LIST_SLOTS;
+    const unsigned int cap = (unsigned int)(((waves + kSlots - 1) / kSlots) * px_wave);
+    char *ws = nullptr;
+    const void *before = ctx->ws[ws_slot];
+    AB_TRY(ab_workspace(ctx, ws_slot, (size_t)2 * kSlots * sizeof(unsigned int) + (size_t)kSlots * cap * sizeof(int), (void **)&ws));
+    out->count = (unsigned int *)ws;
+    out->ticket = out->count + kSlots;
+    out->list = (int *)(ws + (size_t)2 * kSlots * sizeof(unsigned int));
+    out->cap = cap;
+    if (always_clear || ws != before) AB_HIP(ctx, hipMemsetAsync(out->count, 0, 2 * kSlots * sizeof(unsigned int), ctx->stream));
+    return AB_OK;
+}
+
+int ab_stack_lists_trace(ab_ctx *ctx, const ab_stack_lists &lists, int64_t total) {
+    if (!ab_env("AB_TRACE")) return AB_OK;
+    std::vector<unsigned int> cnt(AB_STACK_LIST_SLOTS, 0);
+    AB_HIP(ctx, hipMemcpyAsync(cnt.data(), lists.count, cnt.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+    AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    unsigned long long tot = 0, mx = 0;
+    for (unsigned int c : cnt) tot += c, mx = c > mx ? c : mx;
+    ab_count_fallback(ctx, AB_FB_STACK_GENERAL_PIXELS, tot);
+    fprintf(stderr, "[ab_trace] stack: %llu of %lld pixels handed to the list pass (%.2f %%), fullest list %llu of %u\n", tot, (long long)total,
+            100.0 * (double)tot / (double)total, mx, lists.cap);
+    return AB_OK;
+}
+
+// deferred-pixel lists of the two-pass mode (256-thread workgroups: four waves of 64 pixels).  The general pass leaves every counter
+// at zero again, so only a fresh workspace needs clearing -- unless AB_TRACE keeps the counts for the host to read
+static int setup_defer(ab_ctx *ctx, StackArgs *args, int64_t total) {
+    args->keep_counts = ab_env("AB_TRACE") ? 1 : 0;
+    ab_stack_lists lists;
+    AB_TRY(ab_stack_lists_setup(ctx, AB_WS_STACK_DEFER, ((total + 255) / 256) * 4, 64, args->keep_counts != 0, &lists));
+    args->defer_count = lists.count;
+    args->defer_ticket = lists.ticket;
+    args->defer_list = lists.list;
+    args->defer_cap = lists.cap;
+    return AB_OK;
+}
+
+// the kernel arguments of n frames (ld == nullptr: every row stride is cols)
+static void fill_stack_args(ab_ctx *ctx, const float *const *planes, const int64_t *ld, size_t n, int64_t rows, int64_t cols, const ab_stack_config *cfg,
+                            float *out_dev, double *out_sum_dev, uint32_t *out_cnt_dev, StackArgs &args) {
+    memset(&args, 0, sizeof args);
+    args.contiguous = 1;
+    for (size_t i = 0; i < n; ++i) {
+        args.p[i] = planes[i];
+        if (i < (size_t)kMaxStrided) args.ld[i] = ld ? ld[i] : cols;
+        if (ld && ld[i] != cols) args.contiguous = 0;
+    }
+    args.n = (int)n;
+    args.n_real = (int)n;
+    args.rows = rows;
+    args.cols = cols;
+    args.sigma_low = cfg->sigma_low;
+    args.sigma_high = cfg->sigma_high;
+    args.max_iter = cfg->max_iterations;
+    args.out = out_dev;
+    args.out_sum = out_sum_dev;
+    args.out_cnt = out_cnt_dev;
+    args.rejected = ctx->counters;
+}
+
+// kEngineLane: the +inf pads and the two-pass lists the plan asks for
+static int lane_extras(ab_ctx *ctx, StackPlan *plan, size_t n, int64_t total, int64_t cols, StackArgs &args) {
+    if (plan->pad_inf) {  // the kernel sees n == NP again (direct gather)
+        const float *inf_plane = nullptr;
+        AB_TRY(ab_stack_inf_plane(ctx, total, &inf_plane));
+        for (int f = (int)n; f < plan->np; ++f) {
+            args.p[f] = inf_plane;
+            if (f < kMaxStrided) args.ld[f] = cols;
+        }
+        args.n = plan->np;
+    }
+    if (plan->two_pass && ab_dev_env("AB_STACK_SINGLE_PASS")) {  // (developer A/B)
+        plan->two_pass = false;
+        plan->list = kListNone;
+    }
+    if (plan->two_pass) AB_TRY(setup_defer(ctx, &args, total));
+    return AB_OK;
+}
+
+// Shared implementation.  dplanes: device pointers + row strides of the n frames.  Check, plan (stack_plan.hpp), clear the counters,
+// record the events around the engine's kernels, read back.
 int ab_stack_device(ab_ctx *ctx, const float *const *dplanes, const int64_t *ld, size_t n, int64_t rows,
                     int64_t cols, const ab_stack_config *cfg, float *out_dev, double *out_sum_dev,
                     uint32_t *out_cnt_dev, uint64_t *out_rejected, bool median_only) {
@@ -1235,159 +1259,60 @@ int ab_stack_device(ab_ctx *ctx, const float *const *dplanes, const int64_t *ld,
     AB_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t total = rows * cols;
     const bool partial = out_sum_dev != nullptr;
-
+    bool contiguous = true, aligned16 = true;
+    for (size_t i = 0; i < n; ++i) {
+        contiguous = contiguous && ld[i] == cols;
+        aligned16 = aligned16 && ((uintptr_t)dplanes[i] & 15) == 0;
+    }
+    StackPlan plan = ab_stack_plan(n, total, contiguous, partial, median_only, ctx->stack_exact, ctx->stack_deep_from, aligned16);
     const bool first_chunk = !ctx->stack_keep_counters;  // (sharded.hip stacks in row chunks: the later ones add to the first one's counts and events)
     if (first_chunk) AB_HIP(ctx, hipMemsetAsync(ctx->counters, 0, kRejSlots * sizeof(unsigned long long), ctx->stream));
-    // 65 .. 128 contiguous frames, plain full-image stack: still one lane per pixel, 128 samples in registers (one wave per
-    // SIMD).  Everything else beyond 64 frames -- ragged strides, partial sums, the median combine, the exact engine, more
-    // than 128 frames -- takes one wave per pixel (stack_wide.hip).
-    bool contig_all = total < (int64_t(1) << 30);
-    for (size_t i = 0; i < n && contig_all; ++i) contig_all = ld[i] == cols;
-    const bool reg128 = n > 64 && n <= 256 && contig_all && !partial && !ctx->stack_exact;  // (and 129 .. 256; median_combine too)
-    // Round 6: 129 .. 256 contiguous frames take two lanes per pixel, 128 samples each, two waves per SIMD -- stack_duo.hip's fast pass
-    // for the default engine's stack and the median combine, stack_pair.hip's oracle-arithmetic kernel for AB_STACK_EXACT=1 (15.5 ms
-    // for 256 x 4096^2 where the wave-per-pixel kernel took 151).  AB_STACK_NO_DUO=1 (developer build) keeps round 5's routes.
-    static const bool no_duo = ab_dev_env("AB_STACK_NO_DUO") != nullptr;
-    const bool duo = n > 128 && n <= 256 && contig_all && !partial && !no_duo;
-    if (n > 64 && (!reg128 || duo)) {  // deeper than one lane's registers
+    StackArgs args;  // kEngineLane only
+    if (plan.engine == kEngineLane) {
+        fill_stack_args(ctx, dplanes, ld, n, rows, cols, cfg, out_dev, out_sum_dev, out_cnt_dev, args);
+        AB_TRY(lane_extras(ctx, &plan, n, total, cols, args));
+    }
+    const bool timed = plan.engine != kEngineSingle;  // (a single frame is a copy: ab_stack_last_kernel_ms speaks of multi-frame stacks)
+    if (timed) {
         for (hipEvent_t &e : ctx->stack_ev)
             if (!e) AB_HIP(ctx, hipEventCreate(&e));
         ctx->stack_ev_valid = false;
         if (first_chunk) AB_HIP(ctx, hipEventRecord(ctx->stack_ev[0], ctx->stream));
-        // 257 .. 512 contiguous frames, plain full-image stack or median combine: two lanes per pixel (stack_pair.hip), bit-identical
-        // to the wave-per-pixel kernel (AB_STACK_NO_PAIR=1 keeps that one); everything else: one wave per pixel (stack_wide.hip)
-        // 513 .. 4096: the wave-per-pixel kernel with 16 / 32 / 64 registers per lane; beyond: one workgroup per pixel, samples
-        // in global scratch (stack_deep.hip; a context created under AB_STACK_DEEP_FROM=k sends every stack of more than k >= 64 frames there: the tests do)
-        static const bool no_pair = ab_dev_env("AB_STACK_NO_PAIR") != nullptr;
-        static const bool no_octo = ab_dev_env("AB_STACK_NO_OCTO") != nullptr;  // (developer A/B: 513 .. 1024 frames one wave per pixel as before)
-        if (n > (size_t)ctx->stack_deep_from)
+    }
+    switch (plan.engine) {
+        case kEngineSingle: {
+            const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+            hipLaunchKernelGGL(stack_single_kernel, grid, block, 0, ctx->stream, dplanes[0], ld[0], rows, cols,
+                               partial ? nullptr : out_dev, out_sum_dev, out_cnt_dev);
+            AB_HIP(ctx, hipGetLastError());
+            break;
+        }
+        case kEngineLane:
+            if (median_only)
+                AB_TRY((launch_stack<false, false, 10>(ctx, plan, args)));
+            else if (ctx->stack_exact)
+                AB_TRY(partial ? (launch_stack<true, true>(ctx, plan, args)) : (launch_stack<false, true>(ctx, plan, args)));
+            else
+                AB_TRY(partial ? (launch_stack<true, false>(ctx, plan, args)) : (launch_stack<false, false>(ctx, plan, args)));
+            break;
+        case kEnginePair:
+        case kEngineDuo:
+        case kEngineQuad:
+            AB_TRY(ab_stack_pair_device(ctx, plan, dplanes, n, rows, cols, cfg, out_dev, median_only));
+            break;
+        case kEngineWide:
+            AB_TRY(ab_stack_wide_device(ctx, plan, dplanes, ld, contiguous, n, rows, cols, cfg, out_dev, out_sum_dev, out_cnt_dev, median_only));
+            break;
+        case kEngineDeep:
             AB_TRY(ab_stack_deep_device(ctx, dplanes, ld, n, rows, cols, cfg, out_dev, out_sum_dev, out_cnt_dev, median_only));
-        else if (duo || (n > 256 && n <= 512 && contig_all && !partial && !no_pair) ||
-                 (n > 512 && n <= 1024 && contig_all && !partial && !ctx->stack_exact && !no_octo))  // (eight lanes per pixel: stack_quad.hip)
-            AB_TRY(ab_stack_pair_device(ctx, dplanes, n, rows, cols, cfg, out_dev, median_only));
-        else
-            AB_TRY(ab_stack_wide_device(ctx, dplanes, ld, n, rows, cols, cfg, out_dev, out_sum_dev, out_cnt_dev, median_only));
-        AB_HIP(ctx, hipEventRecord(ctx->stack_ev[1], ctx->stream));
-        ctx->stack_ev_valid = true;
-        if (out_rejected) AB_TRY(read_rejected(ctx, out_rejected));
-        return AB_OK;
+            break;
+        default: return ab_set_error(ctx, AB_ERR_INVALID, "internal: no stacking engine %d", plan.engine);
     }
-    if (n == 1) {
-        const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-        hipLaunchKernelGGL(stack_single_kernel, grid, block, 0, ctx->stream, dplanes[0], ld[0], rows, cols,
-                           partial ? nullptr : out_dev, out_sum_dev, out_cnt_dev);
-        AB_HIP(ctx, hipGetLastError());
-    } else {
-        StackArgs args;
-        memset(&args, 0, sizeof args);
-        int contiguous = 1;
-        for (size_t i = 0; i < n; ++i) {
-            args.p[i] = dplanes[i];
-            if (i < (size_t)kMaxStrided) args.ld[i] = ld[i];
-            if (ld[i] != cols) contiguous = 0;
-        }
-        args.n = (int)n;
-    args.n_real = (int)n;
-        args.contiguous = contiguous;
-        args.rows = rows;
-        args.cols = cols;
-        args.sigma_low = cfg->sigma_low;
-        args.sigma_high = cfg->sigma_high;
-        args.max_iter = cfg->max_iterations;
-        args.out = out_dev;
-        args.out_sum = out_sum_dev;
-        args.out_cnt = out_cnt_dev;
-        args.rejected = ctx->counters;
-        int np = 2;
-        while (np < (int)n) np <<= 1;
-        bool padded = false;
-        // A frame count between two powers of two would run the padded kernel, whose per-frame `f < n` predicates make it
-        // 2-3x slower (37 frames: 2.7 ms against 1.3 ms for 64).  With contiguous planes the missing frames are aliased to
-        // one plane of +inf instead: a non-finite sample is exactly what the algorithm ignores (combine.rs:170-175), the
-        // kernel sees n == NP again (direct gather, two-pass mode), and the pad reads stay in L2.
-        if ((int)n < np && np >= 8 && contiguous && total < (int64_t(1) << 30)) {
-            float *inf_plane = nullptr;
-            const void *before = ctx->ws[AB_WS_STACK_INF];
-            const size_t had = ctx->ws_bytes[AB_WS_STACK_INF];
-            AB_TRY(ab_workspace(ctx, AB_WS_STACK_INF, (size_t)total * sizeof(float), (void **)&inf_plane));
-            if (inf_plane != before || had < (size_t)total * sizeof(float))
-                AB_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)inf_plane, 0x7f800000, ctx->ws_bytes[AB_WS_STACK_INF] / sizeof(float), ctx->stream));
-            for (int f = (int)n; f < np; ++f) {
-                args.p[f] = inf_plane;
-                if (f < kMaxStrided) args.ld[f] = cols;
-            }
-            args.n = np;
-            n = (size_t)np;
-            padded = true;
-        }
-        // (the fast pass of the two-pass mode only looks at sorted positions NP-4 .. NP-1 for the high end: on a padded stack
-        // those are pads and every pixel would be deferred, so padded stacks take the single-pass kernel)
-        if (!padded && !median_only && !ctx->stack_exact && (int)n == np && np >= 8 && contiguous && total < (int64_t(1) << 30) &&
-            !ab_dev_env("AB_STACK_SINGLE_PASS")) {
-            AB_TRY(setup_defer(ctx, &args, total));
-        }
-        for (hipEvent_t &e : ctx->stack_ev)
-            if (!e) AB_HIP(ctx, hipEventCreate(&e));
-        ctx->stack_ev_valid = false;
-        if (first_chunk) AB_HIP(ctx, hipEventRecord(ctx->stack_ev[0], ctx->stream));
-        if (np == 256) {  // 129 .. 256 contiguous frames: 256 samples per lane (VGPRs + AGPRs), single pass
-#ifndef AB_DEV_ABLATION
-            // (round 6: these frame counts take two lanes per pixel -- `duo` above; round 5's one-lane kernels are built into the
-            // developer library only, for the A/B under AB_STACK_NO_DUO=1)
-            return ab_set_error(ctx, AB_ERR_INVALID, "internal: %d frames reached the one-lane 256-sample route", args.n_real);
-#else
-            const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-            // frame-count classes of 32 (AB_STACK_NO_CLASSES=1: every count pays for 256): the pads' loads and the network's
-            // operations on pad wires are gone at compile time
-            static const bool no_classes = ab_dev_env("AB_STACK_NO_CLASSES") != nullptr;
-            const int cls = no_classes ? 256 : (args.n_real + 31) / 32 * 32;
-#define AB_LAUNCH_256(NREAL)                                                                                                               \
-    do {                                                                                                                                   \
-        if (median_only)                                                                                                                   \
-            hipLaunchKernelGGL((stack_sigma_clip_kernel<256, false, false, 10, true, kPlain, kInNative, NREAL>), grid, block, 0, ctx->stream, args); \
-        else                                                                                                                               \
-            hipLaunchKernelGGL((stack_sigma_clip_kernel<256, false, false, 99, true, kPlain, kInNative, NREAL>), grid, block, 0, ctx->stream, args); \
-    } while (0)
-            if (cls <= 160) AB_LAUNCH_256(160);
-            else if (cls == 192) AB_LAUNCH_256(192);
-            else if (cls == 224) AB_LAUNCH_256(224);
-            else AB_LAUNCH_256(256);
-#undef AB_LAUNCH_256
-            AB_HIP(ctx, hipGetLastError());
-#endif
-        } else if (np == 128) {  // reg128 (checked above): only the direct-gather kernels exist for 128 samples per lane
-            const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-            if (median_only) {
-                hipLaunchKernelGGL((stack_sigma_clip_kernel<128, false, false, 10, true>), grid, block, 0, ctx->stream, args);
-            } else if (args.defer_list) {
-                hipLaunchKernelGGL((stack_sigma_clip_kernel<128, false, false, 99, true, kFastPass>), grid, block, 0, ctx->stream, args);
-                hipLaunchKernelGGL((stack_sigma_clip_kernel<128, false, false, 99, true, kGeneralPass>), dim3(kDeferSlots * kGenWaves), dim3(64), 0, ctx->stream, args);
-            } else {
-                hipLaunchKernelGGL((stack_sigma_clip_kernel<128, false, false, 99, true>), grid, block, 0, ctx->stream, args);
-            }
-            AB_HIP(ctx, hipGetLastError());
-        } else if (median_only)
-            AB_TRY((launch_stack<false, false, 10>(ctx, args, np)));
-        else if (ctx->stack_exact)
-            AB_TRY(partial ? (launch_stack<true, true>(ctx, args, np)) : (launch_stack<false, true>(ctx, args, np)));
-        else
-            AB_TRY(partial ? (launch_stack<true, false>(ctx, args, np)) : (launch_stack<false, false>(ctx, args, np)));
+    if (timed) {
         AB_HIP(ctx, hipEventRecord(ctx->stack_ev[1], ctx->stream));
         ctx->stack_ev_valid = true;
     }
-    if (ab_env("AB_TRACE") && n > 1) {  // developer aid: how many pixels the fast pass handed to the general pass
-        std::vector<unsigned int> cnt(kDeferSlots, 0);
-        void *ws = ctx->ws[AB_WS_STACK_DEFER];
-        if (ws) {
-            AB_HIP(ctx, hipMemcpyAsync(cnt.data(), ws, kDeferSlots * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
-            AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            unsigned long long tot = 0, mx = 0;
-            for (unsigned int c : cnt) tot += c, mx = c > mx ? c : mx;
-            ab_count_fallback(ctx, AB_FB_STACK_GENERAL_PIXELS, tot);
-            fprintf(stderr, "[ab_trace] stack: %llu of %lld pixels deferred (%.2f %%), fullest list %llu\n", tot, (long long)total,
-                    100.0 * (double)tot / (double)total, mx);
-        }
-    }
+    if (plan.engine == kEngineLane && plan.two_pass) AB_TRY(ab_stack_lists_trace(ctx, {args.defer_count, args.defer_ticket, args.defer_list, args.defer_cap}, total));
     if (out_rejected) AB_TRY(read_rejected(ctx, out_rejected));
     return AB_OK;
 }
@@ -1476,23 +1401,10 @@ int ab_stack_sigma_clip_raw(ab_ctx *ctx, const void *const *raw_planes_dev, size
                             (long long)total);
     AB_HIP(ctx, hipSetDevice(ctx->device));
     AB_HIP(ctx, hipMemsetAsync(ctx->counters, 0, kRejSlots * sizeof(unsigned long long), ctx->stream));
-    StackArgs args;
-    memset(&args, 0, sizeof args);
-    for (size_t i = 0; i < n; ++i) {
+    for (size_t i = 0; i < n; ++i)
         AB_CHECK(ctx, raw_planes_dev[i] && ((uintptr_t)raw_planes_dev[i] & 3) == 0, "raw plane %zu is null or not 4-byte aligned", i);
-        args.p[i] = (const float *)raw_planes_dev[i];
-        args.ld[i] = out->cols;
-    }
-    args.n = (int)n;
-    args.n_real = (int)n;
-    args.contiguous = 1;
-    args.rows = out->rows;
-    args.cols = out->cols;
-    args.sigma_low = cfg->sigma_low;
-    args.sigma_high = cfg->sigma_high;
-    args.max_iter = cfg->max_iterations;
-    args.out = out->data;
-    args.rejected = ctx->counters;
+    StackArgs args;
+    fill_stack_args(ctx, (const float *const *)raw_planes_dev, nullptr, n, out->rows, out->cols, cfg, out->data, nullptr, nullptr, args);
     args.identity = std::fabs(bscale - 1.0) < 1e-15 && std::fabs(bzero) < 1e-15;
     if (!args.identity && bitpix == 16 && bscale == 1.0 && bzero == std::floor(bzero) && std::fabs(bzero) <= 8.0e6) args.identity = 2;
     args.bscale = bscale;

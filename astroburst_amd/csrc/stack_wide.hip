@@ -1,7 +1,7 @@
-// Per-pixel kappa-sigma stacking of MORE than 64 frames (65 .. 512) on gfx950.
+// Per-pixel kappa-sigma stacking of MORE than 64 frames (65 .. 4096) on gfx950.
 //
 // stack_sigma_clip.hip keeps a pixel's samples in one lane's registers, which ends at 64.  Here one WAVE owns a pixel:
-// lane l holds the samples of frames l, l + 64, ... (K = 2, 4 or 8 registers), the wave sorts its 64 K values with a
+// lane l holds the samples of frames l, l + 64, ... (K = 2 .. 64 registers), the wave sorts its 64 K values with a
 // bitonic network whose intra-lane stages use constant register indices and whose cross-lane stages are shuffles, and
 // everything sigma_clip_combine (core/stacking/combine.rs:14-92) needs is then a rank lookup (v_readlane) or a
 // wave-wide count.  The f64 sums run over the sorted survivors one by one in ascending order, exactly as the CPU
@@ -9,6 +9,7 @@
 // ~2000 instructions per pixel and uncoalesced gathers (one lane per plane): tens of milliseconds for 4096^2 x 128,
 // a fallback for deep stacks rather than a roofline kernel.
 #include "ab_common.hpp"
+#include "stack_plan.hpp"
 #include "wave_sort.hpp"
 
 #include <algorithm>
@@ -356,25 +357,14 @@ __global__ __launch_bounds__(256) void stack_wide_list_kernel(const WideArgs a, 
     if (threadIdx.x == 0) list_count[blockIdx.x] = 0;
 }
 
-}  // namespace
-
-// dplanes / ld are HOST arrays of n entries (64 < n <= 512); counters already cleared by the caller
-int ab_stack_wide_device(ab_ctx *ctx, const float *const *dplanes, const int64_t *ld, size_t n, int64_t rows, int64_t cols,
-                         const ab_stack_config *cfg, float *out_dev, double *out_sum_dev, uint32_t *out_cnt_dev, bool median_only) {
-    AB_CHECK(ctx, n > 64 && n <= 4096, "the wave-per-pixel stack takes 65 .. 4096 frames (got %zu)", n);
-    void *ws = nullptr;
-    AB_TRY(ab_workspace(ctx, AB_WS_STACK_WIDE, n * (sizeof(float *) + sizeof(int64_t)), &ws));
-    // the tables are tiny; a blocking copy keeps the host arrays' lifetime out of the picture
-    AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    AB_HIP(ctx, hipMemcpy(ws, dplanes, n * sizeof(float *), hipMemcpyHostToDevice));
-    AB_HIP(ctx, hipMemcpy((char *)ws + n * sizeof(float *), ld, n * sizeof(int64_t), hipMemcpyHostToDevice));
+// p / ld: DEVICE tables of n entries (ld may be null when every plane is contiguous)
+WideArgs fill_wide_args(ab_ctx *ctx, const float *const *p, const int64_t *ld, size_t n, bool contiguous, int64_t rows, int64_t cols,
+                        const ab_stack_config *cfg, float *out_dev, double *out_sum_dev, uint32_t *out_cnt_dev, bool median_only) {
     WideArgs a;
-    a.p = (const float *const *)ws;
-    a.ld = (const int64_t *)((char *)ws + n * sizeof(float *));
+    a.p = p;
+    a.ld = ld;
     a.n = (int)n;
-    a.contiguous = 1;
-    for (size_t i = 0; i < n; ++i)
-        if (ld[i] != cols) a.contiguous = 0;
+    a.contiguous = contiguous ? 1 : 0;
     a.rows = rows;
     a.cols = cols;
     a.sigma_low = cfg->sigma_low;
@@ -385,77 +375,71 @@ int ab_stack_wide_device(ab_ctx *ctx, const float *const *dplanes, const int64_t
     a.out_cnt = out_cnt_dev;
     a.rejected = ctx->counters;
     a.median_only = median_only ? 1 : 0;
+    return a;
+}
+
+template <int K, bool TREE>
+int launch_wide_tile(ab_ctx *ctx, dim3 tgrid, const WideArgs &a) {
+    AB_HIP(ctx, hipFuncSetAttribute((const void *)stack_wide_tile_kernel<K, TREE>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
+    hipLaunchKernelGGL((stack_wide_tile_kernel<K, TREE>), tgrid, dim3(64 * tile_waves<K>()), 65536, ctx->stream, a);
+    return AB_OK;
+}
+// the LDS-staged kernels exist for K >= 8 (257 frames and more), the four-pixel ones for K <= 8 (up to 512 frames): stack_plan.hpp
+template <int K>
+int launch_wide(ab_ctx *ctx, const StackPlan &plan, dim3 grid, dim3 tgrid, const WideArgs &a) {
+    if constexpr (K >= 8) {
+        if (plan.gather == kGatherTiled) return plan.tree ? launch_wide_tile<K, true>(ctx, tgrid, a) : launch_wide_tile<K, false>(ctx, tgrid, a);
+    }
+    if constexpr (K <= 8) {
+        if (plan.gather == kGatherQuad) {
+            hipLaunchKernelGGL(stack_wide_quad_kernel<K>, grid, dim3(256), 0, ctx->stream, a);
+            return AB_OK;
+        }
+    }
+    if (plan.gather != kGatherScalar) return ab_set_error(ctx, AB_ERR_INVALID, "internal: no gather %d with %d registers per lane", plan.gather, K);
+    hipLaunchKernelGGL(stack_wide_kernel<K>, grid, dim3(256), 0, ctx->stream, a);
+    return AB_OK;
+}
+
+}  // namespace
+
+// dplanes / ld are HOST arrays of n entries (64 < n <= 4096; contiguous: every ld == cols); counters already cleared by the caller.  plan (stack_plan.hpp): K and the
+// gather -- groups of 256 / K pixels staged through LDS (two workgroups of 64 KB per CU), four pixels per 16-byte load, or one at a time
+int ab_stack_wide_device(ab_ctx *ctx, const StackPlan &plan, const float *const *dplanes, const int64_t *ld, bool contiguous, size_t n, int64_t rows, int64_t cols,
+                         const ab_stack_config *cfg, float *out_dev, double *out_sum_dev, uint32_t *out_cnt_dev, bool median_only) {
+    AB_CHECK(ctx, n > 64 && n <= 4096, "the wave-per-pixel stack takes 65 .. 4096 frames (got %zu)", n);
+    AB_CHECK(ctx, plan.engine == kEngineWide, "internal: not a wave-per-pixel plan");
+    void *ws = nullptr;
+    AB_TRY(ab_workspace(ctx, AB_WS_STACK_WIDE, n * (sizeof(float *) + sizeof(int64_t)), &ws));
+    // the tables are tiny; a blocking copy keeps the host arrays' lifetime out of the picture
+    AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    AB_HIP(ctx, hipMemcpy(ws, dplanes, n * sizeof(float *), hipMemcpyHostToDevice));
+    AB_HIP(ctx, hipMemcpy((char *)ws + n * sizeof(float *), ld, n * sizeof(int64_t), hipMemcpyHostToDevice));
+    const WideArgs a = fill_wide_args(ctx, (const float *const *)ws, (const int64_t *)((char *)ws + n * sizeof(float *)), n, contiguous, rows, cols, cfg,
+                                      out_dev, out_sum_dev, out_cnt_dev, median_only);
     const int64_t total = rows * cols;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((total + 3) / 4, (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8));
-    bool quad = a.contiguous && (total & 3) == 0;
-    for (size_t i = 0; i < n && quad; ++i) quad = ((uintptr_t)dplanes[i] & 15) == 0;
-    // 513 .. 4096 frames (K = 16, 32, 64 registers per lane and array): the same wave-per-pixel definition, one pixel at a time
-    // (four pixels' worth of 16-byte loads would not fit the register file beside two sort arrays)
-    // (the LDS-staged form: contiguous 16-byte aligned planes, whole groups of 16 pixels; two workgroups of 64 KB per CU)
-    const int64_t gpx = n > 2048 ? 4 : (n > 1024 ? 8 : (n > 512 ? 16 : 32));  // pixels per group of stack_wide_tile_kernel<64 / 32 / 16 / 8>
-    const bool tiled = quad && total % gpx == 0 && n > 256;  // (257 .. 512 frames reach this file only where stack_pair.hip does not take them)
-    const int tgrid = (int)std::max<int64_t>(1, std::min<int64_t>(total / 4, (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 2));
-    // the tree sums: the default engine here; the partial sums of the sharded estimator and AB_STACK_EXACT=1 keep the ascending chain
-    const bool tree = !ctx->stack_exact && !out_sum_dev;
-#define AB_WIDE_TILE(KK, TT)                                                                                                                   \
-    do {                                                                                                                                       \
-        AB_HIP(ctx, hipFuncSetAttribute((const void *)stack_wide_tile_kernel<KK, TT>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));  \
-        hipLaunchKernelGGL((stack_wide_tile_kernel<KK, TT>), dim3(tgrid), dim3(64 * tile_waves<KK>()), 65536, ctx->stream, a);                                 \
-    } while (0)
-    if (tiled && n > 2048) {
-        if (tree) AB_WIDE_TILE(64, true); else AB_WIDE_TILE(64, false);
-    } else if (tiled && n > 1024) {
-        if (tree) AB_WIDE_TILE(32, true); else AB_WIDE_TILE(32, false);
-    } else if (tiled && n > 512) {
-        if (tree) AB_WIDE_TILE(16, true); else AB_WIDE_TILE(16, false);
-    } else if (tiled) {
-        if (tree) AB_WIDE_TILE(8, true); else AB_WIDE_TILE(8, false);
-#undef AB_WIDE_TILE
-    } else if (n > 2048) {
-        hipLaunchKernelGGL(stack_wide_kernel<64>, dim3(grid), dim3(256), 0, ctx->stream, a);
-    } else if (n > 1024) {
-        hipLaunchKernelGGL(stack_wide_kernel<32>, dim3(grid), dim3(256), 0, ctx->stream, a);
-    } else if (n > 512) {
-        hipLaunchKernelGGL(stack_wide_kernel<16>, dim3(grid), dim3(256), 0, ctx->stream, a);
-    } else if (quad) {
-        if (n <= 128)
-            hipLaunchKernelGGL(stack_wide_quad_kernel<2>, dim3(grid), dim3(256), 0, ctx->stream, a);
-        else if (n <= 256)
-            hipLaunchKernelGGL(stack_wide_quad_kernel<4>, dim3(grid), dim3(256), 0, ctx->stream, a);
-        else
-            hipLaunchKernelGGL(stack_wide_quad_kernel<8>, dim3(grid), dim3(256), 0, ctx->stream, a);
-    } else if (n <= 128) {
-        hipLaunchKernelGGL(stack_wide_kernel<2>, dim3(grid), dim3(256), 0, ctx->stream, a);
-    } else if (n <= 256) {
-        hipLaunchKernelGGL(stack_wide_kernel<4>, dim3(grid), dim3(256), 0, ctx->stream, a);
-    } else {
-        hipLaunchKernelGGL(stack_wide_kernel<8>, dim3(grid), dim3(256), 0, ctx->stream, a);
+    const int64_t cus = ctx->cu_count > 0 ? ctx->cu_count : 256;
+    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((total + 3) / 4, cus * 8)));
+    const dim3 tgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>(total / 4, cus * 2)));
+    switch (plan.k) {
+        case 2: AB_TRY(launch_wide<2>(ctx, plan, grid, tgrid, a)); break;
+        case 4: AB_TRY(launch_wide<4>(ctx, plan, grid, tgrid, a)); break;
+        case 8: AB_TRY(launch_wide<8>(ctx, plan, grid, tgrid, a)); break;
+        case 16: AB_TRY(launch_wide<16>(ctx, plan, grid, tgrid, a)); break;
+        case 32: AB_TRY(launch_wide<32>(ctx, plan, grid, tgrid, a)); break;
+        case 64: AB_TRY(launch_wide<64>(ctx, plan, grid, tgrid, a)); break;
+        default: return ab_set_error(ctx, AB_ERR_INVALID, "internal: no wave-per-pixel kernel with %d registers per lane", plan.k);
     }
     AB_HIP(ctx, hipGetLastError());
     return AB_OK;
 }
 
-
 // table_dev: DEVICE array of at least n plane pointers (contiguous planes of rows x cols); 2048 lists (stack_pair.hpp: kListSlots)
 int ab_stack_wide_list_device(ab_ctx *ctx, const float *const *table_dev, size_t n, int64_t rows, int64_t cols, const ab_stack_config *cfg, float *out_dev,
                               bool median_only, unsigned int *list_count, const int *list, unsigned int cap) {
     AB_CHECK(ctx, n > 512 && n <= 1024, "internal: the list pass of the wave-per-pixel kernel takes 513 .. 1024 frames (got %zu)", n);
-    WideArgs a;
-    a.p = table_dev;
-    a.ld = nullptr;
-    a.n = (int)n;
-    a.contiguous = 1;
-    a.rows = rows;
-    a.cols = cols;
-    a.sigma_low = cfg->sigma_low;
-    a.sigma_high = cfg->sigma_high;
-    a.max_iter = cfg->max_iterations;
-    a.out = out_dev;
-    a.out_sum = nullptr;
-    a.out_cnt = nullptr;
-    a.rejected = ctx->counters;
-    a.median_only = median_only ? 1 : 0;
-    hipLaunchKernelGGL(stack_wide_list_kernel<16>, dim3(2048), dim3(256), 0, ctx->stream, a, list_count, list, cap);
+    const WideArgs a = fill_wide_args(ctx, table_dev, nullptr, n, true, rows, cols, cfg, out_dev, nullptr, nullptr, median_only);
+    hipLaunchKernelGGL(stack_wide_list_kernel<16>, dim3(AB_STACK_LIST_SLOTS), dim3(256), 0, ctx->stream, a, list_count, list, cap);
     AB_HIP(ctx, hipGetLastError());
     return AB_OK;
 }

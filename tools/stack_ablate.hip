@@ -5,9 +5,16 @@
 #include "../astroburst_amd/csrc/stack_sigma_clip.hip"
 // (the > 64-frame path lives in stack_wide.hip, whose file-scope constants collide with stack_sigma_clip.hip's when both are
 // pulled into one translation unit; this tool never stacks more than 64 frames)
-int ab_stack_wide_device(ab_ctx *ctx, const float *const *, const int64_t *, size_t, int64_t, int64_t, const ab_stack_config *, float *, double *,
-                         uint32_t *, bool) {
+int ab_stack_wide_device(ab_ctx *ctx, const StackPlan &, const float *const *, const int64_t *, bool, size_t, int64_t, int64_t, const ab_stack_config *, float *,
+                         double *, uint32_t *, bool) {
     return ab_set_error(ctx, AB_ERR_INVALID, "stack_ablate: the wide path is not linked into this tool");
+}
+int ab_stack_pair_device(ab_ctx *ctx, const StackPlan &, const float *const *, size_t, int64_t, int64_t, const ab_stack_config *, float *, bool) {
+    return ab_set_error(ctx, AB_ERR_INVALID, "stack_ablate: the multi-lane path is not linked into this tool");
+}
+int ab_stack_deep_device(ab_ctx *ctx, const float *const *, const int64_t *, size_t, int64_t, int64_t, const ab_stack_config *, float *, double *, uint32_t *,
+                         bool) {
+    return ab_set_error(ctx, AB_ERR_INVALID, "stack_ablate: the deep path is not linked into this tool");
 }
 
 __global__ void fill_kernel(float *p, int64_t n, uint32_t seed, float cr_rate) {
