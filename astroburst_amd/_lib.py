@@ -174,6 +174,15 @@ class RLResultC(C.Structure):  # RLResult's scalars (deconvolution.rs:214-219)
     _fields_ = [("iterations_run", C.c_size_t), ("convergence", C.c_double)]
 
 
+class WaveletConfigC(C.Structure):  # WaveletConfig (wavelet.rs:10-15): the threshold list as pointer + count
+    _fields_ = [("num_scales", C.c_size_t), ("thresholds", C.POINTER(C.c_float)), ("num_thresholds", C.c_size_t),
+                ("linear_denoise", C.c_int32)]
+
+
+class WaveletResultC(C.Structure):  # WaveletResult's scalars (wavelet.rs:27-33)
+    _fields_ = [("scales_processed", C.c_size_t), ("noise_estimate", C.c_double)]
+
+
 class DrizzleConfigC(C.Structure):  # DrizzleConfig (types/stacking.rs) + the affine estimate's num_threads
     _fields_ = [("scale", C.c_double), ("pixfrac", C.c_double), ("kernel", C.c_int32), ("sigma_low", C.c_float), ("sigma_high", C.c_float),
                 ("sigma_iterations", C.c_size_t), ("align", C.c_int32), ("alignment_method", C.c_int32), ("num_threads", C.c_int32)]
@@ -393,6 +402,8 @@ def lib() -> C.CDLL:
                                           C.POINTER(StfParamsC)]
     L.ab_generate_gaussian_psf.argtypes = [C.c_size_t, C.c_float, C.POINTER(C.c_float)]
     L.ab_richardson_lucy.argtypes = [vp, pp, pp, C.POINTER(RLConfigC), pp, C.POINTER(RLResultC)]
+    L.ab_wavelet_scale_thresholds.argtypes = [C.c_double, C.POINTER(WaveletConfigC), C.POINTER(C.c_float)]
+    L.ab_wavelet_denoise.argtypes = [vp, pp, C.POINTER(WaveletConfigC), pp, C.POINTER(WaveletResultC)]
     L.ab_drizzle_output_dims.argtypes = [pp, C.c_size_t, C.POINTER(DrizzleConfigC), i64p, i64p, i64p, i64p]
     L.ab_drizzle_frames.argtypes = [vp, pp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(DrizzleConfigC), pp, pp, C.POINTER(DrizzleResultC)]
     L.ab_drizzle_stack.argtypes = [vp, pp, C.c_size_t, C.POINTER(DrizzleConfigC), pp, pp, C.POINTER(C.c_double), C.POINTER(DrizzleResultC)]

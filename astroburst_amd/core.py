@@ -219,6 +219,25 @@ def generate_gaussian_psf(size: int, sigma: float) -> np.ndarray:
     return out
 
 
+def _wavelet_config(num_scales, thresholds, linear_denoise, keep):
+    """ab_wavelet_config over a float array that `keep` holds alive for the length of the call"""
+    th = (C.c_float * max(len(thresholds), 1))(*[float(t) for t in thresholds])
+    keep.append(th)
+    return _lib.WaveletConfigC(max(int(num_scales), 0), th if len(thresholds) else None, len(thresholds), 1 if linear_denoise else 0)
+
+
+def wavelet_scale_thresholds(noise_sigma: float, thresholds=(3.0, 2.5, 2.0, 1.5, 1.0)) -> np.ndarray:
+    """The eight per-scale f32 thresholds wavelet_denoise derives from noise_sigma (wavelet.rs:93-99, :218-225): scale j takes
+    thresholds[j], beyond the list its last entry, of an empty list 1.0 (host scalar maths in the library: no GPU)."""
+    keep = []
+    cfg = _wavelet_config(8, thresholds, True, keep)
+    out = np.zeros(8, np.float32)
+    rc = _lib.lib().ab_wavelet_scale_thresholds(float(noise_sigma), C.byref(cfg), out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != _lib.AB_OK:
+        raise AstroBurstError(rc, "ab_wavelet_scale_thresholds: bad arguments")
+    return out
+
+
 def _drizzle_config(scale, pixfrac, kernel, sigma_low, sigma_high, sigma_iterations, align=False, alignment_method=0, num_threads=8):
     kernel = DRIZZLE_KERNELS[kernel.lower()] if isinstance(kernel, str) else int(kernel)
     alignment_method = DRIZZLE_ALIGNMENT[alignment_method.lower()] if isinstance(alignment_method, str) else int(alignment_method)
@@ -1586,6 +1605,25 @@ class Context:
         res = _lib.RLResultC()
         self._check(self._L.ab_richardson_lucy(self._h, C.byref(pi), C.byref(pk), C.byref(cfg), C.byref(po), C.byref(res)))
         return out, int(res.iterations_run), float(res.convergence)
+
+    # ---- core/imaging/wavelet.rs ---------------------------------------------------------------------------
+    wavelet_scale_thresholds = staticmethod(wavelet_scale_thresholds)
+
+    def wavelet_denoise(self, image, num_scales=5, thresholds=(3.0, 2.5, 2.0, 1.5, 1.0), linear_denoise=True, out=None):
+        """wavelet_denoise (wavelet.rs:41-133) -> (image, scales_processed, noise_estimate), bit for bit the reference's.  image and
+        out: numpy (host) or CUDA tensors (device), CPU tensors accepted; the result is of the image's kind unless `out` is given.
+        num_scales is clamped to [1, 8]; the defaults are WaveletConfig::default()."""
+        keep = []
+        pi = self._plane(image, keep)
+        if out is None:
+            out = self._new_like(image, pi.rows, pi.cols)
+        if not _is_torch(out) and (out.shape != (pi.rows, pi.cols) or out.dtype != np.float32 or not out.flags.c_contiguous):
+            raise AstroBurstError(_lib.AB_ERR_INVALID, f"output must be a contiguous float32 array of {pi.rows}x{pi.cols}")
+        po = self._out_plane(out, keep, pi.rows, pi.cols)
+        cfg = _wavelet_config(num_scales, thresholds, linear_denoise, keep)
+        res = _lib.WaveletResultC()
+        self._check(self._L.ab_wavelet_denoise(self._h, C.byref(pi), C.byref(cfg), C.byref(po), C.byref(res)))
+        return out, int(res.scales_processed), float(res.noise_estimate)
 
     # ---- core/stacking/drizzle.rs -------------------------------------------------------------------------
     drizzle_output_dims = staticmethod(drizzle_output_dims)

@@ -57,6 +57,7 @@ enum {
     AB_WS_DETECT_CAND,        // the candidate lists the tile pass of a registration batch leaves for the labelling pass (detect.hip: TileCand)
     AB_WS_DECONV,             // Richardson-Lucy: chain state, padded PSF weights, per-workgroup partials, the ratio plane (deconv.hip)
     AB_WS_DRIZZLE,            // drizzle: the frame table, per-workgroup rejected partials, the long-list path's sample columns (drizzle.hip)
+    AB_WS_WAVELET,            // wavelet denoising: the horizontal pass's plane and the smoothed planes c_1 .. c_S (wavelet.hip)
     AB_WS_SLOTS
 };
 

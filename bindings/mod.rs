@@ -41,6 +41,7 @@ use crate::core::imaging::calibration_pipeline::{
 use crate::core::imaging::curves::LevelsParams;
 use crate::core::imaging::masked_stretch::{MaskedStretchConfig, MaskedStretchResult, MaskedStretchRgbResult};
 use crate::core::imaging::star_mask::{StarMaskConfig, StarMaskResult};
+use crate::core::imaging::wavelet::{WaveletConfig, WaveletResult};
 use crate::core::stacking::calibration::CalibrationConfig;
 use crate::infra::progress::ProgressHandle;
 use crate::types::compose::{AlignMethod, ChannelStats, DimensionHarmonize, RgbComposeConfig, WhiteBalance};
@@ -707,6 +708,38 @@ pub fn richardson_lucy(hip: &Hip, image: &impl PlaneSrc, psf: &impl PlaneSrc, co
     let mut po = out.ab_mut();
     hip.with_progress(progress, || hip.check(unsafe { sys::ab_richardson_lucy(hip.ctx, &image.ab(), &psf.ab(), &cfg, &mut po, &mut res) }))?;
     Ok(RLResult { image: out, iterations_run: res.iterations_run, convergence: res.convergence, elapsed_ms: start.elapsed().as_millis() as u64 })
+}
+
+// ---- core/imaging/wavelet.rs (wavelet_denoise_cmd) ------------------------------------------------------------------------------------------------------
+/// the C view of a WaveletConfig; it borrows the threshold list, so it must not outlive `config`
+fn wavelet_cfg(config: &WaveletConfig) -> sys::ab_wavelet_config {
+    sys::ab_wavelet_config {
+        num_scales: config.num_scales,
+        // (the generated struct drops C's const: the library only reads the list)
+        thresholds: if config.thresholds.is_empty() { std::ptr::null_mut() } else { config.thresholds.as_ptr() as *mut f32 },
+        num_thresholds: config.thresholds.len(),
+        linear_denoise: config.linear_denoise as i32,
+    }
+}
+/// drop-in for wavelet_denoise (wavelet.rs:41-133), bit for bit; progress (2 S + 1 ticks, the reference's stage strings) and cancel included
+pub fn wavelet_denoise(hip: &Hip, image: &impl PlaneSrc, config: &WaveletConfig, progress: Option<&ProgressHandle>) -> Result<WaveletResult> {
+    let start = std::time::Instant::now();
+    let mut out = Array2::<f32>::zeros(image.dims());
+    let cfg = wavelet_cfg(config);
+    let mut res: sys::ab_wavelet_result = unsafe { std::mem::zeroed() };
+    let mut po = out.ab_mut();
+    hip.with_progress(progress, || hip.check(unsafe { sys::ab_wavelet_denoise(hip.ctx, &image.ab(), &cfg, &mut po, &mut res) }))?;
+    Ok(WaveletResult { denoised: out, scales_processed: res.scales_processed, noise_estimate: res.noise_estimate, elapsed_ms: start.elapsed().as_millis() as u64 })
+}
+/// the eight per-scale f32 thresholds wavelet_denoise derives from noise_sigma (wavelet.rs:93-99, :218-225): host maths in the library
+pub fn wavelet_scale_thresholds(noise_sigma: f64, config: &WaveletConfig) -> Result<[f32; 8]> {
+    let cfg = wavelet_cfg(config);
+    let mut out = [0.0f32; 8];
+    let rc = unsafe { sys::ab_wavelet_scale_thresholds(noise_sigma, &cfg, out.as_mut_ptr()) };
+    if rc != sys::AB_OK {
+        bail!("wavelet_scale_thresholds: invalid arguments (status {rc})");
+    }
+    Ok(out)
 }
 
 // ---- core/stacking/drizzle.rs (calibration.rs:320 drizzle_from_paths, drizzle_rgb_cmd) ----------------------------------------------------------------------

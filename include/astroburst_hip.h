@@ -717,6 +717,32 @@ AB_API int ab_drizzle_frames(ab_ctx *ctx, const ab_plane *planes, size_t n, cons
 AB_API int ab_drizzle_stack(ab_ctx *ctx, const ab_plane *planes, size_t n, const ab_drizzle_config *cfg, ab_plane_mut *out_image,
                             ab_plane_mut *out_weight, double *offsets_dx_dy, ab_drizzle_result *res);
 
+/* ---- a trous wavelet denoising, core/imaging/wavelet.rs (wavelet_denoise_cmd) ------------------------------------------------ */
+typedef struct { /* WaveletConfig (wavelet.rs:10-15); Default (:17-25): 5 scales, {3.0, 2.5, 2.0, 1.5, 1.0}, linear_denoise = true */
+    size_t num_scales;       /* clamped to [1, 8] (:47), not rejected */
+    const float *thresholds; /* per-scale sigma multipliers: num_thresholds entries (NULL when 0); scale j takes entry j, beyond the
+                              * list its last entry, of an empty list 1.0 (:93-97) -- entries past the eighth are never read */
+    size_t num_thresholds;
+    int32_t linear_denoise;  /* bool: soft thresholding (:227-236), else hard (:238-244) */
+} ab_wavelet_config;
+typedef struct { /* WaveletResult's scalars (:27-33); elapsed_ms is the host's to measure */
+    size_t scales_processed;
+    double noise_estimate;
+} ab_wavelet_result;
+/* The per-scale thresholds of wavelet_denoise (:93-99) for all eight scales: out[j] = ts_j * (f32)(noise_sigma *
+ * atrous_noise_scaling(j)) (:218-225) -- the product in f64, the cast, then the f32 multiply.  Host-only scalar maths, bit for bit
+ * the reference's; the GPU path takes its thresholds from this function.  cfg->num_scales is not read. */
+AB_API int ab_wavelet_scale_thresholds(double noise_sigma, const ab_wavelet_config *cfg, float out[8]);
+/* wavelet_denoise (:41-133): the B3-spline a trous decomposition (atrous_smooth_buffers, :135-186; clamped borders, step 2^j),
+ * noise_sigma = 1.4826 * median of the finite |d_0| (estimate_noise_sigma, :203-216), soft or hard thresholding of every detail
+ * plane and the reconstruction with its finite-and-non-negative gate (:112-121).  img and out host or device, out = img's dims
+ * and not overlapping it; NULL arguments, an empty image, or 2^31 pixels or more -> AB_ERR_INVALID.  Every f32 operation is the
+ * reference's, in its order and unfused: `out`, noise_estimate and scales_processed equal the reference's bit for bit, NaN / inf
+ * pixels included.  Every scale is two streaming launches (a horizontal and a vertical pass).
+ * Progress: 2 * S + 1 ticks ("decomposing scale i/S", "thresholding scale i/S", "reconstructing"); cancellation is seen before
+ * every decomposing and every thresholding tick (:62-67, :86-91).  Not asynchronous: the median is read back. */
+AB_API int ab_wavelet_denoise(ab_ctx *ctx, const ab_plane *img, const ab_wavelet_config *cfg, ab_plane_mut *out, ab_wavelet_result *res);
+
 /* ---- bench support: a plain float4 device copy, the measured HBM ceiling ---- */
 AB_API int ab_bench_copy(ab_ctx *ctx, const float *src_dev, float *dst_dev, size_t n_floats);
 
