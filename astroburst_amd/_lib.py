@@ -183,6 +183,10 @@ class WaveletResultC(C.Structure):  # WaveletResult's scalars (wavelet.rs:27-33)
     _fields_ = [("scales_processed", C.c_size_t), ("noise_estimate", C.c_double)]
 
 
+class FftResultC(C.Structure):  # FftResult's scalars (core/analysis/fft.rs:11-17)
+    _fields_ = [("display_rows", C.c_int64), ("display_cols", C.c_int64), ("original_size", C.c_int64), ("windowed", C.c_int32)]
+
+
 class DrizzleConfigC(C.Structure):  # DrizzleConfig (types/stacking.rs) + the affine estimate's num_threads
     _fields_ = [("scale", C.c_double), ("pixfrac", C.c_double), ("kernel", C.c_int32), ("sigma_low", C.c_float), ("sigma_high", C.c_float),
                 ("sigma_iterations", C.c_size_t), ("align", C.c_int32), ("alignment_method", C.c_int32), ("num_threads", C.c_int32)]
@@ -404,6 +408,12 @@ def lib() -> C.CDLL:
     L.ab_richardson_lucy.argtypes = [vp, pp, pp, C.POINTER(RLConfigC), pp, C.POINTER(RLResultC)]
     L.ab_wavelet_scale_thresholds.argtypes = [C.c_double, C.POINTER(WaveletConfigC), C.POINTER(C.c_float)]
     L.ab_wavelet_denoise.argtypes = [vp, pp, C.POINTER(WaveletConfigC), pp, C.POINTER(WaveletResultC)]
+    f32p = C.POINTER(C.c_float)
+    L.ab_power_spectrum_dims.argtypes = [C.c_int64, C.c_int64, i64p, i64p]
+    L.ab_hann_symmetric_f32.argtypes = [C.c_size_t, f32p]
+    L.ab_fft2_forward_f32.argtypes = [vp, pp, f32p, f32p, C.c_int64, C.c_int64, vp, C.c_int32]
+    L.ab_compute_power_spectrum.argtypes = [vp, pp, C.c_int32, pp, C.POINTER(FftResultC)]
+    L.ab_spectrum_to_u8.argtypes = [vp, pp, vp, C.c_int32, f32p, f32p, f32p]
     L.ab_drizzle_output_dims.argtypes = [pp, C.c_size_t, C.POINTER(DrizzleConfigC), i64p, i64p, i64p, i64p]
     L.ab_drizzle_frames.argtypes = [vp, pp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(DrizzleConfigC), pp, pp, C.POINTER(DrizzleResultC)]
     L.ab_drizzle_stack.argtypes = [vp, pp, C.c_size_t, C.POINTER(DrizzleConfigC), pp, pp, C.POINTER(C.c_double), C.POINTER(DrizzleResultC)]

@@ -119,6 +119,15 @@ class DrizzleResult:  # types/stacking.rs DrizzleResult (drizzle.rs:335-344)
     rejected_pixels: int
 
 
+@dataclass
+class FftResult:  # core/analysis/fft.rs:11-17
+    spectrum: object
+    display_rows: int
+    display_cols: int
+    original_size: int
+    windowed: bool
+
+
 DRIZZLE_KERNELS = {"square": 0, "gaussian": 1, "lanczos3": 2}
 DRIZZLE_ALIGNMENT = {"phase_correlation": 0, "zncc": 1}
 
@@ -216,6 +225,25 @@ def generate_gaussian_psf(size: int, sigma: float) -> np.ndarray:
     rc = _lib.lib().ab_generate_gaussian_psf(int(size), float(sigma), out.ctypes.data_as(C.POINTER(C.c_float)))
     if rc != _lib.AB_OK:
         raise AstroBurstError(rc, "ab_generate_gaussian_psf: bad arguments")
+    return out
+
+
+def power_spectrum_dims(rows: int, cols: int):
+    """(original_size, display_size) of compute_power_spectrum (core/analysis/fft.rs:24-25, :53-57): the next power of two of the
+    longer side, and that capped at 1024.  Host-only; images beyond 16384 a side raise AB_ERR_UNSUPPORTED."""
+    size, disp = C.c_int64(0), C.c_int64(0)
+    rc = _lib.lib().ab_power_spectrum_dims(int(rows), int(cols), C.byref(size), C.byref(disp))
+    if rc != _lib.AB_OK:
+        raise AstroBurstError(rc, "ab_power_spectrum_dims: rows and cols must be >= 1 and at most 16384")
+    return int(size.value), int(disp.value)
+
+
+def hann_symmetric_f32(n: int) -> np.ndarray:
+    """hann_symmetric::<f32>(n) (math/window.rs:20-35), host-only: the table the GPU path multiplies by"""
+    out = np.empty(int(n), np.float32)
+    rc = _lib.lib().ab_hann_symmetric_f32(int(n), out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != _lib.AB_OK:
+        raise AstroBurstError(rc, "ab_hann_symmetric_f32: bad arguments")
     return out
 
 
@@ -1624,6 +1652,74 @@ class Context:
         res = _lib.WaveletResultC()
         self._check(self._L.ab_wavelet_denoise(self._h, C.byref(pi), C.byref(cfg), C.byref(po), C.byref(res)))
         return out, int(res.scales_processed), float(res.noise_estimate)
+
+    # ---- core/analysis/fft.rs (compute_fft_spectrum) ----------------------------------------------------------
+    power_spectrum_dims = staticmethod(power_spectrum_dims)
+    hann_symmetric_f32 = staticmethod(hann_symmetric_f32)
+
+    def fft2_forward(self, image, fft_rows, fft_cols, win_y=None, win_x=None, out=None):
+        """prepare_windowed_buffer / prepare_buffer_no_window + FftEngine2D::<f32>::forward_2d (math/fft.rs:137-148, :202-245) ->
+        complex64 (fft_rows, fft_cols).  image: numpy (host) or a CUDA tensor (device); win_y / win_x: host f32 tables of the image's
+        rows / cols, both or neither; the result is of the image's kind unless `out` (complex64, contiguous) is given."""
+        keep = []
+        pi = self._plane(image, keep)
+        if (win_y is None) != (win_x is None):
+            raise AstroBurstError(_lib.AB_ERR_INVALID, "win_y and win_x must both be given or both be None")
+        wy = wx = None
+        if win_y is not None:
+            wy = np.ascontiguousarray(win_y, dtype=np.float32)
+            wx = np.ascontiguousarray(win_x, dtype=np.float32)
+            if wy.shape != (pi.rows,) or wx.shape != (pi.cols,):
+                raise AstroBurstError(_lib.AB_ERR_INVALID, f"the windows must hold {pi.rows} and {pi.cols} floats")
+        fft_rows, fft_cols = int(fft_rows), int(fft_cols)
+        if fft_rows < 1 or fft_cols < 1:
+            raise AstroBurstError(_lib.AB_ERR_INVALID, "fft_rows and fft_cols must be powers of two in 1 .. 16384")
+        if out is None:
+            out = (torch.empty((fft_rows, fft_cols), dtype=torch.complex64, device=image.device) if _is_torch(image) and image.is_cuda
+                   else np.empty((fft_rows, fft_cols), np.complex64))
+        f32p = C.POINTER(C.c_float)
+        if _is_torch(out):
+            assert out.is_cuda and out.dtype == torch.complex64 and out.is_contiguous() and tuple(out.shape) == (fft_rows, fft_cols)
+            self.use_torch_stream()
+            ptr, on_dev = out.data_ptr(), 1
+        else:
+            assert out.dtype == np.complex64 and out.flags.c_contiguous and out.shape == (fft_rows, fft_cols)
+            ptr, on_dev = out.ctypes.data, 0
+        self._check(self._L.ab_fft2_forward_f32(self._h, C.byref(pi), wy.ctypes.data_as(f32p) if wy is not None else None,
+                                                wx.ctypes.data_as(f32p) if wx is not None else None, fft_rows, fft_cols,
+                                                C.c_void_p(ptr), on_dev))
+        return out
+
+    def compute_power_spectrum(self, image, apply_window=True, out=None) -> FftResult:
+        """compute_power_spectrum_opts (core/analysis/fft.rs:23-68) -> FftResult: the shifted ln(1 + |F|) map of the (Hann-windowed)
+        image zero-padded to a power of two, area-averaged down to 1024^2 beyond that.  image: numpy (host) or a CUDA tensor
+        (device); the spectrum is of the image's kind unless `out` is given."""
+        keep = []
+        pi = self._plane(image, keep)
+        _, disp = power_spectrum_dims(pi.rows, pi.cols)
+        if out is None:
+            out = self._new_like(image, disp, disp)
+        orows, ocols = (int(out.shape[0]), int(out.shape[1])) if len(out.shape) == 2 else (0, 0)
+        if not _is_torch(out) and (out.dtype != np.float32 or not out.flags.c_contiguous):
+            raise AstroBurstError(_lib.AB_ERR_INVALID, "the spectrum must be a contiguous float32 array")
+        po = self._out_plane(out, keep, orows, ocols)
+        res = _lib.FftResultC()
+        self._check(self._L.ab_compute_power_spectrum(self._h, C.byref(pi), 1 if apply_window else 0, C.byref(po), C.byref(res)))
+        return FftResult(out, int(res.display_rows), int(res.display_cols), int(res.original_size), bool(res.windowed))
+
+    def spectrum_to_u8(self, spectrum, out=None):
+        """The per-pixel part of compute_fft_spectrum (cmd/analysis/mod.rs:66-96) -> (u8 image, min, max, dc): the spectrum
+        stretched to bytes over its own range, dc = spectrum[rows / 2, cols / 2].  Bytes are of the spectrum's kind."""
+        keep = []
+        ps = self._plane(spectrum, keep)
+        dev = _is_torch(spectrum) and spectrum.is_cuda
+        if out is None:
+            out = torch.empty((ps.rows, ps.cols), dtype=torch.uint8, device=spectrum.device) if dev else np.empty((ps.rows, ps.cols), np.uint8)
+        ptr = out.data_ptr() if _is_torch(out) else out.ctypes.data
+        mn, mx, dc = C.c_float(0), C.c_float(0), C.c_float(0)
+        self._check(self._L.ab_spectrum_to_u8(self._h, C.byref(ps), C.c_void_p(ptr), 1 if (_is_torch(out) and out.is_cuda) else 0,
+                                              C.byref(mn), C.byref(mx), C.byref(dc)))
+        return out, mn.value, mx.value, dc.value
 
     # ---- core/stacking/drizzle.rs -------------------------------------------------------------------------
     drizzle_output_dims = staticmethod(drizzle_output_dims)

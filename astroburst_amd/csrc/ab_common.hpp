@@ -58,6 +58,9 @@ enum {
     AB_WS_DECONV,             // Richardson-Lucy: chain state, padded PSF weights, per-workgroup partials, the ratio plane (deconv.hip)
     AB_WS_DRIZZLE,            // drizzle: the frame table, per-workgroup rejected partials, the long-list path's sample columns (drizzle.hip)
     AB_WS_WAVELET,            // wavelet denoising: the horizontal pass's plane and the smoothed planes c_1 .. c_S (wavelet.hip)
+    AB_WS_FFT_TABLES,         // the f32 twiddle tables of every line length 2 .. 16384 + the two window tables of the call (spectrum.hip)
+    AB_WS_FFT_A,              // the 2-D FFT's row-pass output, fft_rows x fft_cols complex f32 (spectrum.hip)
+    AB_WS_FFT_B,              // its transpose, which the second line pass transforms in place (spectrum.hip)
     AB_WS_SLOTS
 };
 
@@ -169,6 +172,7 @@ struct ab_ctx {
     // phase_corr.hip: the (rows, cols) the two table sets in AB_WS_PHASE_TABLES were built for, and the workspace they live in
     int pc_tab_dims[2][2] = {{0, 0}, {0, 0}};
     const void *pc_tab_ws = nullptr;
+    const void *fft_tab_ws = nullptr;  // spectrum.hip: the workspace its twiddle tables were built in
 };
 
 // stage boundary: AB_ERR_CANCELLED ("Operation cancelled") if the host asked to stop, else ticks the callback (if any)

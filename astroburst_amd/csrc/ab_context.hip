@@ -209,6 +209,7 @@ int ab_ctx_trim(ab_ctx *ctx) try {
     drop(ctx->scratch, ctx->scratch_bytes, false, "hipFree(scratch)");
     for (int i = 0; i < AB_WS_SLOTS; ++i) drop(ctx->ws[i], ctx->ws_bytes[i], false, "hipFree(workspace)");
     ctx->pc_tab_ws = nullptr;  // (phase_corr.hip rebuilds its tables when the workspace pointer changes)
+    ctx->fft_tab_ws = nullptr; // (spectrum.hip: the same for its twiddle tables)
     ctx->stats_bar = nullptr;  // (stats.hip clears the resident kernel's barrier flags when its workspace is new)
     drop(ctx->upload_buf, ctx->upload_bytes, false, "hipFree(upload_buf)");
     // the pinned read-back buffers (they grow with the frame-group size: G * kSelCap selection records) and the declined-tile lists

@@ -29,6 +29,7 @@ pub use device::{DevicePlane, PlaneDst, PlaneSrc, DEVICE_CACHE};
 use crate::core::alignment::affine::{AffineAlignMethod, AffineAlignResult, AffineTransform};
 use crate::core::alignment::pair::AlignPairResult;
 use crate::core::alignment::phase_correlation::PhaseCorrelationResult;
+use crate::core::analysis::fft::FftResult;
 use crate::core::analysis::star_detection::{DetectedStar, DetectionResult};
 use crate::core::analysis::subframe::{SubframeMetrics, SubframeWeightConfig};
 use crate::core::astrometry::spcc::{SpccConfig, SpccResult, WhiteReference};
@@ -740,6 +741,67 @@ pub fn wavelet_scale_thresholds(noise_sigma: f64, config: &WaveletConfig) -> Res
         bail!("wavelet_scale_thresholds: invalid arguments (status {rc})");
     }
     Ok(out)
+}
+
+// ---- core/analysis/fft.rs (compute_fft_spectrum) --------------------------------------------------------------------------------------------------------
+/// (original_size, display_size) of compute_power_spectrum (fft.rs:24-25, :53-57): host maths in the library
+pub fn power_spectrum_dims(rows: usize, cols: usize) -> Result<(usize, usize)> {
+    let (mut size, mut disp) = (0i64, 0i64);
+    let rc = unsafe { sys::ab_power_spectrum_dims(rows as i64, cols as i64, &mut size, &mut disp) };
+    if rc != sys::AB_OK {
+        bail!("power_spectrum_dims: {rows} x {cols} is empty or beyond 16384 a side (status {rc})");
+    }
+    Ok((size as usize, disp as usize))
+}
+/// drop-in for window::hann_symmetric::<f32> (math/window.rs:20-35): host maths in the library
+pub fn hann_symmetric_f32(n: usize) -> Vec<f32> {
+    let mut w = vec![0.0f32; n];
+    if n > 0 {
+        unsafe { sys::ab_hann_symmetric_f32(n, w.as_mut_ptr()) };
+    }
+    w
+}
+/// prepare_windowed_buffer / prepare_buffer_no_window + FftEngine2D::<f32>::forward_2d (math/fft.rs:137-148, :202-245): the
+/// fft_rows x fft_cols spectrum as interleaved (re, im) f32 in natural row-major order; `windows` = (win_y, win_x) or None
+pub fn fft2_forward_f32(hip: &Hip, image: &impl PlaneSrc, windows: Option<(&[f32], &[f32])>, fft_rows: usize, fft_cols: usize) -> Result<Vec<f32>> {
+    let (rows, cols) = image.dims();
+    if let Some((wy, wx)) = windows {
+        if wy.len() != rows || wx.len() != cols {
+            bail!("fft2_forward_f32: the windows must hold {rows} and {cols} values");
+        }
+    }
+    let mut out = vec![0.0f32; 2 * fft_rows * fft_cols];
+    let (wy, wx) = windows.map_or((std::ptr::null(), std::ptr::null()), |(y, x)| (y.as_ptr(), x.as_ptr()));
+    hip.check(unsafe { sys::ab_fft2_forward_f32(hip.ctx, &image.ab(), wy, wx, fft_rows as i64, fft_cols as i64, out.as_mut_ptr(), 0) })?;
+    Ok(out)
+}
+/// drop-in for compute_power_spectrum_opts (fft.rs:23-68)
+pub fn compute_power_spectrum_opts(hip: &Hip, data: &impl PlaneSrc, apply_window: bool) -> Result<FftResult> {
+    let (rows, cols) = data.dims();
+    let (_, disp) = power_spectrum_dims(rows, cols)?;
+    let mut spectrum = Array2::<f32>::zeros((disp, disp));
+    let mut res: sys::ab_fft_result = unsafe { std::mem::zeroed() };
+    let mut po = spectrum.ab_mut();
+    hip.check(unsafe { sys::ab_compute_power_spectrum(hip.ctx, &data.ab(), apply_window as i32, &mut po, &mut res) })?;
+    Ok(FftResult {
+        spectrum,
+        display_width: res.display_cols as usize,
+        display_height: res.display_rows as usize,
+        original_size: res.original_size as usize,
+        windowed: res.windowed != 0,
+    })
+}
+/// drop-in for compute_power_spectrum (fft.rs:19-21)
+pub fn compute_power_spectrum(hip: &Hip, data: &impl PlaneSrc) -> Result<FftResult> {
+    compute_power_spectrum_opts(hip, data, true)
+}
+/// the per-pixel part of compute_fft_spectrum (cmd/analysis/mod.rs:66-96): (pixels, min_val, max_val, dc)
+pub fn spectrum_to_u8(hip: &Hip, spectrum: &impl PlaneSrc) -> Result<(Vec<u8>, f32, f32, f32)> {
+    let (r, c) = spectrum.dims();
+    let mut out = vec![0u8; r * c];
+    let (mut mn, mut mx, mut dc) = (0.0f32, 0.0f32, 0.0f32);
+    hip.check(unsafe { sys::ab_spectrum_to_u8(hip.ctx, &spectrum.ab(), out.as_mut_ptr(), 0, &mut mn, &mut mx, &mut dc) })?;
+    Ok((out, mn, mx, dc))
 }
 
 // ---- core/stacking/drizzle.rs (calibration.rs:320 drizzle_from_paths, drizzle_rgb_cmd) ----------------------------------------------------------------------

@@ -743,6 +743,43 @@ AB_API int ab_wavelet_scale_thresholds(double noise_sigma, const ab_wavelet_conf
  * every decomposing and every thresholding tick (:62-67, :86-91).  Not asynchronous: the median is read back. */
 AB_API int ab_wavelet_denoise(ab_ctx *ctx, const ab_plane *img, const ab_wavelet_config *cfg, ab_plane_mut *out, ab_wavelet_result *res);
 
+/* ---- FFT power spectrum, core/analysis/fft.rs (compute_fft_spectrum: cmd/analysis/mod.rs:66-96) ------------------------------ */
+/* math/fft.rs:137-148 (FftEngine2D::<f32>::forward_2d), :202-245 (prepare_windowed_buffer, prepare_buffer_no_window),
+ * math/window.rs:20-35 (hann_symmetric).  The transform is this library's own f32 FFT (radix-2 butterflies, twiddles evaluated in
+ * f64 and rounded once to f32), not rustfft's: results agree with the reference to single-precision FFT accuracy, not bit for bit.
+ * Two calls on the same input return the same bits.  |pixel| >= 1e30 is outside the contract. */
+typedef struct { /* FftResult's scalars (fft.rs:11-17) */
+    int64_t display_rows, display_cols; /* display_height, display_width */
+    int64_t original_size;
+    int32_t windowed;
+} ab_fft_result;
+/* compute_power_spectrum's dims (fft.rs:24-25, :53-57), host-only: original_size = max(rows, cols).next_power_of_two(),
+ * display_size = min(original_size, 1024).  rows or cols < 1 -> AB_ERR_INVALID; original_size > 16384 -> AB_ERR_UNSUPPORTED.
+ * Either output pointer may be NULL. */
+AB_API int ab_power_spectrum_dims(int64_t rows, int64_t cols, int64_t *original_size, int64_t *display_size);
+/* hann_symmetric::<f32>(n) (window.rs:20-35), host-only: n == 1 -> 1; else 0.5 * (1 - cosf((2f * PIf) * (i as f32) / max(n - 1, 1)))
+ * in f32.  n == 0 writes nothing.  The GPU path takes its windows from this function. */
+AB_API int ab_hann_symmetric_f32(size_t n, float *out);
+/* prepare_windowed_buffer / prepare_buffer_no_window + forward_2d on an fft_rows x fft_cols buffer (each a power of two in
+ * 1 .. 16384): pixel (y, x) enters as (v * win_y[y]) * win_x[x] in f32 (v alone when both windows are NULL), a non-finite pixel as
+ * 0, everything beyond the image as 0.  image (host or device): rows <= fft_rows, cols <= fft_cols; win_y / win_x: HOST tables of
+ * image->rows / image->cols floats, both NULL or both given; out: fft_rows * fft_cols interleaved (re, im) f32 in natural
+ * row-major order, host or device (out_on_device).  The padded buffer is never materialised and rows of padding are not transformed.
+ * Workspace: 16 * fft_rows * fft_cols bytes of the context (released by ab_ctx_trim); AB_ERR_NOMEM when it cannot be had. */
+AB_API int ab_fft2_forward_f32(ab_ctx *ctx, const ab_plane *image, const float *win_y, const float *win_x, int64_t fft_rows, int64_t fft_cols,
+                               float *out, int32_t out_on_device);
+/* compute_power_spectrum_opts (fft.rs:23-68): the (windowed) image zero-padded to original_size^2, forward_2d, fftshift,
+ * ln(1 + |F|), and beyond 1024^2 the s x s block mean (s = original_size / 1024, downsample_area_average :70-97) -- shift,
+ * magnitude, log and mean in one kernel, the original_size^2 log plane is never written.  spectrum: display_size^2
+ * (ab_power_spectrum_dims), host or device. */
+AB_API int ab_compute_power_spectrum(ab_ctx *ctx, const ab_plane *image, int32_t apply_window, ab_plane_mut *spectrum, ab_fft_result *result);
+/* The per-pixel part of compute_fft_spectrum (cmd/analysis/mod.rs:66-96): min / max with f32::min / f32::max (a NaN is skipped),
+ * range = max(max - min, 1e-10), inv = 255 / range, pixel = ((v - min) * inv) as u8 (truncating, saturating, NaN -> 0), all in f32;
+ * dc = spectrum[rows / 2, cols / 2].  spectrum host or device; out_u8: rows * cols bytes, host or device (out_on_device).
+ * min_val / max_val / dc may be NULL.  Not asynchronous: the range is read back. */
+AB_API int ab_spectrum_to_u8(ab_ctx *ctx, const ab_plane *spectrum, uint8_t *out_u8, int32_t out_on_device, float *min_val, float *max_val,
+                             float *dc);
+
 /* ---- bench support: a plain float4 device copy, the measured HBM ceiling ---- */
 AB_API int ab_bench_copy(ab_ctx *ctx, const float *src_dev, float *dst_dev, size_t n_floats);
 
