@@ -304,11 +304,9 @@ int ab_stage_out_begin(ab_ctx *ctx, const ab_plane_mut *p, StagedOut *out);
 int ab_stage_out_finish(ab_ctx *ctx, StagedOut *o);  // downloads (sync) + frees when host
 void ab_stage_out_abort(ab_ctx *ctx, StagedOut *o);
 
-// plane_select.hip: exact order statistics of {v : finite, v > min_valid, (mask == nullptr || mask < 0.5)};
-// keys are v or, with use_dev, |v - center| (f32).
+// plane_select.hip: exact order statistics of {v : finite, v > min_valid}; keys are v or, with use_dev, |v - center| (f32).
 struct ab_plane_sel {
     const float *data = nullptr;
-    const float *mask = nullptr;
     int64_t n = 0;
     float min_valid = 0.0f;
     int use_dev = 0;

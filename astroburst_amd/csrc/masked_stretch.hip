@@ -9,8 +9,8 @@
 // patterns (values >= 0 order like their bits, so the reference's serial "keep the larger" merge is
 // reproduced independent of order), then one streaming pass applies the luminance protection and
 // counts the coverage.  Stretch: every iteration is two HBM-bound steps -- the exact [len/2]
-// element of the unmasked positive pixels (plane_select.hip; the reference rebuilds and selects a
-// P-sized Vec serially, masked_stretch.rs:213-229) and one fused kernel doing apply_mtf + the
+// element of the unmasked positive pixels (the device-resident 11/11/10 select below; the reference rebuilds
+// and selects a P-sized Vec serially, masked_stretch.rs:213-229) and one fused kernel doing apply_mtf + the
 // mask-weighted blend in place (the reference materialises the stretched copy first).
 #include "ab_common.hpp"
 
@@ -424,10 +424,12 @@ __device__ __forceinline__ float mtf_pixel(float x, float m) {
 
 // apply_mtf (:240-255) + the mask-weighted blend (:93-100) in place, + level 0 of the next median -- and, round 4, its LEVEL 1 too
 // when a prediction holds: an unmasked pixel (mask 0, all of the sky) becomes mtf(x) exactly, a monotone function, so the next
-// median would be mtf(this median) if every candidate were unmasked; the few per cent with a soft mask value move it by a few
-// level-1 bins at most, never out of its level-0 bin (a quarter of a binade).  The pass therefore also histograms level 1 of the
-// candidates inside the PREDICTED level-0 bin; the pick after it checks the prediction against the real level-0 histogram and,
-// when it holds, the level-1 pass over the plane returns at once (one of three passes per iteration: 28 -> 20 bytes per pixel).
+// median would be mtf(this median) if every candidate were unmasked; the few per cent with a soft mask value usually move it by a
+// few level-1 bins only.  They CAN move it out of its level-0 bin -- mtf(median) is the target itself, and a target such as 0.25 is
+// the first value of a level-0 bin, so a median pulled just below it lands in the bin before -- which is why the prediction is only
+// ever a guess: the pass also histograms level 1 of the candidates inside the PREDICTED level-0 bin; the pick after it checks the
+// prediction against the real level-0 histogram (bin == pred_b0) and, when it holds, the level-1 pass over the plane returns at
+// once (one of three passes per iteration: 28 -> 20 bytes per pixel); when it does not, level 1 takes its own pass.
 __global__ __launch_bounds__(kBlock) void ms_blend_hist0_kernel(float *__restrict__ work, const float *__restrict__ mask, int64_t n,
                                                                 MsState *st, float protection, unsigned int *hist) {
     if (st->done) return;
@@ -471,7 +473,9 @@ __global__ __launch_bounds__(kBlock) void ms_clamp_kernel(float *__restrict__ wo
 // One workgroup after every histogram pass: the bin of the wanted rank, the narrowed prefix, the histogram cleared for the next
 // pass.  Level 0 also takes the candidate count (rank = count / 2: the [len / 2] element, :226-229).  Level 2 completes a median
 // and runs the loop's head for iteration `it` (:78-92): it = -1: the median before the loop (:71); it = iterations: the loop has run out.
-__global__ __launch_bounds__(kPickBlock) void ms_pick_kernel(unsigned int *hist, MsState *st, int level, int it, int iterations, double target, double threshold) {
+// predict = 0 (developer switch AB_MS_NO_PREDICT): no prediction is declared valid, so level 1 always takes its own pass.
+__global__ __launch_bounds__(kPickBlock) void ms_pick_kernel(unsigned int *hist, MsState *st, int level, int it, int iterations, double target, double threshold,
+                                                             int predict) {
     if (st->done) return;
     __shared__ unsigned long long s_wave[kPickBlock / 64];
     __shared__ uint32_t s_bin;
@@ -571,7 +575,7 @@ __global__ __launch_bounds__(kPickBlock) void ms_pick_kernel(unsigned int *hist,
             st->need_clamp = 0;  // the blend that follows overwrites every pixel and raises it again if it has to
             // the blend that follows predicts the next median's level-0 bin from this median (see ms_blend_hist0_kernel)
             st->pred_b0 = __float_as_uint(mtf_pixel(st->count == 0 ? 0.0f : __uint_as_float(st->prefix_val), mt)) >> 21;
-            st->pred_valid = 1;
+            st->pred_valid = predict;
         }
     }
 }
@@ -586,15 +590,16 @@ int masked_stretch_enqueue(ab_ctx *ctx, hipStream_t stream, const float *img, co
     const int grid = stream_grid(ctx, n);
     const int iterations = (int)std::min<size_t>(cfg.iterations, 1000000);
     const float protection = (float)cfg.protection_amount;
+    const int predict = ab_dev_env("AB_MS_NO_PREDICT") ? 0 : 1;  // (developer A/B: both forms of level 1 on the same input)
     if (!have_range) hipLaunchKernelGGL(ms_range_kernel, dim3(grid), dim3(kBlock), 0, stream, img, n, st);
     hipLaunchKernelGGL(ms_range_finish_kernel, dim3(1), dim3(1), 0, stream, st);
     hipLaunchKernelGGL(ms_normalize_hist0_kernel, dim3(grid), dim3(kBlock), 0, stream, img, mask, n, (const MsState *)st, work, hist);
     auto finish_median = [&](int it) {
-        hipLaunchKernelGGL(ms_pick_kernel, dim3(1), dim3(kPickBlock), 0, stream, hist, st, 0, it, iterations, cfg.target_background, cfg.convergence_threshold);
+        hipLaunchKernelGGL(ms_pick_kernel, dim3(1), dim3(kPickBlock), 0, stream, hist, st, 0, it, iterations, cfg.target_background, cfg.convergence_threshold, predict);
         hipLaunchKernelGGL(ms_hist_kernel, dim3(grid), dim3(kBlock), 0, stream, (const float *)work, mask, n, (const MsState *)st, hist, 1);
-        hipLaunchKernelGGL(ms_pick_kernel, dim3(1), dim3(kPickBlock), 0, stream, hist, st, 1, it, iterations, cfg.target_background, cfg.convergence_threshold);
+        hipLaunchKernelGGL(ms_pick_kernel, dim3(1), dim3(kPickBlock), 0, stream, hist, st, 1, it, iterations, cfg.target_background, cfg.convergence_threshold, predict);
         hipLaunchKernelGGL(ms_hist_kernel, dim3(grid), dim3(kBlock), 0, stream, (const float *)work, mask, n, (const MsState *)st, hist, 2);
-        hipLaunchKernelGGL(ms_pick_kernel, dim3(1), dim3(kPickBlock), 0, stream, hist, st, 2, it, iterations, cfg.target_background, cfg.convergence_threshold);
+        hipLaunchKernelGGL(ms_pick_kernel, dim3(1), dim3(kPickBlock), 0, stream, hist, st, 2, it, iterations, cfg.target_background, cfg.convergence_threshold, predict);
     };
     finish_median(-1);
     // The reference leaves its loop at convergence (masked_stretch.rs:82-91); here an iteration that the decision has switched off

@@ -2,10 +2,11 @@
 //
 // Serves every place the reference collects the valid pixels of a full image into a Vec and calls
 // select_nth_unstable on it: background.rs:135-146 (global median / MAD), :350-361 (model median),
-// masked_stretch.rs:213-229 (median of the unmasked pixels, once per stretch iteration).  Candidates
-// are finite and > min_valid >= 0, so their bit patterns (and those of absolute deviations) order
-// like the values.  Pass 0 histograms the top 11 bits and yields the candidate count; each requested
-// rank then costs two more streaming passes.  All passes are HBM-bound reads of the plane (+ mask).
+// tiles.rs:149-178 (percentile bounds), wavelet.rs:203-216 (the median of the finite |d_0|).  (The masked
+// stretch has its own device-resident chain of the same 11/11/10 select: masked_stretch.hip.)  The keys
+// are non-negative -- candidates are > min_valid >= 0, or the keys are absolute deviations -- so their
+// bit patterns order like the values.  Pass 0 histograms the top 11 bits and yields the candidate count;
+// each requested rank then costs two more streaming passes.  All passes are HBM-bound reads of the plane.
 #include "ab_common.hpp"
 
 #include <algorithm>
@@ -15,7 +16,7 @@ namespace {
 constexpr int kBlock = 256;
 
 struct SelArgs {
-    const float *data, *mask;
+    const float *data;
     int64_t n;
     float min_valid;
     int use_dev;
@@ -33,9 +34,7 @@ __global__ __launch_bounds__(kBlock) void plane_select_hist_kernel(const SelArgs
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.n; i += stride) {
         const float v = a.data[i];
-        bool ok = __builtin_isfinite(v) && v > a.min_valid;
-        if (a.mask) ok = ok && a.mask[i] < 0.5f;
-        if (ok) {
+        if (__builtin_isfinite(v) && v > a.min_valid) {
             const float k = a.use_dev ? fabsf(v - a.center) : v;
             const uint32_t key = __float_as_uint(k);
             if ((key & a.prefix_mask) == a.prefix_val) atomicAdd(&lds[(key >> a.shift) & (nb - 1)], 1u);
@@ -51,7 +50,7 @@ int run_pass(ab_ctx *ctx, const ab_plane_sel &s, uint32_t mask, uint32_t val, in
     AB_HIP(ctx, hipMemsetAsync(ctx->sel_hist, 0, nb * sizeof(unsigned int), ctx->stream));
     const int grid = (int)std::max<int64_t>(
         1, std::min<int64_t>((s.n + kBlock - 1) / kBlock, (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8));
-    SelArgs a{s.data, s.mask, s.n, s.min_valid, s.use_dev, s.center, mask, val, shift, nbits, ctx->sel_hist};
+    SelArgs a{s.data, s.n, s.min_valid, s.use_dev, s.center, mask, val, shift, nbits, ctx->sel_hist};
     hipLaunchKernelGGL(plane_select_hist_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, a);
     AB_HIP(ctx, hipGetLastError());
     AB_HIP(ctx, hipMemcpyAsync(host, ctx->sel_hist, nb * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
@@ -115,7 +114,10 @@ int ab_plane_select_ranks(ab_ctx *ctx, const ab_plane_sel &s, int max_ranks, con
                 continue;
             }
             const uint32_t m = mask | (((1u << bits[level]) - 1u) << shifts[level]);
-            unsigned int *hn = level == 0 ? h1 : h2;  // (a level's histogram is consumed before the next group overwrites it)
+            // Every item of this level has been located in `h` above, before the first child pass: a level's histogram is never read
+            // again once its groups exist.  So no histogram can be overwritten while it is still needed, whichever buffer a child
+            // pass fills -- level 2 could reuse h1; h2 only keeps the two levels' counts apart.
+            unsigned int *hn = level == 0 ? h1 : h2;
             AB_TRY(run_pass(ctx, s, m, v, shifts[level + 1], bits[level + 1], hn));
             AB_TRY(descend(level + 1, m, v, hn, g.second));
         }
