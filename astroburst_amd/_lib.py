@@ -187,6 +187,14 @@ class FftResultC(C.Structure):  # FftResult's scalars (core/analysis/fft.rs:11-1
     _fields_ = [("display_rows", C.c_int64), ("display_cols", C.c_int64), ("original_size", C.c_int64), ("windowed", C.c_int32)]
 
 
+class CubeC(C.Structure):  # ab_cube: one contiguous [z][y][x] block of f32
+    _fields_ = [("data", C.c_void_p), ("depth", C.c_int64), ("rows", C.c_int64), ("cols", C.c_int64), ("on_device", C.c_int32)]
+
+
+class CubeStatsC(C.Structure):  # GlobalCubeStats (core/cube/eager.rs:160-166)
+    _fields_ = [("median", C.c_float), ("sigma", C.c_float), ("low", C.c_float), ("high", C.c_float)]
+
+
 class DrizzleConfigC(C.Structure):  # DrizzleConfig (types/stacking.rs) + the affine estimate's num_threads
     _fields_ = [("scale", C.c_double), ("pixfrac", C.c_double), ("kernel", C.c_int32), ("sigma_low", C.c_float), ("sigma_high", C.c_float),
                 ("sigma_iterations", C.c_size_t), ("align", C.c_int32), ("alignment_method", C.c_int32), ("num_threads", C.c_int32)]
@@ -414,6 +422,16 @@ def lib() -> C.CDLL:
     L.ab_fft2_forward_f32.argtypes = [vp, pp, f32p, f32p, C.c_int64, C.c_int64, vp, C.c_int32]
     L.ab_compute_power_spectrum.argtypes = [vp, pp, C.c_int32, pp, C.POINTER(FftResultC)]
     L.ab_spectrum_to_u8.argtypes = [vp, pp, vp, C.c_int32, f32p, f32p, f32p]
+    cp, csp = C.POINTER(CubeC), C.POINTER(CubeStatsC)
+    pmp = C.POINTER(Plane)  # (ab_plane_mut has ab_plane's layout)
+    L.ab_cube_collapse_mean.argtypes = [vp, cp, C.c_int32, pmp]
+    L.ab_cube_collapse_median.argtypes = [vp, cp, C.c_int32, pmp]
+    L.ab_cube_streaming_step.argtypes = [C.c_int64]
+    L.ab_cube_streaming_step.restype = C.c_uint64
+    L.ab_cube_global_stats.argtypes = [vp, cp, C.c_int32, C.c_int64, csp, u64p]
+    L.ab_cube_normalize_frame.argtypes = [vp, pp, csp, pmp]
+    L.ab_cube_export_frames.argtypes = [vp, cp, csp, C.c_int64, vp, C.c_int32, i64p]
+    L.ab_cube_extract_spectrum.argtypes = [vp, cp, C.c_int64, C.c_int64, vp, C.c_int32]
     L.ab_drizzle_output_dims.argtypes = [pp, C.c_size_t, C.POINTER(DrizzleConfigC), i64p, i64p, i64p, i64p]
     L.ab_drizzle_frames.argtypes = [vp, pp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(DrizzleConfigC), pp, pp, C.POINTER(DrizzleResultC)]
     L.ab_drizzle_stack.argtypes = [vp, pp, C.c_size_t, C.POINTER(DrizzleConfigC), pp, pp, C.POINTER(C.c_double), C.POINTER(DrizzleResultC)]

@@ -128,6 +128,22 @@ class FftResult:  # core/analysis/fft.rs:11-17
     windowed: bool
 
 
+@dataclass
+class GlobalCubeStats:  # core/cube/eager.rs:160-166
+    median: float
+    sigma: float
+    low: float
+    high: float
+
+
+CUBE_VALID_NONZERO, CUBE_VALID_ABOVE_PADDING = 0, 1  # ab_cube_valid_rule: the eager path's rule, the lazy path's
+
+
+def cube_streaming_step(depth: int) -> int:
+    """The frame stride of compute_global_stats_streaming (core/cube/lazy.rs:334-335).  Host-only."""
+    return int(_lib.lib().ab_cube_streaming_step(int(depth)))
+
+
 DRIZZLE_KERNELS = {"square": 0, "gaussian": 1, "lanczos3": 2}
 DRIZZLE_ALIGNMENT = {"phase_correlation": 0, "zncc": 1}
 
@@ -1720,6 +1736,108 @@ class Context:
         self._check(self._L.ab_spectrum_to_u8(self._h, C.byref(ps), C.c_void_p(ptr), 1 if (_is_torch(out) and out.is_cuda) else 0,
                                               C.byref(mn), C.byref(mx), C.byref(dc)))
         return out, mn.value, mx.value, dc.value
+
+    # ---- core/cube/{eager,lazy}.rs (process_cube_cmd, process_cube_lazy_cmd) ---------------------------------------
+    cube_streaming_step = staticmethod(cube_streaming_step)
+
+    def _cube(self, cube, keep):
+        """ab_cube of a contiguous 3-D float32 numpy array (host) or CUDA tensor (device), [z][y][x]"""
+        if _is_torch(cube):
+            if not (cube.is_cuda and cube.dtype == torch.float32 and cube.dim() == 3 and cube.is_contiguous()):
+                raise AstroBurstError(_lib.AB_ERR_INVALID, "a device cube is a contiguous 3-D float32 CUDA tensor")
+            self.use_torch_stream()
+            keep.append(cube)
+            return _lib.CubeC(C.c_void_p(cube.data_ptr()), cube.shape[0], cube.shape[1], cube.shape[2], 1)
+        a = np.ascontiguousarray(cube, dtype=np.float32)
+        if a.ndim != 3:
+            raise AstroBurstError(_lib.AB_ERR_INVALID, "a cube is 3-D (depth, rows, cols)")
+        keep.append(a)
+        return _lib.CubeC(C.c_void_p(a.ctypes.data), a.shape[0], a.shape[1], a.shape[2], 0)
+
+    @staticmethod
+    def _cube_stats_c(stats):
+        if isinstance(stats, GlobalCubeStats):
+            stats = (stats.median, stats.sigma, stats.low, stats.high)
+        return _lib.CubeStatsC(*[float(np.float32(v)) for v in stats])
+
+    def _collapse(self, fn, cube, rule, out):
+        keep = []
+        pc = self._cube(cube, keep)
+        if out is None:
+            out = self._new_like(cube, int(pc.rows), int(pc.cols))
+        po = self._out_plane(out, keep, int(out.shape[0]), int(out.shape[1]))
+        self._check(fn(self._h, C.byref(pc), int(rule), C.byref(po)))
+        return out
+
+    def collapse_mean(self, cube, rule=CUBE_VALID_NONZERO, out=None):
+        """collapse_mean (core/cube/eager.rs:24-26 = math/simd.rs:216-253; rule 1: collapse_mean_lazy, lazy.rs:246-284) -> (rows, cols):
+        per pixel the f64 sum of the valid samples in ascending z over their count, as f32; bit for bit.  Of the cube's kind."""
+        return self._collapse(self._L.ab_cube_collapse_mean, cube, rule, out)
+
+    def collapse_median(self, cube, rule=CUBE_VALID_NONZERO, out=None):
+        """collapse_median (eager.rs:28-55; rule 1: collapse_median_lazy, lazy.rs:286-329) -> (rows, cols): element [len / 2] of every
+        column's valid samples; bit for bit.  Of the cube's kind."""
+        return self._collapse(self._L.ab_cube_collapse_median, cube, rule, out)
+
+    def compute_global_stats(self, cube, rule=CUBE_VALID_NONZERO, frame_step=1, want_count=False):
+        """compute_global_stats (eager.rs:168-208) -> GlobalCubeStats over the frames z = 0, frame_step, ...; with want_count also n"""
+        keep = []
+        pc = self._cube(cube, keep)
+        st, n = _lib.CubeStatsC(), C.c_uint64(0)
+        self._check(self._L.ab_cube_global_stats(self._h, C.byref(pc), int(rule), int(frame_step), C.byref(st), C.byref(n)))
+        g = GlobalCubeStats(st.median, st.sigma, st.low, st.high)
+        return (g, int(n.value)) if want_count else g
+
+    def compute_global_stats_streaming(self, cube, want_count=False):
+        """compute_global_stats_streaming (lazy.rs:331-370): the lazy path's rule over every cube_streaming_step(depth)-th frame"""
+        depth = int(cube.shape[0]) if len(cube.shape) == 3 else 0
+        return self.compute_global_stats(cube, CUBE_VALID_ABOVE_PADDING, cube_streaming_step(depth), want_count)
+
+    def normalize_with_global(self, frame, stats, out=None):
+        """normalize_with_global (eager.rs:210-222) = normalize_frame_with_stats (lazy.rs:87-99): asinh((10 / sigma) * (clamp(v, low,
+        high) - median)), a non-finite pixel -> 0; the f32 rounding of the f64 asinh of the f32 argument.  Of the frame's kind."""
+        st = self._cube_stats_c(stats)
+        return self._unary(self._L.ab_cube_normalize_frame, frame, out, C.byref(st))
+
+    def export_cube_frames(self, cube, stats, frame_step=1, out=None):
+        """The per-pixel work of export_cube_frames_sampled (eager.rs:224-246) / process_cube_lazy's frame loop (lazy.rs:414-420) up to
+        the PNG encoder -> uint8 (frame_count, rows, cols): every frame_step-th frame normalised and stretched over its own range.
+        Of the cube's kind unless `out` is given."""
+        keep = []
+        pc = self._cube(cube, keep)
+        st = self._cube_stats_c(stats)
+        step = max(1, int(frame_step))
+        frames = (int(pc.depth) + step - 1) // step
+        shape = (frames, int(pc.rows), int(pc.cols))
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=cube.device) if _is_torch(cube) else np.empty(shape, np.uint8)
+        if _is_torch(out):
+            assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == shape
+            ptr, on_dev = out.data_ptr(), 1
+        else:
+            assert out.dtype == np.uint8 and out.flags.c_contiguous and out.shape == shape
+            ptr, on_dev = out.ctypes.data, 0
+        count = C.c_int64(0)
+        self._check(self._L.ab_cube_export_frames(self._h, C.byref(pc), C.byref(st), step, C.c_void_p(ptr), on_dev, C.byref(count)))
+        assert count.value == frames
+        return out
+
+    def extract_spectrum(self, cube, y, x, out=None):
+        """extract_spectrum (eager.rs:57-60) / extract_spectrum_at (lazy.rs:222-239) -> the depth values at (y, x), of the cube's kind;
+        out of bounds raises with the reference's message"""
+        keep = []
+        pc = self._cube(cube, keep)
+        if out is None:
+            out = (torch.empty((int(pc.depth),), dtype=torch.float32, device=cube.device) if _is_torch(cube)
+                   else np.empty((int(pc.depth),), np.float32))
+        if _is_torch(out):
+            assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == pc.depth
+            ptr, on_dev = out.data_ptr(), 1
+        else:
+            assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == pc.depth
+            ptr, on_dev = out.ctypes.data, 0
+        self._check(self._L.ab_cube_extract_spectrum(self._h, C.byref(pc), int(y), int(x), C.c_void_p(ptr), on_dev))
+        return out
 
     # ---- core/stacking/drizzle.rs -------------------------------------------------------------------------
     drizzle_output_dims = staticmethod(drizzle_output_dims)

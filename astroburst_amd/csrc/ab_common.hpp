@@ -61,6 +61,7 @@ enum {
     AB_WS_FFT_TABLES,         // the f32 twiddle tables of every line length 2 .. 16384 + the two window tables of the call (spectrum.hip)
     AB_WS_FFT_A,              // the 2-D FFT's row-pass output, fft_rows x fft_cols complex f32 (spectrum.hip)
     AB_WS_FFT_B,              // its transpose, which the second line pass transforms in place (spectrum.hip)
+    AB_WS_CUBE,               // the device copy of a host-resident spectral cube, for the length of one call (cube.hip)
     AB_WS_SLOTS
 };
 
@@ -266,6 +267,8 @@ inline hipError_t ab_stream_create_masked(ab_ctx *ctx, hipStream_t *out, const c
 int ab_catch(ab_ctx *ctx, const char *fn);
 #define AB_CATCH(ctx) catch (...) { return ab_catch((ctx), __func__); }
 #define AB_CATCH_NOCTX catch (...) { return ab_catch(nullptr, __func__); }
+// for a host-only entry point that returns a value, not a status: the exception is reported, `v` is returned
+#define AB_CATCH_NOCTX_VALUE(v) catch (...) { (void)ab_catch(nullptr, __func__); return (v); }
 
 // Scratch arena: returns a device pointer valid until the next ab_scratch() call with a larger size.
 extern thread_local std::string *ab_tls_error_sink;  // see ab_set_error
@@ -273,6 +276,10 @@ int ab_scratch(ab_ctx *ctx, size_t bytes, void **out);
 int ab_pinned(ab_ctx *ctx, size_t bytes, void **out);
 // persistent workspace `slot` of at least `bytes` (contents are undefined after a growth)
 int ab_workspace(ab_ctx *ctx, int slot, size_t bytes, void **out);
+// the same for a caller whose contract names AB_ERR_NOMEM: exhausted device memory is that status, not AB_ERR_HIP
+int ab_workspace_or_nomem(ab_ctx *ctx, int slot, size_t bytes, void **out);
+// AB_ERR_CANCELLED (with the reference's message) once ab_request_cancel() has been called on the context's root
+int ab_cancel_point(ab_ctx *ctx);
 
 // Frame-parallel fan-out: items 0..n-1 are pulled by up to ctx->register_workers host threads, each driving a child context
 // (own non-blocking stream + workspaces, cached in ctx->workers).  ctx->stream is drained first (unless the caller did and keeps
@@ -311,6 +318,10 @@ struct ab_plane_sel {
     float min_valid = 0.0f;
     int use_dev = 0;
     float center = 0.0f;
+    // the spectral cube's form (cube.hip): cube_rule >= 0 (an ab_cube_valid_rule) replaces the min_valid test, the keys are signed
+    // (deviation keys excepted), and the n candidates are n / frame_len whole frames, frame k at data + k * frame_step * frame_len
+    int cube_rule = -1;
+    int64_t frame_len = 0, frame_step = 1;
 };
 // count, the [count/2] element and (want_lower, even count) the [count/2 - 1] element
 int ab_plane_order_stats(ab_ctx *ctx, const ab_plane_sel &s, int want_lower, uint64_t *count_out, float *mid_out, float *lower_out);

@@ -54,6 +54,13 @@ int ab_catch(ab_ctx *ctx, const char *fn) {
     return code;
 }
 
+int ab_cancel_point(ab_ctx *ctx) {
+    ab_ctx *root = ctx;
+    while (root->parent) root = root->parent;
+    if (root->cancel.load(std::memory_order_relaxed)) return ab_set_error(ctx, AB_ERR_CANCELLED, "Operation cancelled");
+    return AB_OK;
+}
+
 int ab_progress(ab_ctx *ctx, const char *stage, uint64_t current, uint64_t total) {
     ab_ctx *root = ctx;
     while (root->parent) root = root->parent;
@@ -334,7 +341,7 @@ int ab_scratch(ab_ctx *ctx, size_t bytes, void **out) {
     return AB_OK;
 }
 
-int ab_workspace(ab_ctx *ctx, int slot, size_t bytes, void **out) {
+static int workspace(ab_ctx *ctx, int slot, size_t bytes, void **out, bool nomem) {
     if (slot < 0 || slot >= AB_WS_SLOTS) return ab_set_error(ctx, AB_ERR_INVALID, "bad workspace slot %d", slot);
     if (bytes > ctx->ws_bytes[slot]) {
         if (ctx->ws[slot]) {
@@ -343,12 +350,21 @@ int ab_workspace(ab_ctx *ctx, int slot, size_t bytes, void **out) {
             ctx->ws[slot] = nullptr;
             ctx->ws_bytes[slot] = 0;
         }
-        AB_HIP(ctx, hipMalloc(&ctx->ws[slot], bytes));
+        const hipError_t e = hipMalloc(&ctx->ws[slot], bytes);
+        if (nomem && e == hipErrorOutOfMemory) {
+            (void)hipGetLastError();
+            ctx->ws[slot] = nullptr;
+            return ab_set_error(ctx, AB_ERR_NOMEM, "cannot allocate %zu bytes of device memory (workspace %d)", bytes, slot);
+        }
+        AB_HIP(ctx, e);
         ctx->ws_bytes[slot] = bytes;
     }
     *out = ctx->ws[slot];
     return AB_OK;
 }
+
+int ab_workspace(ab_ctx *ctx, int slot, size_t bytes, void **out) { return workspace(ctx, slot, bytes, out, false); }
+int ab_workspace_or_nomem(ab_ctx *ctx, int slot, size_t bytes, void **out) { return workspace(ctx, slot, bytes, out, true); }
 
 int ab_pinned(ab_ctx *ctx, size_t bytes, void **out) {
     if (bytes > ctx->pinned_bytes) {

@@ -7,6 +7,11 @@
 // are non-negative -- candidates are > min_valid >= 0, or the keys are absolute deviations -- so their
 // bit patterns order like the values.  Pass 0 histograms the top 11 bits and yields the candidate count;
 // each requested rank then costs two more streaming passes.  All passes are HBM-bound reads of the plane.
+//
+// The spectral cube's global statistics (cube.hip; eager.rs:168-208, lazy.rs:331-370) take the same select over SIGNED values:
+// ab_plane_sel::cube_rule >= 0 instantiates the histogram kernel a second time, with the cube's two validity rules, the
+// order-preserving key bits ^ (sign ? 0xFFFFFFFF : 0x80000000), and the candidates laid out as every frame_step-th frame of
+// frame_len values.  The host descent is shared; the callers above keep the first instantiation, their arguments and results.
 #include "ab_common.hpp"
 
 #include <algorithm>
@@ -24,20 +29,44 @@ struct SelArgs {
     uint32_t prefix_mask, prefix_val;
     int shift, nbits;
     unsigned int *hist;
+    // the cube's form only (kCube): validity rule, frame geometry -- frame k of `frames` starts at data + k * frame_step * frame_len
+    int cube_rule;
+    int64_t frame_len, frame_step, frames;
 };
 
+// kCube = false: the planes' form, exactly as every caller before the cube had it.  kCube = true: blockIdx.y strides the frames.
+template <bool kCube>
 __global__ __launch_bounds__(kBlock) void plane_select_hist_kernel(const SelArgs a) {
     __shared__ unsigned int lds[2048];
     const uint32_t nb = 1u << a.nbits;
     for (uint32_t i = threadIdx.x; i < nb; i += kBlock) lds[i] = 0;
     __syncthreads();
     const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.n; i += stride) {
-        const float v = a.data[i];
-        if (__builtin_isfinite(v) && v > a.min_valid) {
-            const float k = a.use_dev ? fabsf(v - a.center) : v;
-            const uint32_t key = __float_as_uint(k);
-            if ((key & a.prefix_mask) == a.prefix_val) atomicAdd(&lds[(key >> a.shift) & (nb - 1)], 1u);
+    if constexpr (!kCube) {
+        for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.n; i += stride) {
+            const float v = a.data[i];
+            if (__builtin_isfinite(v) && v > a.min_valid) {
+                const float k = a.use_dev ? fabsf(v - a.center) : v;
+                const uint32_t key = __float_as_uint(k);
+                if ((key & a.prefix_mask) == a.prefix_val) atomicAdd(&lds[(key >> a.shift) & (nb - 1)], 1u);
+            }
+        }
+    } else {
+        for (int64_t f = blockIdx.y; f < a.frames; f += gridDim.y) {
+            const float *frame = a.data + f * a.frame_step * a.frame_len;
+            for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.frame_len; i += stride) {
+                const float v = frame[i];
+                if (__builtin_isfinite(v) && (a.cube_rule == AB_CUBE_VALID_NONZERO ? v != 0.0f : v > 1e-7f)) {
+                    uint32_t key;
+                    if (a.use_dev) {
+                        key = __float_as_uint(fabsf(v - a.center));
+                    } else {
+                        const uint32_t b = __float_as_uint(v);
+                        key = b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+                    }
+                    if ((key & a.prefix_mask) == a.prefix_val) atomicAdd(&lds[(key >> a.shift) & (nb - 1)], 1u);
+                }
+            }
         }
     }
     __syncthreads();
@@ -48,10 +77,20 @@ __global__ __launch_bounds__(kBlock) void plane_select_hist_kernel(const SelArgs
 int run_pass(ab_ctx *ctx, const ab_plane_sel &s, uint32_t mask, uint32_t val, int shift, int nbits, unsigned int *host) {
     const uint32_t nb = 1u << nbits;
     AB_HIP(ctx, hipMemsetAsync(ctx->sel_hist, 0, nb * sizeof(unsigned int), ctx->stream));
-    const int grid = (int)std::max<int64_t>(
-        1, std::min<int64_t>((s.n + kBlock - 1) / kBlock, (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8));
-    SelArgs a{s.data, s.n, s.min_valid, s.use_dev, s.center, mask, val, shift, nbits, ctx->sel_hist};
-    hipLaunchKernelGGL(plane_select_hist_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, a);
+    const int64_t target = (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8;
+    if (s.cube_rule < 0) {
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((s.n + kBlock - 1) / kBlock, target));
+        SelArgs a{s.data, s.n, s.min_valid, s.use_dev, s.center, mask, val, shift, nbits, ctx->sel_hist, -1, 0, 1, 0};
+        hipLaunchKernelGGL(plane_select_hist_kernel<false>, dim3(grid), dim3(kBlock), 0, ctx->stream, a);
+    } else {
+        AB_TRY(ab_cancel_point(ctx));  // the cube's contract: the cancel flag is looked at before every pass over the cube
+        // frames along y (at most `target` rows of blocks: the kernel strides the rest), enough blocks along x to fill the chip
+        const int64_t frames = (s.n + s.frame_len - 1) / s.frame_len;
+        const int gy = (int)std::min<int64_t>(frames, target);
+        const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((s.frame_len + kBlock - 1) / kBlock, (target + gy - 1) / gy));
+        SelArgs a{s.data, s.n, s.min_valid, s.use_dev, s.center, mask, val, shift, nbits, ctx->sel_hist, s.cube_rule, s.frame_len, s.frame_step, frames};
+        hipLaunchKernelGGL(plane_select_hist_kernel<true>, dim3(gx, gy), dim3(kBlock), 0, ctx->stream, a);
+    }
     AB_HIP(ctx, hipGetLastError());
     AB_HIP(ctx, hipMemcpyAsync(host, ctx->sel_hist, nb * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
     AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -110,7 +149,9 @@ int ab_plane_select_ranks(ab_ctx *ctx, const ab_plane_sel &s, int max_ranks, con
         for (auto &g : groups) {
             const uint32_t v = val | (g.first << shifts[level]);
             if (level == 2) {
-                for (const Item &it : g.second) memcpy(&vals[it.r], &v, sizeof(float));
+                // (the cube's signed keys go back through their own inverse; its deviation keys are plain bit patterns like the planes')
+                const uint32_t bits_out = (s.cube_rule >= 0 && !s.use_dev) ? ((v & 0x80000000u) ? (v ^ 0x80000000u) : ~v) : v;
+                for (const Item &it : g.second) memcpy(&vals[it.r], &bits_out, sizeof(float));
                 continue;
             }
             const uint32_t m = mask | (((1u << bits[level]) - 1u) << shifts[level]);

@@ -34,6 +34,7 @@ use crate::core::analysis::star_detection::{DetectedStar, DetectionResult};
 use crate::core::analysis::subframe::{SubframeMetrics, SubframeWeightConfig};
 use crate::core::astrometry::spcc::{SpccConfig, SpccResult, WhiteReference};
 use crate::core::compose::channel_blend::BlendWeight;
+use crate::core::cube::eager::GlobalCubeStats;
 use crate::core::compose::rgb::ProcessedRgb;
 use crate::core::imaging::background::{BackgroundConfig, BackgroundResult};
 use crate::core::imaging::calibration_pipeline::{
@@ -802,6 +803,93 @@ pub fn spectrum_to_u8(hip: &Hip, spectrum: &impl PlaneSrc) -> Result<(Vec<u8>, f
     let (mut mn, mut mx, mut dc) = (0.0f32, 0.0f32, 0.0f32);
     hip.check(unsafe { sys::ab_spectrum_to_u8(hip.ctx, &spectrum.ab(), out.as_mut_ptr(), 0, &mut mn, &mut mx, &mut dc) })?;
     Ok((out, mn, mx, dc))
+}
+
+// ---- core/cube/{eager,lazy}.rs (process_cube_cmd, process_cube_lazy_cmd: cmd/cube.rs) --------------------------------------------------------------------
+/// The two validity rules of the cube paths: eager (`finite && != 0.0`) and lazy (`stats::is_valid_pixel`)
+#[derive(Clone, Copy, PartialEq, Eq, Debug)]
+pub enum CubeValidRule {
+    NonZero = 0,
+    AbovePadding = 1,
+}
+fn cube_ab(cube: &Array3<f32>) -> sys::ab_cube {
+    let (depth, rows, cols) = cube.dim();
+    let s = cube.as_slice().expect("contiguous");
+    sys::ab_cube { data: s.as_ptr(), depth: depth as i64, rows: rows as i64, cols: cols as i64, on_device: 0 }
+}
+fn cube_stats_ab(g: &GlobalCubeStats) -> sys::ab_cube_stats {
+    sys::ab_cube_stats { median: g.median, sigma: g.sigma, low: g.low, high: g.high }
+}
+/// collapse_mean under either rule (rule 1 = LazyCube::collapse_mean_lazy, lazy.rs:246-284, over the decoded frames)
+pub fn collapse_mean_rule(hip: &Hip, cube: &Array3<f32>, rule: CubeValidRule) -> Result<Array2<f32>> {
+    let (_, rows, cols) = cube.dim();
+    let mut out = Array2::<f32>::zeros((rows, cols));
+    let mut po = out.ab_mut();
+    hip.check(unsafe { sys::ab_cube_collapse_mean(hip.ctx, &cube_ab(cube), rule as i32, &mut po) })?;
+    Ok(out)
+}
+/// drop-in for collapse_mean (eager.rs:24-26 = math/simd.rs:216-253): bit for bit
+pub fn collapse_mean(hip: &Hip, cube: &Array3<f32>) -> Result<Array2<f32>> {
+    collapse_mean_rule(hip, cube, CubeValidRule::NonZero)
+}
+/// collapse_median under either rule (rule 1 = LazyCube::collapse_median_lazy, lazy.rs:286-329)
+pub fn collapse_median_rule(hip: &Hip, cube: &Array3<f32>, rule: CubeValidRule) -> Result<Array2<f32>> {
+    let (_, rows, cols) = cube.dim();
+    let mut out = Array2::<f32>::zeros((rows, cols));
+    let mut po = out.ab_mut();
+    hip.check(unsafe { sys::ab_cube_collapse_median(hip.ctx, &cube_ab(cube), rule as i32, &mut po) })?;
+    Ok(out)
+}
+/// drop-in for collapse_median (eager.rs:28-55): bit for bit
+pub fn collapse_median(hip: &Hip, cube: &Array3<f32>) -> Result<Array2<f32>> {
+    collapse_median_rule(hip, cube, CubeValidRule::NonZero)
+}
+/// the frame stride of compute_global_stats_streaming (lazy.rs:334-335): host maths in the library
+pub fn cube_streaming_step(depth: usize) -> usize {
+    unsafe { sys::ab_cube_streaming_step(depth as i64) as usize }
+}
+/// the global statistics over every `frame_step`-th frame under `rule`, and the number of valid values they were taken from
+pub fn compute_global_stats_sampled(hip: &Hip, cube: &Array3<f32>, rule: CubeValidRule, frame_step: usize) -> Result<(GlobalCubeStats, u64)> {
+    let mut st: sys::ab_cube_stats = unsafe { std::mem::zeroed() };
+    let mut n = 0u64;
+    hip.check(unsafe { sys::ab_cube_global_stats(hip.ctx, &cube_ab(cube), rule as i32, frame_step as i64, &mut st, &mut n) })?;
+    Ok((GlobalCubeStats { median: st.median, sigma: st.sigma, low: st.low, high: st.high }, n))
+}
+/// drop-in for compute_global_stats (eager.rs:168-208): bit for bit
+pub fn compute_global_stats(hip: &Hip, cube: &Array3<f32>) -> Result<GlobalCubeStats> {
+    Ok(compute_global_stats_sampled(hip, cube, CubeValidRule::NonZero, 1)?.0)
+}
+/// drop-in for LazyCube::compute_global_stats_streaming (lazy.rs:331-370) over the decoded frames: bit for bit
+pub fn compute_global_stats_streaming(hip: &Hip, cube: &Array3<f32>) -> Result<GlobalCubeStats> {
+    Ok(compute_global_stats_sampled(hip, cube, CubeValidRule::AbovePadding, cube_streaming_step(cube.dim().0))?.0)
+}
+/// drop-in for normalize_with_global (eager.rs:210-222): the f32 rounding of the f64 asinh, within 2 f32 ulp of f32::asinh
+pub fn normalize_with_global(hip: &Hip, data: &impl PlaneSrc, g: &GlobalCubeStats) -> Result<Array2<f32>> {
+    let mut out = Array2::<f32>::zeros(data.dims());
+    let mut po = out.ab_mut();
+    hip.check(unsafe { sys::ab_cube_normalize_frame(hip.ctx, &data.ab(), &cube_stats_ab(g), &mut po) })?;
+    Ok(out)
+}
+/// drop-in for normalize_frame_with_stats (lazy.rs:87-99)
+pub fn normalize_frame_with_stats(hip: &Hip, data: &impl PlaneSrc, stats: &GlobalCubeStats) -> Result<Array2<f32>> {
+    normalize_with_global(hip, data, stats)
+}
+/// the per-pixel work of export_cube_frames_sampled (eager.rs:224-246) / process_cube_lazy's frame loop (lazy.rs:414-420): the L8
+/// bytes of every `step`-th frame, frame k at [k * rows * cols ..], and the frame count; the caller encodes the PNGs
+pub fn export_cube_frames(hip: &Hip, cube: &Array3<f32>, g: &GlobalCubeStats, step: usize) -> Result<(Vec<u8>, usize)> {
+    let (depth, rows, cols) = cube.dim();
+    let step = step.max(1);
+    let frames = (depth + step - 1) / step;
+    let mut out = vec![0u8; frames * rows * cols];
+    let mut count = 0i64;
+    hip.check(unsafe { sys::ab_cube_export_frames(hip.ctx, &cube_ab(cube), &cube_stats_ab(g), step as i64, out.as_mut_ptr(), 0, &mut count) })?;
+    Ok((out, count as usize))
+}
+/// drop-in for extract_spectrum (eager.rs:57-60) with LazyCube::extract_spectrum_at's bounds error (lazy.rs:222-239)
+pub fn extract_spectrum(hip: &Hip, cube: &Array3<f32>, y: usize, x: usize) -> Result<Vec<f32>> {
+    let mut out = vec![0.0f32; cube.dim().0];
+    hip.check(unsafe { sys::ab_cube_extract_spectrum(hip.ctx, &cube_ab(cube), y as i64, x as i64, out.as_mut_ptr(), 0) })?;
+    Ok(out)
 }
 
 // ---- core/stacking/drizzle.rs (calibration.rs:320 drizzle_from_paths, drizzle_rgb_cmd) ----------------------------------------------------------------------

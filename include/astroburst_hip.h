@@ -780,6 +780,73 @@ AB_API int ab_compute_power_spectrum(ab_ctx *ctx, const ab_plane *image, int32_t
 AB_API int ab_spectrum_to_u8(ab_ctx *ctx, const ab_plane *spectrum, uint8_t *out_u8, int32_t out_on_device, float *min_val, float *max_val,
                              float *dc);
 
+/* ---- spectral (IFU) cubes, core/cube/{eager,lazy}.rs (process_cube_cmd, process_cube_lazy_cmd: cmd/cube.rs) ------------------- */
+/* A cube is one contiguous [z][y][x] block of f32, exactly ndarray::Array3<f32>'s standard layout (eager) or the decoded frames
+ * of the mmap'ed file one after another (lazy): voxel (z, y, x) at data[(z * rows + y) * cols + x].  All voxel indexing is 64-bit.
+ * A host-resident cube (on_device = 0) is uploaded once per call into a workspace of the context (depth * rows * cols * 4 bytes,
+ * released by ab_ctx_trim; AB_ERR_NOMEM when it cannot be had).  Every entry: NULL arguments, depth / rows / cols < 1 or output
+ * dims that do not match -> AB_ERR_INVALID; so does depth >= 2^32 or more than 2^40 voxels (per-pixel counts and ranks are u32, as
+ * the reference's are).  Cancellation (ab_ctx_request_cancel) is looked at before each pass over the cube;
+ * there are no progress ticks (the reference has none here).  The collapsed previews' robust_asinh_preview (math/simd.rs:160-214)
+ * is not part of this section: the host keeps it, with the PNG encoder, the mmap, the header parsing, classify_spectral_cube,
+ * build_wavelength_axis and the LRU frame cache. */
+typedef struct {
+    const float *data;
+    int64_t depth, rows, cols;
+    int32_t on_device; /* 0 host, 1 device (HBM) */
+} ab_cube;
+typedef enum {
+    AB_CUBE_VALID_NONZERO = 0,      /* finite && v != 0.0: the eager path (eager.rs:39, :171; math/simd.rs:227) */
+    AB_CUBE_VALID_ABOVE_PADDING = 1 /* finite && v > 1e-7f: the lazy path, stats::is_valid_pixel (core/imaging/stats.rs:11-13) */
+} ab_cube_valid_rule;
+typedef struct { /* GlobalCubeStats (eager.rs:160-166) */
+    float median, sigma, low, high;
+} ab_cube_stats;
+/* collapse_mean_simd (math/simd.rs:216-253) = collapse_mean (eager.rs:24-26), rule 0; collapse_mean_lazy (lazy.rs:246-284), rule 1.
+ * Per pixel: the f64 sum of the valid samples in ascending z, their u32 count, (sum / count as f64) as f32; no valid sample -> 0.
+ * One lane owns a pixel's whole column, so the additions happen in the reference's order: bit for bit.  out: rows x cols, host or
+ * device; asynchronous on the context's stream when it is a device plane.  rule: an ab_cube_valid_rule. */
+AB_API int ab_cube_collapse_mean(ab_ctx *ctx, const ab_cube *cube, int32_t rule, ab_plane_mut *out);
+/* collapse_median (eager.rs:28-55), rule 0; collapse_median_lazy (lazy.rs:286-329), rule 1: element [len / 2] -- the upper median --
+ * of the column's valid samples under f32_cmp (math/median.rs:4-13); no valid sample -> 0.  A radix select along z on the
+ * order-preserving key of the bit pattern (8-bit digits, four passes over the column): bit for bit, negative values and ties
+ * included.  out as above. */
+AB_API int ab_cube_collapse_median(ab_ctx *ctx, const ab_cube *cube, int32_t rule, ab_plane_mut *out);
+/* The frame stride of compute_global_stats_streaming (lazy.rs:334-335), host-only: s = min(32, depth); depth > s ? depth / s : 1.
+ * depth < 1 -> 1. */
+AB_API uint64_t ab_cube_streaming_step(int64_t depth);
+/* compute_global_stats (eager.rs:168-208): rule 0, frame_step 1.  compute_global_stats_streaming (lazy.rs:331-370): rule 1,
+ * frame_step = ab_cube_streaming_step(depth).  The frames used are z = 0, step, 2 * step, ... (step_by; frame_step < 1 is taken as
+ * 1).  With the n valid values of those frames sorted into s: median = s[n / 2], low = s[(n as f64 * 0.01) as usize],
+ * high = s[min((n as f64 * 0.999) as usize, n - 1)] (the rank products in f64 on the host, as written), sigma =
+ * max(d[n / 2] * 1.4826f32, 1e-10f32) with d the sorted |v - median| computed in f32.  n = 0 -> {0, 1, 0, 1}.  count (nullable)
+ * receives n.  An 11/11/10-bit radix select over signed keys, the three ranks descending together, then the select of the
+ * deviations: all four values bit for bit.  Not asynchronous: the histograms are read back. */
+AB_API int ab_cube_global_stats(ab_ctx *ctx, const ab_cube *cube, int32_t rule, int64_t frame_step, ab_cube_stats *stats, uint64_t *count);
+/* normalize_with_global (eager.rs:210-222) = normalize_frame_with_stats (lazy.rs:87-99): a non-finite pixel -> 0, otherwise
+ * asinh((10f32 / sigma) * (clamp(v, low, high) - median)), the argument formed in f32 in that order.  !(low <= high) or a NaN
+ * statistic -> AB_ERR_INVALID (the reference panics in f32::clamp).
+ * DEFINITION of the result: the f32 rounding of the f64 asinh of that f32 argument (computed in f64 on the device).  Rust's
+ * f32::asinh is ln_1p(ax + ax / (hypot(1, 1 / ax) + 1 / ax)) through the platform libm's f32 functions, so its bits depend on the
+ * libm and are not a target: this result is within 2 f32 ulp of the reference's own formula (that formula evaluated in f32 differs
+ * from the definition on 5 - 14 % of values, depending on their distribution, by at most 2 ulp).  An argument that overflows f32 is outside the contract.
+ * img and out: the same dims, host or device; asynchronous for device planes. */
+AB_API int ab_cube_normalize_frame(ab_ctx *ctx, const ab_plane *img, const ab_cube_stats *stats, ab_plane_mut *out);
+/* The per-pixel work of export_cube_frames_sampled (eager.rs:224-246) and of process_cube_lazy's frame loop (lazy.rs:414-420) up
+ * to the PNG encoder: for every z = k * step (frame_step < 1 is taken as 1) the frame normalised as above, its (min, max)
+ * (find_minmax_simd, math/simd.rs:263-271), range = max(max - min, 1e-10), inv = 255f32 / range and byte = (v.is_finite() &&
+ * v > 1e-7) ? ((v - min) * inv).clamp(0, 255) as u8 : 0 (infra/render/grayscale.rs:10-29; everything at or below the median renders
+ * 0).  Frame k lands at out_u8 + k * rows * cols (host or device: out_on_device), frame_count (nullable) = ceil(depth / step).
+ * Two launches for all frames: the normalised f32 frames are never written, the per-frame ranges stay on the device.
+ * Asynchronous for a device output. */
+AB_API int ab_cube_export_frames(ab_ctx *ctx, const ab_cube *cube, const ab_cube_stats *stats, int64_t frame_step, uint8_t *out_u8,
+                                 int32_t out_on_device, int64_t *frame_count);
+/* extract_spectrum (eager.rs:57-60), LazyCube::extract_spectrum_at (lazy.rs:222-239): the depth values at (y, x) into out (host or
+ * device: out_on_device).  y >= rows or x >= cols (or negative) -> AB_ERR_INVALID, "Pixel (y, x) out of bounds".  Asynchronous
+ * for a device cube with a device output.  A host cube is read where it lies (nothing is uploaded): its column is gathered on
+ * the host, and with a device output the call has synchronised the stream and finished the copy when it returns. */
+AB_API int ab_cube_extract_spectrum(ab_ctx *ctx, const ab_cube *cube, int64_t y, int64_t x, float *out, int32_t out_on_device);
+
 /* ---- bench support: a plain float4 device copy, the measured HBM ceiling ---- */
 AB_API int ab_bench_copy(ab_ctx *ctx, const float *src_dev, float *dst_dev, size_t n_floats);
 

@@ -163,7 +163,7 @@ def generate():
         L.append("#[derive(Clone, Copy, Debug)]")
         L.append(f"pub struct {name} {{")
         for (fname, ctype, ptr, dims), (_, off, _) in zip(fields, lay):
-            t = rust_type(ctype, ptr, ctype == "float" and name == "ab_plane" or ctype == "char" or (name in ("ab_calibration_masters", "ab_batch_channel_input") and ctype == "ab_plane"),
+            t = rust_type(ctype, ptr, ctype == "float" and name in ("ab_plane", "ab_cube") or ctype == "char" or (name in ("ab_calibration_masters", "ab_batch_channel_input") and ctype == "ab_plane"),
                           structs, enums)
             for d in reversed(dims):
                 t = f"[{t}; {d}]"
