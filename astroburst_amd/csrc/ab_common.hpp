@@ -403,6 +403,9 @@ int ab_normalize_params_many_device(ab_ctx *ctx, const float *const *planes, siz
 
 int ab_phase_correlate_device(ab_ctx *ctx, const float *ref, int64_t ref_rows, int64_t ref_cols, int64_t ref_ld, const float *tgt,
                               int64_t tgt_rows, int64_t tgt_cols, int64_t tgt_ld, double *dx, double *dy, double *confidence);
+// the same for n targets of one size against one reference, a batch per stage (ab_phase_correlate_device is the case n = 1)
+int ab_phase_correlate_many_device(ab_ctx *ctx, const float *ref, int64_t ref_ld, const float *const *tgts, const int64_t *tgt_ld, size_t n, int64_t rows,
+                                   int64_t cols, double *dx, double *dy, double *confidence);
 int ab_align_channel_affine_device(ab_ctx *ctx, const float *ref, const float *tgt, int64_t rows, int64_t cols, int num_threads,
                                    ab_affine_align_result *out);
 int ab_shift_device(ab_ctx *ctx, const float *src, int64_t rows, int64_t cols, int64_t src_ld, double dy, double dx, float *out);

@@ -30,9 +30,6 @@
 #include <cmath>
 #include <thread>
 
-int ab_phase_correlate_device(ab_ctx *ctx, const float *ref, int64_t ref_rows, int64_t ref_cols, int64_t ref_ld, const float *tgt,
-                              int64_t tgt_rows, int64_t tgt_cols, int64_t tgt_ld, double *dx, double *dy, double *confidence);
-
 namespace {
 
 constexpr size_t kMaxStars = 120;            // affine.rs:8-22

@@ -65,11 +65,6 @@
 #include "sort_ops.hpp"
 #include "sortnet_gen.hpp"
 
-int ab_phase_correlate_device(ab_ctx *ctx, const float *ref, int64_t ref_rows, int64_t ref_cols, int64_t ref_ld, const float *tgt,
-                              int64_t tgt_rows, int64_t tgt_cols, int64_t tgt_ld, double *dx, double *dy, double *confidence);
-int ab_align_channel_affine_device(ab_ctx *ctx, const float *ref, const float *tgt, int64_t rows, int64_t cols, int num_threads,
-                                   ab_affine_align_result *out);
-
 namespace {
 
 constexpr int kBlock = 256;

@@ -6,12 +6,6 @@
 
 #include <cmath>
 
-int ab_phase_correlate_device(ab_ctx *ctx, const float *ref, int64_t ref_rows, int64_t ref_cols, int64_t ref_ld, const float *tgt,
-                              int64_t tgt_rows, int64_t tgt_cols, int64_t tgt_ld, double *dx, double *dy, double *confidence);
-int ab_phase_correlate_many_device(ab_ctx *ctx, const float *ref, int64_t ref_ld, const float *const *tgts, const int64_t *tgt_ld, size_t n, int64_t rows,
-                                   int64_t cols, double *dx, double *dy, double *confidence);
-int ab_shift_device(ab_ctx *ctx, const float *src, int64_t rows, int64_t cols, int64_t src_ld, double dy, double dx, float *out);
-
 namespace {
 int32_t round_to_i32(double v) {  // `result.offset.0.round() as i32` (combine.rs:135-136): saturating, NaN -> 0
     const double r = std::round(v);
@@ -53,15 +47,12 @@ extern "C" int ab_stack_images(ab_ctx *ctx, const ab_plane *planes, size_t n, co
         ld[staged] = st[staged].cols;
     }
     const size_t plane_bytes = (size_t)min_rows * (size_t)min_cols * sizeof(float);
-    // every frame against frame 0 as ONE batch per stage (AB_STACK_PAIRWISE=1: a phase_correlate call per pair, round 4's form)
+    // every frame against frame 0 as ONE batch per stage
     std::vector<double> sdx(n, 0.0), sdy(n, 0.0), scf(n, 0.0);
-    static const bool pairwise = ab_dev_env("AB_STACK_PAIRWISE") != nullptr;
-    if (rc == AB_OK && !pairwise)
+    if (rc == AB_OK)
         rc = ab_phase_correlate_many_device(ctx, dp[0], ld[0], dp.data() + 1, ld.data() + 1, n - 1, min_rows, min_cols, sdx.data() + 1, sdy.data() + 1, scf.data() + 1);
     for (size_t i = 1; rc == AB_OK && i < n; ++i) {
-        double dx = sdx[i], dy = sdy[i], conf = scf[i];
-        if (pairwise) rc = ab_phase_correlate_device(ctx, dp[0], min_rows, min_cols, ld[0], dp[i], min_rows, min_cols, ld[i], &dx, &dy, &conf);
-        if (rc != AB_OK) break;
+        const double dx = sdx[i], dy = sdy[i];
         if (offsets_dy_dx) {
             offsets_dy_dx[2 * i] = round_to_i32(dy);
             offsets_dy_dx[2 * i + 1] = round_to_i32(dx);

@@ -100,3 +100,92 @@ def test_stack_images_align_device_planes(ctx, oracle):
     res = ctx.stack_images([torch.from_numpy(f).cuda() for f in frames], align=True)
     out, rej, offs = oracle.stack_images_align(frames)
     assert res.offsets == offs and np.array_equal(res.image.cpu().numpy(), out) and res.rejected_pixels == rej
+
+
+def round_to_i32(v):
+    """`result.offset.0.round() as i32` (combine.rs:135-136) as stack_images.hip's round_to_i32 does it: half away from zero, NaN -> 0."""
+    return 0 if np.isnan(v) else int(np.sign(v) * np.floor(abs(v) + 0.5))
+
+
+_FIELD = []
+
+
+def smooth_field():
+    """the aperiodic field of the cases above (smoothed noise), made once"""
+    if not _FIELD:
+        from scipy.ndimage import gaussian_filter
+        _FIELD.append(gaussian_filter(np.random.default_rng(1).standard_normal((1300, 1300)), 2.0).astype(np.float32) * 1000)
+    return _FIELD[0]
+
+
+def refined_by_the_crop_rule(oracle, ref, tgt):
+    """Which way phase_correlation.rs:66-80 goes for a pair above 512 px, from the oracle's coarse shift by the crop arithmetic:
+    True = the centred crops have equal sizes and the pair is refined, False = the target's crop is clipped and the coarse answer kept."""
+    rows, cols = ref.shape
+    ds = (min(512, rows), min(512, cols))
+    cdx, cdy, _ = oracle.correlate_single(oracle.area_downsample(ref, *ds), oracle.area_downsample(tgt, *ds))
+    cy = min(max(rows // 2 + round_to_i32(cdy * rows / 512.0), 0), rows - 1)
+    cx = min(max(cols // 2 + round_to_i32(cdx * cols / 512.0), 0), cols - 1)
+    size = lambda c, n: min(c + 256, n) - max(c - 256, 0)      # extract_crop, :91-103
+    return (size(cy, rows), size(cx, cols)) == (size(rows // 2, rows), size(cols // 2, cols))
+
+
+def frames_two_rounds():
+    """19 frames = 18 targets = a round of 16 and a round of 2; target 3 is constant (degenerate: it leaves its round's list of
+    correlated pairs, so every later pair of the round sits one place further down), target 9 holds NaN / +-inf pixels."""
+    base = smooth_field()
+    rng = np.random.default_rng(11)
+    cut = lambda sy, sx: base[700 - sy:700 - sy + 96, 600 - sx:600 - sx + 128].copy()
+    shifts = [(dy, dx) for dy in (-4, -2, 0, 1, 3, 5) for dx in (-5, -1, 4)]   # 18 distinct shifts of an aperiodic field
+    frames = [cut(0, 0)] + [cut(dy, dx) + rng.standard_normal((96, 128)).astype(np.float32) for dy, dx in shifts]
+    frames[3] = np.full((96, 128), 100.0, np.float32)
+    frames[9][10, 10], frames[9][20, 30], frames[9][5, 5] = np.nan, np.inf, -np.inf
+    return frames
+
+
+def frames_coarse_to_fine():
+    """520 x 300 (above 512: coarse-to-fine), four targets: row shifts 2 and -3 leave the target's 512-row crop whole (refined), 9 and
+    -11 push it over the border (crop sizes differ: the coarse answer is kept) -- both outcomes in one batch."""
+    base = smooth_field()
+    rng = np.random.default_rng(12)
+    cut = lambda sy, sx: base[40 - sy:40 - sy + 520, 50 - sx:50 - sx + 300].copy()
+    return [cut(0, 0)] + [cut(sy, sx) + rng.standard_normal((520, 300)).astype(np.float32) for sy, sx in [(2, -3), (9, 5), (-3, 4), (-11, -7)]]
+
+
+def frames_degenerate_reference():
+    ref = make_pattern(96, 128)
+    rng = np.random.default_rng(13)
+    return [np.full(ref.shape, 100.0, np.float32)] + [shift_array(ref, dy, dx) + rng.standard_normal(ref.shape).astype(np.float32)
+                                                      for dy, dx in [(3, -2), (-4, 5), (1, 1)]]
+
+
+@pytest.mark.parametrize("case", ["two_rounds", "coarse_to_fine", "degenerate_reference"])
+def test_stack_images_offsets_equal_pairwise_phase_correlate(ctx, oracle, case):
+    """stack_images(align) registers every frame on frame 0 in batches of 16 pairs; phase_correlate handles one pair.  Both must give
+    the same (dy, dx) for every frame -- the batch is the single pair's arithmetic in the single pair's order -- and the oracle's."""
+    frames = {"two_rounds": frames_two_rounds, "coarse_to_fine": frames_coarse_to_fine, "degenerate_reference": frames_degenerate_reference}[case]()
+    pairs = [ctx.phase_correlate(frames[0], f) for f in frames[1:]]
+    for dx, dy, _ in pairs:                                     # the noise keeps every shift away from a rounding tie
+        assert min(abs(abs(v) % 1.0 - 0.5) for v in (dx, dy)) > 1e-3, (dx, dy)
+    pairwise = [(0, 0)] + [(round_to_i32(dy), round_to_i32(dx)) for dx, dy, _ in pairs]
+    offsets = ctx.stack_images(frames, align=True).offsets
+    assert offsets == pairwise
+    assert offsets == oracle.stack_images_align(frames)[2]
+    if case == "two_rounds":
+        assert offsets[3] == (0, 0) and pairs[2] == (0.0, 0.0, 0.0)                    # the constant target
+        assert len(set(offsets[1:3] + offsets[4:])) == 17                            # distinct: a pair landing in another's slot shows
+    elif case == "coarse_to_fine":
+        assert [refined_by_the_crop_rule(oracle, frames[0], f) for f in frames[1:]] == [True, False, True, False]
+        for got, f in zip(pairs, frames[1:]):
+            check(got, oracle.phase_correlate(frames[0], f))
+    else:
+        assert offsets == [(0, 0)] * 4 and all(p == (0.0, 0.0, 0.0) for p in pairs)
+
+
+def test_phase_correlate_single_pair_non_power_of_two(ctx, oracle):
+    """33 x 17 through phase_correlate: a batch of one pair (gridDim.y == 1) on transforms padded to 64 x 32."""
+    rng = np.random.default_rng(33)
+    a = make_pattern(33, 17) + rng.standard_normal((33, 17)).astype(np.float32) * 10
+    b = shift_array(a, 3, -2) + rng.standard_normal((33, 17)).astype(np.float32)
+    a[0, 0] = np.nan
+    check(ctx.phase_correlate(a, b), oracle.phase_correlate(a, b))
