@@ -174,6 +174,29 @@ class RLResultC(C.Structure):  # RLResult's scalars (deconvolution.rs:214-219)
     _fields_ = [("iterations_run", C.c_size_t), ("convergence", C.c_double)]
 
 
+class PsfEstimationConfigC(C.Structure):  # PsfEstimationConfig (psf_estimation.rs:16-25)
+    _fields_ = [("num_stars", C.c_size_t), ("cutout_radius", C.c_size_t), ("saturation_threshold", C.c_double),
+                ("min_peak_fraction", C.c_double), ("max_ellipticity", C.c_double), ("edge_margin", C.c_size_t),
+                ("max_center_distance_fraction", C.c_double)]
+
+
+class PsfStarC(C.Structure):  # StarCandidate (psf_estimation.rs:4-14)
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("peak", C.c_double), ("flux", C.c_double), ("fwhm", C.c_double),
+                ("ellipticity", C.c_double), ("distance_from_center", C.c_double), ("snr", C.c_double)]
+
+
+class PsfResultC(C.Structure):  # PsfResult's scalars (psf_estimation.rs:41-50) + the outcome and the two counts
+    _fields_ = [("outcome", C.c_int32), ("kernel_size", C.c_size_t), ("average_fwhm", C.c_double), ("average_ellipticity", C.c_double),
+                ("spread_pixels", C.c_double), ("stars_used", C.c_size_t), ("stars_rejected", C.c_size_t), ("stars_detected", C.c_size_t),
+                ("stars_filtered", C.c_size_t)]
+
+
+AB_PSF_OK, AB_PSF_NO_STARS_DETECTED, AB_PSF_NO_STARS_PASSED, AB_PSF_NO_CUTOUTS = range(4)
+AB_PSF_MAX_CUTOUT_RADIUS = 31
+PSF_OUTCOME_MESSAGES = {AB_PSF_NO_STARS_DETECTED: "No stars detected in image", AB_PSF_NO_STARS_PASSED: "No stars passed quality filters",
+                        AB_PSF_NO_CUTOUTS: "Failed to extract star cutouts"}  # the reference's Err strings (:65, :87, :108)
+
+
 class WaveletConfigC(C.Structure):  # WaveletConfig (wavelet.rs:10-15): the threshold list as pointer + count
     _fields_ = [("num_scales", C.c_size_t), ("thresholds", C.POINTER(C.c_float)), ("num_thresholds", C.c_size_t),
                 ("linear_denoise", C.c_int32)]
@@ -414,6 +437,11 @@ def lib() -> C.CDLL:
                                           C.POINTER(StfParamsC)]
     L.ab_generate_gaussian_psf.argtypes = [C.c_size_t, C.c_float, C.POINTER(C.c_float)]
     L.ab_richardson_lucy.argtypes = [vp, pp, pp, C.POINTER(RLConfigC), pp, C.POINTER(RLResultC)]
+    L.ab_psf_estimation_config_default.argtypes = [C.POINTER(PsfEstimationConfigC)]
+    L.ab_psf_estimation_config_default.restype = None
+    L.ab_psf_select_stars.argtypes = [C.POINTER(PsfStarC), C.c_size_t, C.POINTER(PsfEstimationConfigC), C.c_double, C.c_int64, C.c_int64,
+                                      C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.ab_estimate_psf.argtypes = [vp, pp, C.POINTER(PsfEstimationConfigC), pp, C.POINTER(PsfStarC), C.c_size_t, C.POINTER(PsfResultC)]
     L.ab_wavelet_scale_thresholds.argtypes = [C.c_double, C.POINTER(WaveletConfigC), C.POINTER(C.c_float)]
     L.ab_wavelet_denoise.argtypes = [vp, pp, C.POINTER(WaveletConfigC), pp, C.POINTER(WaveletResultC)]
     f32p = C.POINTER(C.c_float)

@@ -120,6 +120,31 @@ class DrizzleResult:  # types/stacking.rs DrizzleResult (drizzle.rs:335-344)
 
 
 @dataclass
+class PsfStar:  # StarCandidate (psf_estimation.rs:4-14)
+    x: float
+    y: float
+    peak: float
+    flux: float
+    fwhm: float
+    ellipticity: float
+    distance_from_center: float
+    snr: float
+
+
+@dataclass
+class PsfResult:  # psf_estimation.rs:41-50 (kernel: the (2 r + 1)^2 f32 plane psf_to_kernel yields) + the two counts
+    kernel: object
+    kernel_size: int
+    average_fwhm: float
+    average_ellipticity: float
+    stars_used: list
+    stars_rejected: int
+    spread_pixels: float
+    stars_detected: int
+    stars_filtered: int
+
+
+@dataclass
 class FftResult:  # core/analysis/fft.rs:11-17
     spectrum: object
     display_rows: int
@@ -242,6 +267,45 @@ def generate_gaussian_psf(size: int, sigma: float) -> np.ndarray:
     if rc != _lib.AB_OK:
         raise AstroBurstError(rc, "ab_generate_gaussian_psf: bad arguments")
     return out
+
+
+def _psf_config(num_stars=None, cutout_radius=None, saturation_threshold=None, min_peak_fraction=None, max_ellipticity=None,
+                edge_margin=None, max_center_distance_fraction=None):
+    """PsfEstimationConfig::default() (psf_estimation.rs:27-39, filled in by the library) with the given fields replaced"""
+    cfg = _lib.PsfEstimationConfigC()
+    _lib.lib().ab_psf_estimation_config_default(C.byref(cfg))
+    for name, val, conv in (("num_stars", num_stars, int), ("cutout_radius", cutout_radius, int), ("saturation_threshold", saturation_threshold, float),
+                            ("min_peak_fraction", min_peak_fraction, float), ("max_ellipticity", max_ellipticity, float),
+                            ("edge_margin", edge_margin, int), ("max_center_distance_fraction", max_center_distance_fraction, float)):
+        if val is not None:
+            if conv is int and int(val) < 0:
+                raise AstroBurstError(_lib.AB_ERR_INVALID, f"{name} must not be negative")
+            setattr(cfg, name, conv(val))
+    return cfg
+
+
+def _psf_star_array(stars):
+    arr = (_lib.PsfStarC * max(len(stars), 1))()
+    for i, s in enumerate(stars):
+        t = (s.x, s.y, s.peak, s.flux, s.fwhm, s.ellipticity, s.distance_from_center, s.snr) if hasattr(s, "fwhm") else tuple(s)
+        arr[i] = _lib.PsfStarC(*[float(v) for v in t])
+    return arr
+
+
+def psf_select_stars(stars, max_val: float, rows: int, cols: int, **config):
+    """The quality filter, score_star, the stable descending sort and take(num_stars) of estimate_psf (psf_estimation.rs:68-92,
+    :509-516) -> (indices of the selected stars in selection order, number of stars that passed the filter).  stars: PsfStar
+    objects or 8-tuples (x, y, peak, flux, fwhm, ellipticity, distance_from_center, snr); max_val: the image's maximum; config:
+    PsfEstimationConfig's fields.  Host scalar maths in the library: no GPU."""
+    cfg = _psf_config(**config)
+    n = len(stars)
+    arr = _psf_star_array(stars)
+    idx = (C.c_size_t * max(n, 1))()
+    sel, flt = C.c_size_t(0), C.c_size_t(0)
+    rc = _lib.lib().ab_psf_select_stars(arr, n, C.byref(cfg), float(max_val), int(rows), int(cols), idx, n, C.byref(sel), C.byref(flt))
+    if rc != _lib.AB_OK:
+        raise AstroBurstError(rc, "ab_psf_select_stars: bad arguments")
+    return [int(idx[i]) for i in range(sel.value)], int(flt.value)
 
 
 def power_spectrum_dims(rows: int, cols: int):
@@ -1649,6 +1713,39 @@ class Context:
         res = _lib.RLResultC()
         self._check(self._L.ab_richardson_lucy(self._h, C.byref(pi), C.byref(pk), C.byref(cfg), C.byref(po), C.byref(res)))
         return out, int(res.iterations_run), float(res.convergence)
+
+    # ---- core/imaging/psf_estimation.rs --------------------------------------------------------------------
+    psf_select_stars = staticmethod(psf_select_stars)
+
+    def estimate_psf(self, image, out=None, **config) -> PsfResult:
+        """estimate_psf + psf_to_kernel (psf_estimation.rs:52-149) -> PsfResult.  image: numpy (host) or a CUDA tensor (device); the
+        (2 * cutout_radius + 1)^2 f32 kernel is of the image's kind unless `out` is given -- a device kernel goes straight into
+        richardson_lucy.  config: PsfEstimationConfig's fields (num_stars, cutout_radius, saturation_threshold, min_peak_fraction,
+        max_ellipticity, edge_margin, max_center_distance_fraction); the rest are its defaults.  The reference's three Err returns
+        raise AstroBurstError with the reference's string as .message (code AB_ERR_INVALID)."""
+        cfg = _psf_config(**config)
+        keep = []
+        pi = self._plane(image, keep)
+        size = 2 * int(cfg.cutout_radius) + 1
+        if cfg.cutout_radius <= _lib.AB_PSF_MAX_CUTOUT_RADIUS:   # (beyond it the library answers AB_ERR_UNSUPPORTED before it looks at the plane)
+            if out is None:
+                out = self._new_like(image, size, size)
+            if not _is_torch(out) and (out.dtype != np.float32 or not out.flags.c_contiguous):
+                raise AstroBurstError(_lib.AB_ERR_INVALID, "the kernel output must be a contiguous float32 array")
+            orows, ocols = (int(out.shape[0]), int(out.shape[1])) if len(out.shape) == 2 else (0, 0)
+            po = self._out_plane(out, keep, orows, ocols)
+        else:
+            po = Plane(None, size, size, 0)
+        cap = int(cfg.num_stars) if 0 < cfg.num_stars < (1 << 20) else (1 << 20 if cfg.num_stars else 0)
+        stars = (_lib.PsfStarC * max(cap, 1))()
+        res = _lib.PsfResultC()
+        self._check(self._L.ab_estimate_psf(self._h, C.byref(pi), C.byref(cfg), C.byref(po), stars, cap, C.byref(res)))
+        if res.outcome != _lib.AB_PSF_OK:
+            raise AstroBurstError(_lib.AB_ERR_INVALID, _lib.PSF_OUTCOME_MESSAGES[res.outcome])
+        used = [PsfStar(s.x, s.y, s.peak, s.flux, s.fwhm, s.ellipticity, s.distance_from_center, s.snr)
+                for s in stars[:min(int(res.stars_used), cap)]]
+        return PsfResult(out, int(res.kernel_size), float(res.average_fwhm), float(res.average_ellipticity), used, int(res.stars_rejected),
+                         float(res.spread_pixels), int(res.stars_detected), int(res.stars_filtered))
 
     # ---- core/imaging/wavelet.rs ---------------------------------------------------------------------------
     wavelet_scale_thresholds = staticmethod(wavelet_scale_thresholds)

@@ -62,6 +62,7 @@ enum {
     AB_WS_FFT_A,              // the 2-D FFT's row-pass output, fft_rows x fft_cols complex f32 (spectrum.hip)
     AB_WS_FFT_B,              // its transpose, which the second line pass transforms in place (spectrum.hip)
     AB_WS_CUBE,               // the device copy of a host-resident spectral cube, for the length of one call (cube.hip)
+    AB_WS_PSF,                // PSF estimation: statistics partials, the candidate counter, the f64 / f32 kernel and its scalars (psf.hip)
     AB_WS_SLOTS
 };
 
@@ -323,6 +324,9 @@ struct ab_plane_sel {
     int cube_rule = -1;
     int64_t frame_len = 0, frame_step = 1;
 };
+// a third validity rule of the signed form, internal (psf.hip: compute_image_stats' median, psf_estimation.rs:182-185): every finite
+// value is a candidate -- zeros and negative pixels included, nothing is dropped by a min_valid test
+constexpr int AB_SEL_VALID_FINITE = 2;
 // count, the [count/2] element and (want_lower, even count) the [count/2 - 1] element
 int ab_plane_order_stats(ab_ctx *ctx, const ab_plane_sel &s, int want_lower, uint64_t *count_out, float *mid_out, float *lower_out);
 // the general form: ranks_of(count, ranks) fills up to max_ranks 0-based ranks (clamped to count - 1) and returns how many;

@@ -12,6 +12,7 @@
 // ab_plane_sel::cube_rule >= 0 instantiates the histogram kernel a second time, with the cube's two validity rules, the
 // order-preserving key bits ^ (sign ? 0xFFFFFFFF : 0x80000000), and the candidates laid out as every frame_step-th frame of
 // frame_len values.  The host descent is shared; the callers above keep the first instantiation, their arguments and results.
+// The PSF estimation's image median (psf.hip) is the signed form over one frame with AB_SEL_VALID_FINITE: every finite pixel counts.
 #include "ab_common.hpp"
 
 #include <algorithm>
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(kBlock) void plane_select_hist_kernel(const SelArgs
             const float *frame = a.data + f * a.frame_step * a.frame_len;
             for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.frame_len; i += stride) {
                 const float v = frame[i];
-                if (__builtin_isfinite(v) && (a.cube_rule == AB_CUBE_VALID_NONZERO ? v != 0.0f : v > 1e-7f)) {
+                if (__builtin_isfinite(v) && (a.cube_rule == AB_SEL_VALID_FINITE || (a.cube_rule == AB_CUBE_VALID_NONZERO ? v != 0.0f : v > 1e-7f))) {
                     uint32_t key;
                     if (a.use_dev) {
                         key = __float_as_uint(fabsf(v - a.center));

@@ -42,6 +42,7 @@ use crate::core::imaging::calibration_pipeline::{
 };
 use crate::core::imaging::curves::LevelsParams;
 use crate::core::imaging::masked_stretch::{MaskedStretchConfig, MaskedStretchResult, MaskedStretchRgbResult};
+use crate::core::imaging::psf_estimation::{PsfEstimationConfig, PsfResult, StarCandidate};
 use crate::core::imaging::star_mask::{StarMaskConfig, StarMaskResult};
 use crate::core::imaging::wavelet::{WaveletConfig, WaveletResult};
 use crate::core::stacking::calibration::CalibrationConfig;
@@ -710,6 +711,99 @@ pub fn richardson_lucy(hip: &Hip, image: &impl PlaneSrc, psf: &impl PlaneSrc, co
     let mut po = out.ab_mut();
     hip.with_progress(progress, || hip.check(unsafe { sys::ab_richardson_lucy(hip.ctx, &image.ab(), &psf.ab(), &cfg, &mut po, &mut res) }))?;
     Ok(RLResult { image: out, iterations_run: res.iterations_run, convergence: res.convergence, elapsed_ms: start.elapsed().as_millis() as u64 })
+}
+
+// ---- core/imaging/psf_estimation.rs (deconvolve_rl_cmd with use_empirical_psf) ---------------------------------------------------------------------------
+fn psf_cfg(config: &PsfEstimationConfig) -> sys::ab_psf_estimation_config {
+    sys::ab_psf_estimation_config {
+        num_stars: config.num_stars,
+        cutout_radius: config.cutout_radius,
+        saturation_threshold: config.saturation_threshold,
+        min_peak_fraction: config.min_peak_fraction,
+        max_ellipticity: config.max_ellipticity,
+        edge_margin: config.edge_margin,
+        max_center_distance_fraction: config.max_center_distance_fraction,
+    }
+}
+fn psf_star(s: &sys::ab_psf_star) -> StarCandidate {
+    StarCandidate { x: s.x, y: s.y, peak: s.peak, flux: s.flux, fwhm: s.fwhm, ellipticity: s.ellipticity, distance_from_center: s.distance_from_center, snr: s.snr }
+}
+/// PsfEstimationConfig::default() (psf_estimation.rs:27-39) as the library fills it in
+pub fn psf_estimation_config_default() -> PsfEstimationConfig {
+    let mut c: sys::ab_psf_estimation_config = unsafe { std::mem::zeroed() };
+    unsafe { sys::ab_psf_estimation_config_default(&mut c) };
+    PsfEstimationConfig {
+        num_stars: c.num_stars,
+        cutout_radius: c.cutout_radius,
+        saturation_threshold: c.saturation_threshold,
+        min_peak_fraction: c.min_peak_fraction,
+        max_ellipticity: c.max_ellipticity,
+        edge_margin: c.edge_margin,
+        max_center_distance_fraction: c.max_center_distance_fraction,
+    }
+}
+/// the quality filter, score_star, the stable descending sort and take(num_stars) of estimate_psf (psf_estimation.rs:68-92, :509-516):
+/// (indices of the selected stars in selection order, how many passed the filter); host maths in the library
+pub fn psf_select_stars(stars: &[StarCandidate], config: &PsfEstimationConfig, max_val: f64, rows: usize, cols: usize) -> Result<(Vec<usize>, usize)> {
+    let c: Vec<sys::ab_psf_star> = stars
+        .iter()
+        .map(|s| sys::ab_psf_star { x: s.x, y: s.y, peak: s.peak, flux: s.flux, fwhm: s.fwhm, ellipticity: s.ellipticity, distance_from_center: s.distance_from_center, snr: s.snr })
+        .collect();
+    let mut idx = vec![0usize; stars.len()];
+    let (mut selected, mut filtered) = (0usize, 0usize);
+    let rc = unsafe {
+        sys::ab_psf_select_stars(c.as_ptr(), c.len(), &psf_cfg(config), max_val, rows as i64, cols as i64, idx.as_mut_ptr(), idx.len(), &mut selected, &mut filtered)
+    };
+    if rc != sys::AB_OK {
+        bail!("psf_select_stars: invalid arguments (status {rc})");
+    }
+    idx.truncate(selected);
+    Ok((idx, filtered))
+}
+/// estimate_psf (psf_estimation.rs:52-134) with the kernel left where `kernel` lies -- a device plane goes straight into
+/// richardson_lucy; PsfResult.kernel stays empty in that case.  The reference's three Err strings come back as errors.
+pub fn estimate_psf_into(hip: &Hip, image: &impl PlaneSrc, config: &PsfEstimationConfig, kernel: &mut impl PlaneDst) -> Result<PsfResult> {
+    let cap = config.num_stars.min(1 << 20);
+    let mut stars: Vec<sys::ab_psf_star> = vec![unsafe { std::mem::zeroed() }; cap.max(1)];
+    let mut res: sys::ab_psf_result = unsafe { std::mem::zeroed() };
+    let mut pk = kernel.ab_mut();
+    hip.check(unsafe { sys::ab_estimate_psf(hip.ctx, &image.ab(), &psf_cfg(config), &mut pk, stars.as_mut_ptr(), cap, &mut res) })?;
+    match res.outcome {
+        sys::AB_PSF_OK => {}
+        sys::AB_PSF_NO_STARS_DETECTED => bail!("No stars detected in image"),
+        sys::AB_PSF_NO_STARS_PASSED => bail!("No stars passed quality filters"),
+        _ => bail!("Failed to extract star cutouts"),
+    }
+    Ok(PsfResult {
+        kernel: Vec::new(),
+        kernel_size: res.kernel_size,
+        average_fwhm: res.average_fwhm,
+        average_ellipticity: res.average_ellipticity,
+        stars_used: stars[..res.stars_used.min(cap)].iter().map(psf_star).collect(),
+        stars_rejected: res.stars_rejected,
+        spread_pixels: res.spread_pixels,
+    })
+}
+/// drop-in for estimate_psf (psf_estimation.rs:52-134): the image is never downloaded when it is a device plane
+pub fn estimate_psf(hip: &Hip, image: &impl PlaneSrc, config: &PsfEstimationConfig) -> Result<PsfResult> {
+    let size = config.cutout_radius * 2 + 1;
+    let mut kernel = Array2::<f32>::zeros((size, size));
+    let mut res = estimate_psf_into(hip, image, config, &mut kernel)?;
+    res.kernel = kernel.rows().into_iter().map(|row| row.to_vec()).collect();
+    Ok(res)
+}
+/// drop-in for psf_to_kernel (psf_estimation.rs:136-149): host-only, the reference's own loop
+pub fn psf_to_kernel(psf: &PsfResult) -> Array2<f32> {
+    let size = psf.kernel_size;
+    let mut kernel = Array2::<f32>::zeros((size, size));
+    for (y, row) in psf.kernel.iter().enumerate() {
+        for (x, &val) in row.iter().enumerate() {
+            if y < size && x < size {
+                kernel[[y, x]] = val;
+            }
+        }
+    }
+    kernel
 }
 
 // ---- core/imaging/wavelet.rs (wavelet_denoise_cmd) ------------------------------------------------------------------------------------------------------

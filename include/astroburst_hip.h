@@ -673,6 +673,64 @@ AB_API int ab_generate_gaussian_psf(size_t size, float sigma, float *out_host);
 AB_API int ab_richardson_lucy(ab_ctx *ctx, const ab_plane *img, const ab_plane *psf, const ab_rl_config *cfg, ab_plane_mut *out,
                               ab_rl_result *res);
 
+/* ---- empirical PSF estimation, core/imaging/psf_estimation.rs (deconvolve_rl_cmd with use_empirical_psf) -------------------- */
+typedef struct { /* PsfEstimationConfig (psf_estimation.rs:16-25); Default (:27-39): 30 / 15 / 0.95 / 0.10 / 0.3 / 30 / 0.7 */
+    size_t num_stars;
+    size_t cutout_radius;
+    double saturation_threshold;
+    double min_peak_fraction;
+    double max_ellipticity;
+    size_t edge_margin;
+    double max_center_distance_fraction;
+} ab_psf_estimation_config;
+typedef struct { /* StarCandidate (:4-14) */
+    double x, y, peak, flux, fwhm, ellipticity, distance_from_center, snr;
+} ab_psf_star;
+typedef enum { /* estimate_psf's Ok and its three Err strings (:64-66, :86-88, :107-109) */
+    AB_PSF_OK = 0,
+    AB_PSF_NO_STARS_DETECTED = 1,      /* "No stars detected in image" */
+    AB_PSF_NO_STARS_PASSED = 2,        /* "No stars passed quality filters" */
+    AB_PSF_NO_CUTOUTS = 3              /* "Failed to extract star cutouts" */
+} ab_psf_outcome;
+typedef struct { /* PsfResult's scalars (:41-50); the kernel and stars_used are arguments of their own */
+    int32_t outcome; /* an ab_psf_outcome; the fields below are meaningful for AB_PSF_OK only (the two counts always) */
+    size_t kernel_size; /* 2 * cutout_radius + 1 */
+    double average_fwhm, average_ellipticity, spread_pixels;
+    size_t stars_used;     /* min(num_stars, stars_filtered): the length of PsfResult.stars_used */
+    size_t stars_rejected; /* the reference's candidates.len() - count (:131): filtered stars minus extracted cutouts */
+    size_t stars_detected; /* detect_stars_for_psf's list (:62) */
+    size_t stars_filtered; /* after the quality filter (:68-84) */
+} ab_psf_result;
+#define AB_PSF_MAX_CUTOUT_RADIUS 31
+AB_API void ab_psf_estimation_config_default(ab_psf_estimation_config *cfg);
+/* The quality filter (:68-84), score_star (:509-516), the stable descending sort (:90) and take(num_stars) (:92) over n stars,
+ * host-only scalar maths, bit for bit the reference's: out_idx (cap entries) receives the indices of the selected stars in
+ * selection order, *out_selected their number (min(num_stars, filtered, cap)), *out_filtered how many passed the filter.
+ * max_val = the image's maximum as f64 (LocalStats.max_val), rows / cols its dims.  NULL stars with n > 0, NULL cfg -> AB_ERR_INVALID;
+ * out_idx may be NULL when cap = 0. */
+AB_API int ab_psf_select_stars(const ab_psf_star *stars, size_t n, const ab_psf_estimation_config *cfg, double max_val, int64_t rows,
+                               int64_t cols, size_t *out_idx, size_t cap, size_t *out_selected, size_t *out_filtered);
+/* estimate_psf (:52-134) followed by psf_to_kernel (:136-149).  img host or device (a device plane is never downloaded: candidate
+ * lists, per-star records and nothing else cross to the host); kernel_out host or device, (2 * cutout_radius + 1)^2 f32 -- a device
+ * kernel_out can be handed straight to ab_richardson_lucy; stars_out (nullable when stars_cap = 0) receives the first
+ * min(stars_used, stars_cap) entries of PsfResult.stars_used.
+ * The reference's three Err returns are RESULTS: the call returns AB_OK, res->outcome names the case and kernel_out is untouched.
+ * AB_ERR_INVALID: NULL arguments; rows or cols <= 2 * edge_margin (the reference's `h - margin` loop bounds wrap or are empty);
+ * num_stars = 0 (the reference divides 0 / 0); a kernel plane that is not (2 r + 1)^2; 2^31 pixels or more; a non-finite pixel
+ * (the reference's behaviour on NaN is an accident of partial_cmp; found by the statistics pass at no extra cost).
+ * AB_ERR_UNSUPPORTED: cutout_radius > AB_PSF_MAX_CUTOUT_RADIUS (31: the cutout is kept in LDS as f64).
+ * EXACTNESS.  Given the same detection threshold (:198) everything is reproduced bit for bit: every f64 field of every star, the
+ * selection order, the f32 kernel and the three scalars -- every f64 accumulation chain is summed in the reference's order (raster
+ * order over a window, ascending order over a sorted slice), unfused, with IEEE sqrt and division.  The ONE exception is stddev
+ * (:178-180): sum and sum_sq are formed by a fixed parallel reduction tree (identical from run to run), which cannot reproduce the
+ * rounding of the reference's sequential sums.  The relative error of either sum is bounded by about n * 2^-53, amplified in var by
+ * mean^2 / var; it changes the result only if a pixel lies inside that band around threshold = median + 5 * stddev.  Where the pixels
+ * are integer-valued (raw ADU) and sum_sq < 2^53 both sums are exact in any order and the result is bit-identical without
+ * qualification.  max_val and the median (the [n / 2] order statistic, negative pixels included) are exact.
+ * Not asynchronous: lists and records are read back. */
+AB_API int ab_estimate_psf(ab_ctx *ctx, const ab_plane *img, const ab_psf_estimation_config *cfg, ab_plane_mut *kernel_out,
+                           ab_psf_star *stars_out, size_t stars_cap, ab_psf_result *res);
+
 /* ---- drizzle stacking, core/stacking/drizzle.rs (calibration.rs:320 drizzle_from_paths, drizzle_rgb_cmd) ------------------- */
 typedef struct { /* DrizzleConfig (types/stacking.rs) */
     double scale;   /* clamped to [1, 4] (drizzle.rs:274) */
