@@ -38,10 +38,9 @@ enum {
     AB_WS_STATS,              // state block, 65 536-bin histograms and partials of the statistics chain (stats.hip)
     AB_WS_SHARD,              // (sum f64, count u32) partial planes of the frame-sharded stack (sharded.hip)
     AB_WS_SUBSAMPLE,          // the <= ~100 000-pixel subsample normalize_for_detection takes its percentiles from
-    AB_WS_DETECT_DEV,         // FrameDev + the tile statistics of the chained detection (detect.hip)
     AB_WS_REGISTER_GROUP,     // the target-side matcher workspaces of a group of frames (affine.hip)
     AB_WS_PHASE_TABLES,       // two sets of Hann windows + FFT twiddles of the phase correlation, kept between calls (phase_corr.hip)
-    AB_WS_PIPE_TABLES,        // plane pointers + transforms of the fed background pipeline (detect.hip: ab_bg_pipeline_begin_fed)
+    AB_WS_PIPE_TABLES,        // plane pointers + transforms of a background pipeline (detect.hip: ab_bg_pipeline_begin, ab_bg_pipeline_begin_fed)
     AB_WS_PIPE_SUBSAMPLE,     // its subsamples (one per plane: the chunks' percentile launches overlap)
     AB_WS_SCOPE0,             // eight slots for the planes an entry point needs for the length of one call (masked stretch: luminance,
     AB_WS_SCOPE1,             // mask, disc table, coverage counter, chain state; SPCC: luminance, apertures, fluxes): grow-only like every
@@ -351,7 +350,8 @@ struct ab_frame_cand;
 int ab_detect_stars_group_device(ab_ctx *ctx, const float *const *imgs, int G, int64_t rows, int64_t cols, double sigma_threshold, const ab_pixel_xf *xf,
                                  const double (*bg)[2], size_t max_keep, std::vector<ab_detected_star> *stars /* [G] */,
                                  const struct ab_frame_cand *cand = nullptr /* [G], nullable: the frames' candidate lists (ab_bg_pipeline_cand) */);
-int ab_detect_stars_device(ab_ctx *ctx, const float *img, int64_t rows, int64_t cols, int64_t ld, double sigma_threshold,
+// detect_stars of one contiguous plane, every star: a group of one whose background is estimated here unless the caller has it
+int ab_detect_stars_device(ab_ctx *ctx, const float *img, int64_t rows, int64_t cols, double sigma_threshold,
                            std::vector<ab_detected_star> *stars, double *bg_median_out, double *bg_sigma_out,
                            ab_pixel_xf xf = ab_pixel_xf(), size_t max_keep = (size_t)-1 /* only the brightest max_keep stars are wanted */,
                            bool normalize_first = false /* normalize_for_detection's transform is derived and applied on the device */,
@@ -369,13 +369,15 @@ struct ab_bg_pipeline {
     const ab_pixel_xf *xf_host = nullptr;  // fed pipeline: plane i's transform, valid once ab_bg_pipeline_get(i) has returned
     struct ab_bg_feed_impl *feed = nullptr;  // the feeder thread of a pipeline whose planes are still landing (detect.hip)
     // the candidate lists of plane i's tiles (DEVICE; valid once ab_bg_pipeline_get(i) has returned): entries at cand_ent + (i * ntiles
-    // + tile) * cand_cap (uint2 {position in the tile, raw bits}), counts / cuts at [i * ntiles + tile].  nullptr: the pipeline left none
+    // + tile) * kCandCap (uint2 {position in the tile, raw bits}), counts / cuts at [i * ntiles + tile].  nullptr: the pipeline left none
     // (tiles smaller than 256 px).  detect.hip: label_bgtile_body
     void *cand_ent = nullptr;
     unsigned int *cand_cnt = nullptr;
     float *cand_cut = nullptr;
     int cand_step = 0;  // the background tile's edge (256)
 };
+// entries per 256 x 256 tile of a candidate list (~1000 on a sky tile at 2.5 sigma: the Gaussian tail + the stars' pixels)
+constexpr int kCandCap = 2048;
 // plane i's lists, as ab_detect_stars_group_device takes them
 struct ab_frame_cand {
     const void *ent = nullptr;
@@ -385,7 +387,7 @@ struct ab_frame_cand {
 static inline ab_frame_cand ab_bg_pipeline_cand(const ab_bg_pipeline *p, size_t i) {
     ab_frame_cand c;
     if (p && p->on && p->cand_ent) {
-        c.ent = (const char *)p->cand_ent + i * (size_t)p->ntiles * (size_t)2048 * 8u;  // (kCandCap entries of 8 bytes: detect.hip)
+        c.ent = (const char *)p->cand_ent + i * (size_t)p->ntiles * (size_t)kCandCap * sizeof(uint2);
         c.cnt = p->cand_cnt + i * (size_t)p->ntiles;
         c.cut = p->cand_cut + i * (size_t)p->ntiles;
     }

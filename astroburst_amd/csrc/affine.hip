@@ -975,7 +975,7 @@ int frame_stars(ab_ctx *ctx, const float *img, int64_t rows, int64_t cols, std::
         const double b2[1][2] = {{bg[0], bg[1]}};
         AB_TRY(ab_detect_stars_group_device(ctx, &img, 1, rows, cols, kDetectionSigma, xf, b2, kMaxStars, &stars, cand));
     } else {
-        AB_TRY(ab_detect_stars_device(ctx, img, rows, cols, cols, kDetectionSigma, &stars, &m, &s, xf ? *xf : ab_pixel_xf(), kMaxStars,
+        AB_TRY(ab_detect_stars_device(ctx, img, rows, cols, kDetectionSigma, &stars, &m, &s, xf ? *xf : ab_pixel_xf(), kMaxStars,
                                       /*normalize_first=*/xf == nullptr, xf ? bg : nullptr));  // top_n_stars (:272-277)
     }
     out->clear();

@@ -39,21 +39,8 @@ namespace {
 
 constexpr double kMadToSigma = 1.4826;
 
-// Per-frame parameters that one kernel of the detection chain produces and the next consumes, kept in device memory so that the
-// host need not sit between them: the percentile kernel writes `xf`, the tile kernel reads it, bg_threshold_kernel reduces the
-// tiles to (bg_median, bg_sigma, threshold), the labelling and moment kernels read those.  A kernel given a null FrameDev uses
-// its by-value arguments instead (the stand-alone entry points, and the default registration path: see `chained` in
-// ab_detect_stars_device for why the host still joins after the percentiles and after the tiles).
-struct FrameDev {
-    ab_pixel_xf xf;
-    double bg_median, bg_sigma, threshold;
-    unsigned int finite;  // finite subsample values (< 100: xf.on = 0)
-    unsigned int pad;
-};
-
 // the candidate lists a tile launch leaves for the labelling pass (tile_stream.hpp: CandSink), planes x tiles of the LAUNCH:
-// ent[(plane * tiles + tile) * kCandCap ..], cnt / cut[plane * tiles + tile].  ent == nullptr: no lists.
-constexpr int kCandCap = 2048;  // entries per 256 x 256 tile (~1000 on a sky tile at 2.5 sigma: the Gaussian tail + the stars' pixels)
+// ent[(plane * tiles + tile) * kCandCap ..], cnt / cut[plane * tiles + tile] (kCandCap: ab_common.hpp).  ent == nullptr: no lists.
 struct TileCand {
     uint2 *ent = nullptr;
     unsigned int *cnt = nullptr;
@@ -176,7 +163,6 @@ __global__ __launch_bounds__(absel::kBlock) void tile_background_kernel(const fl
 // plane * tiles-per-plane + tile) with however many blocks it has, and the last block to finish leaves the list empty again.
 __global__ __launch_bounds__(tb::kThreads) void tile_background_bucket_kernel(const float *__restrict__ img_arg, int rows, int cols, int64_t ld,
                                                                               int step, int ntx, const ab_pixel_xf xf_arg, TileOut *__restrict__ out_arg,
-                                                                              const FrameDev *__restrict__ fd,
                                                                               const float *const *__restrict__ many_planes = nullptr,
                                                                               const ab_pixel_xf *__restrict__ many_xf = nullptr,
                                                                               unsigned int *__restrict__ fail = nullptr, int tiles_per_plane = 0) {
@@ -202,7 +188,7 @@ __global__ __launch_bounds__(tb::kThreads) void tile_background_bucket_kernel(co
             img = many_planes[plane];
             out += (size_t)plane * per_plane;
         }
-        const ab_pixel_xf xf = many_planes ? many_xf[plane] : (fd ? fd->xf : xf_arg);
+        const ab_pixel_xf xf = many_planes ? many_xf[plane] : xf_arg;
         const int ty0 = (int)(tile / (unsigned int)ntx) * step, tx0 = (int)(tile % (unsigned int)ntx) * step;
         const int y1 = min(ty0 + step, rows), x1 = min(tx0 + step, cols);
         // thread (tx, ty) of the 256 x 2 layout walks column tx0 + tx downwards, two rows per slot: consecutive lanes read
@@ -255,9 +241,8 @@ __global__ __launch_bounds__(tb::kThreads) void tile_background_bucket_kernel(co
 // CU in flight at ~100 VGPRs each; a tile it cannot settle exactly is appended to `fail` for the kernel above.
 __global__ __launch_bounds__(ts::kThreads) void tile_background_stream_kernel(const float *__restrict__ img_arg, int rows, int cols, int64_t ld, int step,
                                                                               int ntx, const ab_pixel_xf xf_arg, TileOut *__restrict__ out,
-                                                                              const FrameDev *__restrict__ fd, const float *const *__restrict__ many_planes,
-                                                                              const ab_pixel_xf *__restrict__ many_xf, unsigned int *__restrict__ fail,
-                                                                              const TileCand cand) {
+                                                                              const float *const *__restrict__ many_planes, const ab_pixel_xf *__restrict__ many_xf,
+                                                                              unsigned int *__restrict__ fail, const TileCand cand) {
     __shared__ ts::Shared sh;
 #ifdef AB_TILE_VGPR_FLOOR
     // developer experiment: a register floor caps the tile workgroups per CU (four of them take 156 of the 160 KB of LDS, and no
@@ -271,7 +256,7 @@ __global__ __launch_bounds__(ts::kThreads) void tile_background_stream_kernel(co
         img = many_planes[blockIdx.y];
         out += (size_t)blockIdx.y * gridDim.x;
     }
-    const ab_pixel_xf xf = many_planes ? many_xf[blockIdx.y] : (fd ? fd->xf : xf_arg);
+    const ab_pixel_xf xf = many_planes ? many_xf[blockIdx.y] : xf_arg;
     ts::TileRect r;
     r.img = img;
     r.ld = ld;
@@ -320,14 +305,12 @@ __device__ __forceinline__ bool labelled(const unsigned int *__restrict__ mask, 
 // Round 4: 256 threads and 16 KB of LDS per block (was 1024 threads, 64 KB).  Alone the kernel takes the same 22 us, but inside a
 // registration batch a 16-wave workgroup waited for a CU with sixteen free wave slots and 64 KB of LDS while the warp's and the
 // tile kernel's small workgroups kept slipping in ahead of it: 110 us on average.  Same-box A/B of the stage: 12.9 -> 12.4 ms;
-// roots_kernel likewise (kRootsBlock 1024 -> 256): another 0.5 - 0.8 ms.
+// roots_many_kernel likewise (kRootsBlock 1024 -> 256): another 0.5 - 0.8 ms.
 constexpr int kInitBlock = 256, kInitSub = 4 * kInitBlock, kInitRounds = 16, kInitCap = 4 * kInitSub;
 __device__ __forceinline__ void label_init_body(const float *__restrict__ img, int rows, int cols, int64_t ld,
-                                                                double threshold_arg, const ab_pixel_xf xf_arg, int *__restrict__ parent,
+                                                                double threshold, const ab_pixel_xf xf, int *__restrict__ parent,
                                                                 unsigned int *__restrict__ mask, int *__restrict__ plist, unsigned int *nlab,
-                                                                int vec_ok, const FrameDev *__restrict__ fd) {
-    const double threshold = fd ? fd->threshold : threshold_arg;
-    const ab_pixel_xf xf = fd ? fd->xf : xf_arg;
+                                                                int vec_ok) {
     __shared__ int found[kInitCap];
     __shared__ unsigned int nfound, base;
     if (threadIdx.x == 0) nfound = 0;
@@ -1365,11 +1348,9 @@ __device__ __forceinline__ MomGeom mom_geom(const CompStat &s, int lane, bool li
 
 __device__ __forceinline__ void comp_moments_body(const float *__restrict__ img, int cols, int64_t ld, const int *__restrict__ parent,
                                                            const unsigned int *__restrict__ mask, const int *__restrict__ roots, const CompStat *__restrict__ st, unsigned int ncomp,
-                                                           double bg_median_arg, const ab_pixel_xf xf_arg, CompRec *__restrict__ rec,
-                                                           const FrameDev *__restrict__ fd, const unsigned int *__restrict__ sel = nullptr,
+                                                           double bg_median, const ab_pixel_xf xf, CompRec *__restrict__ rec,
+                                                           const unsigned int *__restrict__ sel = nullptr,
                                                            const unsigned int *__restrict__ nsel = nullptr, bool two_hop = false, int mpitch = 0) {
-    const double bg_median = fd ? fd->bg_median : bg_median_arg;
-    const ab_pixel_xf xf = fd ? fd->xf : xf_arg;
     const unsigned int base = (blockIdx.x * 4 + (threadIdx.x >> 6)) * kMomPerWave;
     const int lane = threadIdx.x & 63;
     // with a selection (comp_select_many_kernel) the wave's components are sel[base ..] of the *nsel selected ones and their
@@ -1838,18 +1819,9 @@ __global__ __launch_bounds__(kSelThreads) void comp_select_many_kernel(const Det
     }
 }
 
-__global__ __launch_bounds__(kInitBlock) void label_init_kernel(const float *__restrict__ img, int rows, int cols, int64_t ld, double threshold_arg,
-                                                                const ab_pixel_xf xf_arg, int *__restrict__ parent, unsigned int *__restrict__ mask,
-                                                                int *__restrict__ plist, unsigned int *nlab, int vec_ok, const FrameDev *__restrict__ fd) { AB_LATENCY_KERNEL_PRIO();
-    label_init_body(img, rows, cols, ld, threshold_arg, xf_arg, parent, mask, plist, nlab, vec_ok, fd);
-}
 __global__ __launch_bounds__(kInitBlock) void label_init_many_kernel(const DetGroup g, int rows, int cols, int64_t ld, int vec_ok) { AB_LATENCY_KERNEL_PRIO();
     const int f = blockIdx.y;
-    label_init_body(g.img[f], rows, cols, ld, g.threshold[f], g.xf[f], g.parent[f], g.mask[f], g.plist[f], g.counters[f] + 1, vec_ok, nullptr);
-}
-__global__ __launch_bounds__(256) void label_merge_kernel(int rows, int cols, int *parent, const unsigned int *__restrict__ mask, const int *__restrict__ plist,
-                                                          const unsigned int *__restrict__ nlab) { AB_LATENCY_KERNEL_PRIO();
-    label_merge_body(rows, cols, parent, mask, plist, nlab);
+    label_init_body(g.img[f], rows, cols, ld, g.threshold[f], g.xf[f], g.parent[f], g.mask[f], g.plist[f], g.counters[f] + 1, vec_ok);
 }
 __global__ __launch_bounds__(256) void label_merge_many_kernel(const DetGroup g, int rows, int cols) { AB_LATENCY_KERNEL_PRIO();
     const int f = blockIdx.y;
@@ -1884,10 +1856,6 @@ __global__ __launch_bounds__(256) void label_border_many_kernel(const DetGroup g
     label_border_body(rows, cols, g.parent[f], g.mask[f], g.blist[f] + (size_t)r * g.blist_stride, g.lcnt[f] + (kRegions + r) * kRegionPitch, blockIdx.x / kRegions,
                       gridDim.x / kRegions, g.mask_pitch, g.tile_h, g.tile_w);
 }
-__global__ __launch_bounds__(kRootsBlock) void roots_kernel(const int *__restrict__ parent, const int *__restrict__ plist, const unsigned int *__restrict__ nlab,
-                                                            int *__restrict__ roots, int *__restrict__ cid, unsigned int *nroots, unsigned int cap) { AB_LATENCY_KERNEL_PRIO();
-    roots_body(parent, plist, nlab, roots, cid, nroots, cap);
-}
 __global__ __launch_bounds__(kRootsBlock) void roots_many_kernel(const DetGroup g, unsigned int cap) { AB_LATENCY_KERNEL_PRIO();
     const int f = blockIdx.y;
     if (g.tiled) {
@@ -1898,14 +1866,9 @@ __global__ __launch_bounds__(kRootsBlock) void roots_many_kernel(const DetGroup 
     }
     roots_body(g.parent[f], g.plist[f], g.counters[f] + 1, g.roots[f], g.cid[f], g.counters[f], cap, g.chained ? g.st[f] : nullptr);
 }
-__global__ __launch_bounds__(256) void comp_init_kernel(CompStat *st, unsigned int n) { AB_LATENCY_KERNEL_PRIO(); comp_init_body(st, n); }
 __global__ __launch_bounds__(256) void comp_init_many_kernel(const DetGroup g) { AB_LATENCY_KERNEL_PRIO();
     const int f = blockIdx.y;
     comp_init_body(g.st[f], g.ncomp[f]);
-}
-__global__ __launch_bounds__(256) void comp_stats_kernel(int rows, int cols, int *parent, const int *__restrict__ cid, CompStat *st, const int *__restrict__ plist,
-                                                         const unsigned int *__restrict__ nlab) { AB_LATENCY_KERNEL_PRIO();
-    comp_stats_body<false>(rows, cols, parent, cid, st, plist, nlab);
 }
 __global__ __launch_bounds__(256) void comp_stats_many_kernel(const DetGroup g, int rows, int cols, int64_t ld) { AB_LATENCY_KERNEL_PRIO();
     const int f = blockIdx.y;
@@ -1923,25 +1886,13 @@ __global__ __launch_bounds__(256) void comp_stats_many_kernel(const DetGroup g, 
     }
     comp_stats_body<true>(rows, cols, g.parent[f], g.cid[f], g.st[f], g.plist[f], g.counters[f] + 1, g.img[f], ld, g.xf[f], g.bg_median[f]);
 }
-__global__ __launch_bounds__(256) void comp_moments_kernel(const float *__restrict__ img, int cols, int64_t ld, const int *__restrict__ parent,
-                                                           const unsigned int *__restrict__ mask, const int *__restrict__ roots, const CompStat *__restrict__ st,
-                                                           unsigned int ncomp, double bg_median_arg, const ab_pixel_xf xf_arg, CompRec *__restrict__ rec,
-                                                           const FrameDev *__restrict__ fd) { AB_LATENCY_KERNEL_PRIO();
-    comp_moments_body(img, cols, ld, parent, mask, roots, st, ncomp, bg_median_arg, xf_arg, rec, fd);
-}
 __global__ __launch_bounds__(256) void comp_moments_many_kernel(const DetGroup g, int cols, int64_t ld) { AB_LATENCY_KERNEL_PRIO();
     const int f = blockIdx.y;
-    comp_moments_body(g.img[f], cols, ld, g.parent[f], g.mask[f], g.roots[f], g.st[f], g.ncomp[f], g.bg_median[f], g.xf[f], g.rec[f], nullptr,
+    comp_moments_body(g.img[f], cols, ld, g.parent[f], g.mask[f], g.roots[f], g.st[f], g.ncomp[f], g.bg_median[f], g.xf[f], g.rec[f],
                       g.sel[f], g.sel[f] ? g.counters[f] + 2 : nullptr, g.recs != 0, g.tiled ? g.mask_pitch : 0);
 }
 
 // ---- normalize_for_detection (affine.rs:24-53) ------------------------------------------------------
-__global__ __launch_bounds__(256) void subsample_kernel(const float *__restrict__ img, int64_t len, int64_t step,
-                                                        float *__restrict__ out, int64_t nout) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < nout) out[i] = img[i * step];
-}
-
 __global__ __launch_bounds__(256) void normalize_kernel(const float *__restrict__ img, int64_t len, double lo, double inv_range,
                                                         float *__restrict__ out) {
     const int64_t stride = (int64_t)gridDim.x * 256;
@@ -2010,9 +1961,9 @@ __device__ __forceinline__ void find_rank_2048(const unsigned int *hist, unsigne
 
 // SRC supplies sample i; the sweeps are written once for both sources below
 template <class SRC>
-__device__ __forceinline__ void percentiles_body(const SRC &src, unsigned int ns, PercentileOut *__restrict__ out, FrameDev *__restrict__ fd,
-                                                 ab_pixel_xf *__restrict__ dxf = nullptr /* the transform itself, into a device table ... */,
-                                                 ab_pixel_xf *__restrict__ hxf = nullptr /* ... and into its pinned host mirror (fed pipeline) */) {
+__device__ __forceinline__ void percentiles_body(const SRC &src, unsigned int ns, PercentileOut *__restrict__ out,
+                                                 ab_pixel_xf *__restrict__ dxf /* nullable: the transform itself, into a device table ... */,
+                                                 ab_pixel_xf *__restrict__ hxf /* ... and into its pinned host mirror (fed pipeline) */) {
     __shared__ unsigned int hist[2][2048];
     __shared__ unsigned int wave_tot[16], bcast[2];
     const int t = threadIdx.x;
@@ -2037,10 +1988,6 @@ __device__ __forceinline__ void percentiles_body(const SRC &src, unsigned int ns
     if (m < 100u) {  // affine.rs:34-36: too few samples, the frame is used as it is
         if (t == 0) {
             *out = PercentileOut{0.0f, 0.0f, m, 0u};
-            if (fd) {
-                fd->xf = ab_pixel_xf();
-                fd->finite = m;
-            }
             if (dxf) *dxf = ab_pixel_xf();
             if (hxf) *hxf = ab_pixel_xf();
         }
@@ -2082,17 +2029,13 @@ __device__ __forceinline__ void percentiles_body(const SRC &src, unsigned int ns
     if (t == 0) {
         const float lo = ordered_value(prefix[0]), hi = ordered_value(prefix[1]);
         *out = PercentileOut{lo, hi, m, 0u};
-        if (fd || dxf || hxf) {  // the host's arithmetic (xf_from_percentiles), on the device
+        if (dxf || hxf) {  // the host's arithmetic (xf_from_percentiles), on the device
             ab_pixel_xf xf;
             const double range = (double)hi - (double)lo;
             if (!(range < 1e-15)) {
                 xf.lo = (double)lo;
                 xf.inv = 1.0 / range;
                 xf.on = 1;
-            }
-            if (fd) {
-                fd->xf = xf;
-                fd->finite = m;
             }
             if (dxf) *dxf = xf;
             if (hxf) *hxf = xf;
@@ -2103,7 +2046,7 @@ __device__ __forceinline__ void percentiles_body(const SRC &src, unsigned int ns
 // the subsample held in registers: <= kPctPer values per thread, all loads in flight at once; the three sweeps then read
 // registers.  (Sweeping the buffer in memory cost one dependent L2 round trip per value and sweep -- the LDS atomics keep the
 // compiler from pipelining the loads: 92 us for the workgroup.  Gathering every `step`-th pixel of the plane in this kernel,
-// without subsample_kernel, was worse still: 100 000 scattered cache lines through ONE compute unit, 0.3 ms.)
+// without subsample_many_kernel, was worse still: 100 000 scattered cache lines through ONE compute unit, 0.3 ms.)
 constexpr int kPctPer = 100;
 struct RegSample {
     float v[kPctPer];
@@ -2114,16 +2057,6 @@ struct RegSample {
             if ((unsigned int)(j * 1024) < ns) f(v[j]);  // block-uniform; slots past ns hold NaN
     }
 };
-__global__ __launch_bounds__(1024) void percentiles_reg_kernel(const float *__restrict__ sub, unsigned int ns, PercentileOut *__restrict__ out,
-                                                                FrameDev *__restrict__ fd) {
-    RegSample s;
-#pragma unroll
-    for (int j = 0; j < kPctPer; ++j) {
-        const unsigned int i = (unsigned int)(j * 1024) + threadIdx.x;
-        s.v[j] = i < ns ? sub[i] : __builtin_nanf("");
-    }
-    percentiles_body(s, ns, out, fd);
-}
 
 // larger subsamples (planes of 100 000 .. 200 000 pixels are sampled at step 1): swept from a buffer
 struct MemSample {
@@ -2136,13 +2069,9 @@ struct MemSample {
         }
     }
 };
-__global__ __launch_bounds__(1024) void percentiles_mem_kernel(const float *__restrict__ sub, unsigned int ns, PercentileOut *__restrict__ out,
-                                                                FrameDev *__restrict__ fd) {
-    percentiles_body(MemSample{sub}, ns, out, fd);
-}
 
-// The same for MANY planes of one size in two launches (the registration batch: the percentiles of all 64 frames before any
-// worker starts).  One percentile workgroup per plane -- 64 of them side by side take what one takes, where each used to sit in
+// The launches: the planes of one size (one, or a registration batch's 64 before any worker starts) in two launches.  One
+// percentile workgroup per plane -- 64 of them side by side take what one takes, where each used to sit in
 // its frame's chain: 60 .. 100 us of ONE compute unit during which the three other streams of its hardware queue waited.
 constexpr int kManyPlanes = 128;
 struct PlaneList {
@@ -2161,63 +2090,12 @@ __global__ __launch_bounds__(1024) void percentiles_many_reg_kernel(const float 
         const unsigned int i = (unsigned int)(j * 1024) + threadIdx.x;
         s.v[j] = i < ns ? mine[i] : __builtin_nanf("");
     }
-    percentiles_body(s, ns, out + blockIdx.x, (FrameDev *)nullptr, dxf ? dxf + blockIdx.x : nullptr, hxf ? hxf + blockIdx.x : nullptr);
+    percentiles_body(s, ns, out + blockIdx.x, dxf ? dxf + blockIdx.x : nullptr, hxf ? hxf + blockIdx.x : nullptr);
 }
 __global__ __launch_bounds__(1024) void percentiles_many_mem_kernel(const float *__restrict__ sub, unsigned int ns, PercentileOut *__restrict__ out,
                                                                      ab_pixel_xf *__restrict__ dxf, ab_pixel_xf *__restrict__ hxf) {
-    percentiles_body(MemSample{sub + (size_t)blockIdx.x * ns}, ns, out + blockIdx.x, (FrameDev *)nullptr, dxf ? dxf + blockIdx.x : nullptr,
+    percentiles_body(MemSample{sub + (size_t)blockIdx.x * ns}, ns, out + blockIdx.x, dxf ? dxf + blockIdx.x : nullptr,
                      hxf ? hxf + blockIdx.x : nullptr);
-}
-
-
-// estimate_background's reduction of the tiles (star_detection.rs:70-83) on the device: the upper median of the valid tiles'
-// medians and of their sigmas (sorted[len / 2]; any order of equal values gives the same element), then detect_stars'
-// threshold (:103).  One workgroup; a tile's rank is counted against all others (<= kBgTiles tiles: 256 for a 4096^2 frame).
-constexpr int kBgTiles = 2048;
-struct BgOut {
-    double bg_median, bg_sigma;
-};
-__global__ __launch_bounds__(1024) void bg_threshold_kernel(const TileOut *__restrict__ tiles, int ntiles, double sigma_threshold,
-                                                            FrameDev *__restrict__ fd, BgOut *__restrict__ out) {
-    __shared__ double med[kBgTiles], sig[kBgTiles];
-    __shared__ unsigned int nv_s;
-    __shared__ double res[2];
-    if (threadIdx.x == 0) {
-        nv_s = 0;
-        res[0] = 0.0;  // no valid tile: (0, 1) (:70-72)
-        res[1] = 1.0;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < ntiles; i += 1024) {
-        const TileOut t = tiles[i];
-        if (t.valid) {
-            const unsigned int at = atomicAdd(&nv_s, 1u);
-            med[at] = t.median;
-            sig[at] = t.sigma;
-        }
-    }
-    __syncthreads();
-    const unsigned int nv = nv_s, want = nv / 2;
-    for (unsigned int i = threadIdx.x; i < nv; i += 1024) {
-        const double mi = med[i], si = sig[i];
-        unsigned int rm = 0, rs = 0;
-        for (unsigned int j = 0; j < nv; ++j) {
-            const double mj = med[j], sj = sig[j];
-            rm += (mj < mi || (mj == mi && j < i)) ? 1u : 0u;
-            rs += (sj < si || (sj == si && j < i)) ? 1u : 0u;
-        }
-        if (rm == want) res[0] = mi;
-        if (rs == want) res[1] = si;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double bg_median = res[0], bg_sigma = nv ? fmax(res[1], 1e-10) : 1.0;  // :81
-        fd->bg_median = bg_median;
-        fd->bg_sigma = bg_sigma;
-        fd->threshold = bg_median + sigma_threshold * bg_sigma;  // :103
-        out->bg_median = bg_median;
-        out->bg_sigma = bg_sigma;
-    }
 }
 
 // affine.rs:34-47 from the two order statistics: unchanged frame for < 100 finite samples or a flat range
@@ -2269,12 +2147,12 @@ static int tile_fail_buffer(ab_ctx *ctx, int which, size_t tiles, unsigned int *
 // over whatever it declined (a launch of a few hundred blocks that find an empty list and leave).  AB_TILE_RESIDENT=1: the
 // resident kernel alone (round 2 / 3's arrangement).  which: 0 = the context's stream, 1 = its auxiliary stream.
 static int launch_tile_kernels(ab_ctx *ctx, hipStream_t stream, int which, const float *img, int64_t rows, int64_t cols, int64_t ld, int step, int ntx,
-                               int ntiles, int nplanes, const ab_pixel_xf &xf, TileOut *out, const FrameDev *fd, const float *const *many_planes,
+                               int ntiles, int nplanes, const ab_pixel_xf &xf, TileOut *out, const float *const *many_planes,
                                const ab_pixel_xf *many_xf, const TileCand cand = TileCand()) {
     static const bool resident = ab_dev_env("AB_TILE_RESIDENT") != nullptr;
     if (resident) {
         hipLaunchKernelGGL(tile_background_bucket_kernel, dim3((unsigned)ntiles, (unsigned)nplanes), dim3(tb::kThreads), 0, stream, img, (int)rows, (int)cols,
-                           ld, step, ntx, xf, out, fd, many_planes, many_xf, (unsigned int *)nullptr, 0);
+                           ld, step, ntx, xf, out, many_planes, many_xf, (unsigned int *)nullptr, 0);
         return AB_OK;
     }
     unsigned int *fail = nullptr;
@@ -2283,7 +2161,7 @@ static int launch_tile_kernels(ab_ctx *ctx, hipStream_t stream, int which, const
     // needs LDS (the tile labelling, the votes, the selection) runs beside a tile launch; any padding leaves three and 43 KB free.
     static const unsigned int tile_pad = ab_dev_env("AB_TILE_PAD_KB") ? (unsigned int)std::min(std::max(atoi(ab_dev_env("AB_TILE_PAD_KB")), 0), 100) * 1024u : 0u;
     hipLaunchKernelGGL(tile_background_stream_kernel, dim3((unsigned)ntiles, (unsigned)nplanes), dim3(ts::kThreads), tile_pad, stream, img, (int)rows, (int)cols, ld,
-                       step, ntx, xf, out, fd, many_planes, many_xf, fail, cand);
+                       step, ntx, xf, out, many_planes, many_xf, fail, cand);
     // (the fallback's workgroups need 55 KB of LDS each before they can even look at the -- almost always empty -- list, and inside a batch
     // that room has to be waited for: 256 of them delayed the next tile launch by 16 - 80 us; 64 find it sooner and still work a long list
     // off side by side)
@@ -2291,8 +2169,8 @@ static int launch_tile_kernels(ab_ctx *ctx, hipStream_t stream, int which, const
 #define AB_TILE_FALLBACK_BLOCKS 64
 #endif
     const unsigned int blocks = (unsigned int)std::min<int64_t>((int64_t)ntiles * nplanes, AB_TILE_FALLBACK_BLOCKS);
-    hipLaunchKernelGGL(tile_background_bucket_kernel, dim3(blocks), dim3(tb::kThreads), 0, stream, img, (int)rows, (int)cols, ld, step, ntx, xf, out, fd,
-                       many_planes, many_xf, fail, ntiles);
+    hipLaunchKernelGGL(tile_background_bucket_kernel, dim3(blocks), dim3(tb::kThreads), 0, stream, img, (int)rows, (int)cols, ld, step, ntx, xf, out, many_planes,
+                       many_xf, fail, ntiles);
     return AB_OK;
 }
 
@@ -2314,7 +2192,7 @@ static int tile_stats_host(ab_ctx *ctx, const float *img, int64_t rows, int64_t 
         hipLaunchKernelGGL(tile_background_kernel, dim3(ntiles), dim3(absel::kBlock), 0, ctx->stream, img, (int)rows, (int)cols, ld, step,
                            ntx, xf, (TileOut *)pin);
     else
-        AB_TRY(launch_tile_kernels(ctx, ctx->stream, 0, img, rows, cols, ld, step, ntx, ntiles, 1, xf, (TileOut *)pin, nullptr, nullptr, nullptr));
+        AB_TRY(launch_tile_kernels(ctx, ctx->stream, 0, img, rows, cols, ld, step, ntx, ntiles, 1, xf, (TileOut *)pin, nullptr, nullptr));
     AB_HIP(ctx, hipGetLastError());
     AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     out->assign((const TileOut *)pin, (const TileOut *)pin + ntiles);
@@ -2347,7 +2225,6 @@ static void background_from_tiles(const TileOut *t, int ntiles, double *out_medi
 
 // The candidate lists of a pipeline's planes (TileCand; only for 256-px tiles -- frames of 2048 px and more on the short side -- whose
 // tiles the labelling pass can take one for one): n x ntiles x kCandCap entries + counts + cuts in a workspace of the pipeline's context
-static_assert(kCandCap == 2048, "ab_common.hpp: ab_bg_pipeline_cand assumes 2048 entries per tile");
 static int pipeline_cand_lists(ab_ctx *ctx, size_t n, int ntiles, int step, TileCand *out) {
     *out = TileCand();
     if (step != 256 || n == 0) return AB_OK;
@@ -2416,7 +2293,7 @@ int ab_bg_pipeline_begin(ab_ctx *ctx, const float *const *planes, size_t n, int6
         ctx->aux_pinned_bytes = need;
     }
     char *dv = nullptr;  // device copies of the plane pointers and transforms
-    AB_TRY(ab_workspace(ctx, AB_WS_DETECT_DEV, ptr_bytes + xf_bytes + 64, (void **)&dv));
+    AB_TRY(ab_workspace(ctx, AB_WS_PIPE_TABLES, ptr_bytes + xf_bytes + 64, (void **)&dv));
     const float **dplanes = (const float **)dv;
     ab_pixel_xf *dxf = (ab_pixel_xf *)(dv + ((ptr_bytes + 15) & ~(size_t)15));
     TileCand cand;
@@ -2433,7 +2310,7 @@ int ab_bg_pipeline_begin(ab_ctx *ctx, const float *const *planes, size_t n, int6
             const size_t begin = first ? (c == 0 ? 0 : first + (c - 1) * (size_t)chunk) : c * (size_t)chunk;
             const size_t cnt = (first && c == 0) ? first : std::min<size_t>((size_t)chunk, n - begin);
             AB_TRY(launch_tile_kernels(ctx, ctx->aux_stream, 1, nullptr, rows, cols, cols, step, ntx, ntiles, (int)cnt, ab_pixel_xf(),
-                                       (TileOut *)ctx->aux_pinned + begin * (size_t)ntiles, nullptr, (const float *const *)(dplanes + begin),
+                                       (TileOut *)ctx->aux_pinned + begin * (size_t)ntiles, (const float *const *)(dplanes + begin),
                                        (const ab_pixel_xf *)(dxf + begin), cand_at(cand, begin, ntiles)));
             AB_HIP(ctx, hipEventRecord(ctx->aux_events[c], ctx->aux_stream));
         }
@@ -2495,7 +2372,7 @@ struct FedPlan {  // everything a chunk's launches need, by value (the feeder ou
         AB_HIP(ctx, hipEventRecord(ctx->pct_events[c], ctx->pct_stream));
         AB_HIP(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->pct_events[c], 0));
         AB_TRY(launch_tile_kernels(ctx, ctx->aux_stream, 1, nullptr, rows, cols, cols, step, ntx, ntiles, (int)cnt, ab_pixel_xf(),
-                                   (TileOut *)ctx->aux_pinned + first * (size_t)ntiles, nullptr, (const float *const *)(dplanes + first),
+                                   (TileOut *)ctx->aux_pinned + first * (size_t)ntiles, (const float *const *)(dplanes + first),
                                    (const ab_pixel_xf *)(dxf + first), cand_at(cand, first, ntiles)));
         AB_HIP(ctx, hipEventRecord(ctx->aux_events[c], ctx->aux_stream));
         AB_HIP(ctx, hipGetLastError());
@@ -2799,139 +2676,21 @@ static void finish_stars(const CompRec *recs_begin, unsigned int ncomp, double b
     }
 }
 
-// detect_stars (star_detection.rs:86-258) on a device plane; stars sorted by flux, deduplicated
-int ab_detect_stars_device(ab_ctx *ctx, const float *img, int64_t rows, int64_t cols, int64_t ld, double sigma_threshold,
-                           std::vector<ab_detected_star> *stars, double *bg_median_out, double *bg_sigma_out, ab_pixel_xf xf, size_t max_keep,
-                           bool normalize_first, const double *bg_known) {
-    stars->clear();
-    *bg_median_out = 0.0;
-    *bg_sigma_out = 1.0;
-    if (rows < 3 || cols < 3) return AB_OK;  // :89-98
-    AB_CHECK(ctx, rows * cols < (int64_t(1) << 31), "detect_stars: image too large for 32-bit labels");
-    AB_HIP(ctx, hipSetDevice(ctx->device));
-    ab_trace trace("detect_stars");
-    const int64_t m = std::min(rows, cols);
-    const int64_t tile_size = std::min<int64_t>(std::max<int64_t>(m / 8, 32), 256);  // :100
-    const int64_t P = rows * cols;
-    // The chained form (normalize_first: the registration path): percentiles -> tiles -> background -> threshold -> labels are
-    // enqueued back to back, every parameter travelling through FrameDev; the host joins at the component count.
-    const int step = (int)std::max<int64_t>(tile_size, 16);
-    const int nty = (int)((rows + step - 1) / step), ntx = (int)((cols + step - 1) / step), ntiles = nty * ntx;
-    static const bool legacy_tiles = ab_dev_env("AB_TILE_LEGACY") != nullptr;
-    // OFF by default (AB_DETECT_CHAIN=1 turns it on): measured on the bench, same box, three runs each -- registration stage 18.4 /
-    // 18.6 / 18.7 ms with the two host joins against 21.0 / 21.9 / 22.2 ms chained, although one frame alone gets faster (0.39 ->
-    // 0.37 ms).  Sixteen streams share four in-order hardware queues; a stream that enqueues nine packets in one go holds its
-    // queue until they have all run, and the three streams behind it wait -- the host joins were what interleaved them.
-    static const bool want_chain = ab_dev_env("AB_DETECT_CHAIN") != nullptr;
-    const bool chained = normalize_first && !bg_known && ld == cols && ntiles <= kBgTiles && !legacy_tiles && want_chain;
-    double bg_median = 0.0, bg_sigma = 1.0, threshold = 0.0;
-    FrameDev *fd = nullptr;
-    struct Joined {  // what the host reads at the first synchronisation of the chained form (pinned)
-        PercentileOut po;
-        BgOut bg;
-        unsigned int ncomp;
-    };
-    void *pin = nullptr;
-    if (chained) {
-        char *dv = nullptr;
-        AB_TRY(ab_workspace(ctx, AB_WS_DETECT_DEV, sizeof(FrameDev) + (size_t)ntiles * sizeof(TileOut), (void **)&dv));
-        fd = (FrameDev *)dv;
-        TileOut *tiles = (TileOut *)(dv + sizeof(FrameDev));
-        AB_TRY(ab_pinned(ctx, sizeof(Joined), &pin));
-        Joined *jn = (Joined *)pin;
-        const int64_t sstep = std::max<int64_t>(P / 100000, 1), ns = (P + sstep - 1) / sstep;
-        float *sub = nullptr;
-        AB_TRY(ab_workspace(ctx, AB_WS_SUBSAMPLE, (size_t)ns * sizeof(float), (void **)&sub));
-        hipLaunchKernelGGL(subsample_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, ctx->stream, img, P, sstep, sub, ns);
-        if (ns <= (int64_t)kPctPer * 1024)
-            hipLaunchKernelGGL(percentiles_reg_kernel, dim3(1), dim3(1024), 0, ctx->stream, sub, (unsigned int)ns, &jn->po, fd);
-        else
-            hipLaunchKernelGGL(percentiles_mem_kernel, dim3(1), dim3(1024), 0, ctx->stream, sub, (unsigned int)ns, &jn->po, fd);
-        AB_TRY(launch_tile_kernels(ctx, ctx->stream, 0, img, rows, cols, ld, step, ntx, ntiles, 1, ab_pixel_xf(), tiles, fd, nullptr, nullptr));
-        hipLaunchKernelGGL(bg_threshold_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const TileOut *)tiles, ntiles, sigma_threshold, fd, &jn->bg);
-        AB_HIP(ctx, hipGetLastError());
-    } else if (bg_known) {  // the caller has estimate_background's result for this plane and transform already
-        bg_median = bg_known[0];
-        bg_sigma = bg_known[1];
-        threshold = bg_median + sigma_threshold * bg_sigma;  // :103
-    } else {
-        if (normalize_first) AB_TRY(ab_normalize_params_device(ctx, img, P, &xf));
-        AB_TRY(ab_estimate_background_device(ctx, img, rows, cols, ld, tile_size, &bg_median, &bg_sigma, xf));
-        trace.mark("background");
-        threshold = bg_median + sigma_threshold * bg_sigma;  // :103
-    }
-
-    const unsigned int root_cap = (unsigned int)(P / 4 + 1);  // 8-connected components cannot be denser
-    int *parent = nullptr, *cid = nullptr, *roots = nullptr;
-    AB_TRY(ab_workspace(ctx, AB_WS_DETECT_PARENT, (size_t)P * sizeof(int), (void **)&parent));
-    AB_TRY(ab_workspace(ctx, AB_WS_DETECT_CID, (size_t)P * sizeof(int), (void **)&cid));
-    AB_TRY(ab_workspace(ctx, AB_WS_DETECT_ROOTS, ((size_t)root_cap + 4) * sizeof(int), (void **)&roots));
-    unsigned int *nroots = (unsigned int *)(roots + root_cap), *nlab = nroots + 1;
-    int *plist = nullptr;
-    AB_TRY(ab_workspace(ctx, AB_WS_DETECT_LIST, (size_t)P * sizeof(int), (void **)&plist));
-    unsigned int *mask = nullptr;
-    AB_TRY(ab_workspace(ctx, AB_WS_DETECT_MASK, ((size_t)P / 32 + 2) * sizeof(unsigned int), (void **)&mask));
-    const int gl = (ctx->cu_count > 0 ? ctx->cu_count : 256) * 8;  // list kernels: grid-stride over *nlab entries
-    AB_HIP(ctx, hipMemsetAsync(nroots, 0, 2 * sizeof(unsigned int), ctx->stream));
-    hipLaunchKernelGGL(label_init_kernel, dim3((unsigned)((P + kInitSub * kInitRounds - 1) / (kInitSub * kInitRounds))), dim3(kInitBlock), 0, ctx->stream, img, (int)rows,
-                       (int)cols, ld, threshold, xf, parent, mask, plist, nlab,
-                       (int)(ld == cols && (P & 3) == 0 && ((uintptr_t)img & 15) == 0), (const FrameDev *)fd);
-    hipLaunchKernelGGL(label_merge_kernel, dim3(gl), dim3(256), 0, ctx->stream, (int)rows, (int)cols, parent, mask, plist, nlab);
-    hipLaunchKernelGGL(roots_kernel, dim3(gl / 4), dim3(kRootsBlock), 0, ctx->stream, parent, plist, nlab, roots, cid, nroots, root_cap);
-    AB_HIP(ctx, hipGetLastError());
-    unsigned int ncomp = 0;
-    if (chained) {
-        Joined *jn = (Joined *)pin;
-        AB_HIP(ctx, hipMemcpyAsync(&jn->ncomp, nroots, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
-        AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        ncomp = jn->ncomp;
-        bg_median = jn->bg.bg_median;
-        bg_sigma = jn->bg.bg_sigma;
-    } else {
-        AB_TRY(ab_pinned(ctx, 64, &pin));
-        AB_HIP(ctx, hipMemcpyAsync(pin, nroots, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
-        AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        ncomp = *(const unsigned int *)pin;
-    }
-    *bg_median_out = bg_median;
-    *bg_sigma_out = bg_sigma;
-    trace.mark(chained ? "percentiles+background+label+roots" : "label+roots");
-    AB_CHECK(ctx, ncomp <= root_cap, "detect_stars: %u components exceed the table capacity", ncomp);
-    if (ncomp == 0) return AB_OK;
-    void *cbuf = nullptr;
-    AB_TRY(ab_workspace(ctx, AB_WS_DETECT_COMPS, (size_t)ncomp * (sizeof(CompStat) + sizeof(CompRec)), &cbuf));
-    CompRec *drec = (CompRec *)cbuf;  // 80-byte records from one lane per wave: written to HBM and copied in one piece (straight
-    CompStat *dstat = (CompStat *)(drec + ncomp);  // PCIe stores made the kernel 12 us slower than the copy costs)
-    AB_TRY(ab_pinned(ctx, (size_t)ncomp * sizeof(CompRec), &pin));
-    hipLaunchKernelGGL(comp_init_kernel, dim3((ncomp + 255) / 256), dim3(256), 0, ctx->stream, dstat, ncomp);
-    hipLaunchKernelGGL(comp_stats_kernel, dim3(gl), dim3(256), 0, ctx->stream, (int)rows, (int)cols, parent, cid, dstat, plist, nlab);
-    hipLaunchKernelGGL(comp_moments_kernel, dim3((ncomp + 4 * kMomPerWave - 1) / (4 * kMomPerWave)), dim3(256), 0, ctx->stream, img, (int)cols, ld, parent, mask, roots, dstat, ncomp,
-                       bg_median, xf, drec, (const FrameDev *)fd);
-    AB_HIP(ctx, hipGetLastError());
-    AB_HIP(ctx, hipMemcpyAsync(pin, drec, (size_t)ncomp * sizeof(CompRec), hipMemcpyDeviceToHost, ctx->stream));
-    AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const CompRec *recs_begin = (const CompRec *)pin;
-
-    trace.mark("moments+D2H");
-    if (trace.on) fprintf(stderr, " (%u components)", ncomp);
-    finish_stars(recs_begin, ncomp, bg_sigma, max_keep, stars);
-    trace.mark("sort+dedup");
-    return AB_OK;
-}
-
-// detect_stars (star_detection.rs:86-258) of G <= kGroupMax frames of ONE size in lockstep: the registration batch's form.  The
-// frames' background (estimate_background's median and sigma under their load transform xf[f]) comes from the tile pipeline; every
-// step of the chain is ONE launch for all of them (blockIdx.y = frame), the counters and the component records come back in one
-// copy each.  Results equal G calls of ab_detect_stars_device.
-int ab_detect_stars_group_device(ab_ctx *ctx, const float *const *imgs, int G, int64_t rows, int64_t cols, double sigma_threshold, const ab_pixel_xf *xf,
-                                 const double (*bg)[2], size_t max_keep, std::vector<ab_detected_star> *stars /* [G] */, const ab_frame_cand *cand) {
+// detect_stars (star_detection.rs:86-258) of G <= kGroupMax frames of ONE size in lockstep.  The frames' background
+// (estimate_background's median and sigma under their load transform xf[f]) is the caller's; every step of the chain is ONE launch
+// for all of them (blockIdx.y = frame), the counters and the component records come back in one copy each.
+// full: every component's record comes back -- no selection on the device, the host joins after the root numbering.  That is what a
+// single frame whose caller wants every star takes (ab_detect_stars_device: a group of one), and what a frame whose selection fell
+// short is redone with.
+static int detect_group(ab_ctx *ctx, const float *const *imgs, int G, int64_t rows, int64_t cols, double sigma_threshold, const ab_pixel_xf *xf,
+                        const double (*bg)[2], size_t max_keep, std::vector<ab_detected_star> *stars /* [G] */, const ab_frame_cand *cand, bool full) {
     for (int f = 0; f < G; ++f) stars[f].clear();
     if (rows < 3 || cols < 3 || G <= 0) return AB_OK;  // :89-98
     AB_CHECK(ctx, G <= kGroupMax, "detect_stars: groups of at most %d frames", kGroupMax);
     AB_CHECK(ctx, rows * cols < (int64_t(1) << 31), "detect_stars: image too large for 32-bit labels");
     AB_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t P = rows * cols;
-    const unsigned int root_cap = (unsigned int)(P / 4 + 1);
+    const unsigned int root_cap = (unsigned int)(P / 4 + 1);  // 8-connected components cannot be denser
     int *parent = nullptr, *cid = nullptr, *roots = nullptr, *plist = nullptr;
     unsigned int *mask = nullptr;
     const int mask_pitch = (int)((cols + 31) / 32 * 32);  // (the tiled labelling's; the two-pass form indexes the mask by pixel number)
@@ -2942,11 +2701,13 @@ int ab_detect_stars_group_device(ab_ctx *ctx, const float *const *imgs, int G, i
     // tile-local labelling (label_tile_many_kernel): contiguous planes (always, here) of any width -- the mask's rows are padded to
     // whole words, a row's ragged last quad is loaded float by float; AB_LABEL_LEGACY=1 keeps the two-pass form (the GPU tests run both)
     const bool tiled = !ctx->label_legacy;  // (any width, any dword alignment: round 5)
+    // The matcher's 120 (max_keep <= kSelKeep / 4): the brightest kSelKeep candidates are chosen on the device and only they are
+    // walked and sent (comp_select_many_kernel).  A caller that wants every star, `full`, or AB_DETECT_FULL_RECORDS=1 takes all records.
+    const bool select = !full && !ctx->detect_full_records && 4 * max_keep <= (size_t)kSelKeep;
     // Round 6: with the tile pass's candidate lists (a registration batch's frames: ab_bg_pipeline_cand) the labelling tile IS the 256 x 256
     // background tile and the frame is not read at all (label_bgtile_many_kernel); a frame without lists keeps the 32 x 128 tiles.  The
     // records form only (the chained detection with the device-side selection: decided below with the same conditions).
-    const bool bg_tiles = tiled && cand && cand[0].ent && !ctx->label_pixelwise && !ctx->detect_no_recs && !ctx->detect_full_records && !ctx->detect_midjoin &&
-                          4 * max_keep <= (size_t)kSelKeep;
+    const bool bg_tiles = tiled && select && cand && cand[0].ent && !ctx->label_pixelwise && !ctx->detect_no_recs && !ctx->detect_midjoin;
     const int tile_h = bg_tiles ? kBgRows : kTileH, tile_w = bg_tiles ? kBgT : kTileW, tile_slots = bg_tiles ? kBgSlots : kTileSlots;
     // (background tiles: one workgroup per sub-tile of kBgRows rows, kBgSub of them per 256 x 256 tile -- the last tile row's may lie below the frame)
     const int64_t tiles_x = (cols + tile_w - 1) / tile_w, tiles_y = bg_tiles ? ((rows + kBgT - 1) / kBgT) * kBgSub : (rows + tile_h - 1) / tile_h, ntile = tiles_x * tiles_y;
@@ -2980,9 +2741,6 @@ int ab_detect_stars_group_device(ab_ctx *ctx, const float *const *imgs, int G, i
     const int cus = ctx->cu_count > 0 ? ctx->cu_count : 256;
     // list kernels: grid-stride over the frame's labelled pixels (a fraction of a percent of the frame); tiled: a multiple of kRegions
     const int gl = tiled ? std::max(kRegions, (cus * 2 / kRegions) * kRegions) : cus * 2;
-    // The matcher's 120 (max_keep <= kSelKeep / 4): the brightest kSelKeep candidates are chosen on the device and only they are
-    // walked and sent (comp_select_many_kernel).  A caller that wants every star, or AB_DETECT_FULL_RECORDS=1, takes all records.
-    const bool select = !ctx->detect_full_records && 4 * max_keep <= (size_t)kSelKeep;
     // With the selection the component kernels' grids no longer depend on the component count, so the whole detection is ONE chain
     // with one host join at its end (labels -> roots (which also initialise the component table) -> statistics -> selection ->
     // moments); the table holds comp_cap components per frame, a frame with more is redone in full.  AB_DETECT_MIDJOIN=1 keeps the
@@ -2995,14 +2753,14 @@ int ab_detect_stars_group_device(ab_ctx *ctx, const float *const *imgs, int G, i
     AB_CHECK(ctx, !bg_tiles || recs, "detect_stars: the background-tile labelling needs the records form (%zu records for %u roots)", rec_cap, root_cap);
     const unsigned int comp_cap = recs ? (unsigned int)rec_cap : (unsigned int)std::min<int64_t>(root_cap, (int64_t)1 << 18);
     void *pin = nullptr;
-    unsigned int *selout = nullptr;
+    unsigned int *selout = nullptr;  // PINNED, 8 words per frame: selected, candidates, components, cut key, dense tiles
     if (chained) {
         void *cbuf = nullptr;
         AB_TRY(ab_workspace(ctx, AB_WS_DETECT_COMPS, (size_t)G * comp_cap * sizeof(CompStat) + (size_t)G * kSelCap * sizeof(unsigned int), &cbuf));
         CompStat *dstat = (CompStat *)cbuf;
         unsigned int *dsel = (unsigned int *)(dstat + (size_t)G * comp_cap);
         AB_TRY(ab_pinned(ctx, (size_t)G * kSelCap * sizeof(CompRec) + (size_t)G * 8 * sizeof(unsigned int), &pin));
-        selout = (unsigned int *)((CompRec *)pin + (size_t)G * kSelCap);  // 8 words per frame: selected, candidates, components, cut key, dense tiles
+        selout = (unsigned int *)((CompRec *)pin + (size_t)G * kSelCap);
         for (int f = 0; f < G; ++f) {
             g.rec[f] = (CompRec *)pin + (size_t)f * kSelCap;
             g.st[f] = dstat + (size_t)f * comp_cap;
@@ -3053,105 +2811,84 @@ int ab_detect_stars_group_device(ab_ctx *ctx, const float *const *imgs, int G, i
         hipLaunchKernelGGL(roots_many_kernel, dim3(gl, G), dim3(kRootsBlock), 0, ctx->stream, g, chained ? comp_cap : root_cap);
     }
     AB_HIP(ctx, hipGetLastError());
+    const dim3 sel_grid((kSelCap + 4 * kMomPerWave - 1) / (4 * kMomPerWave), G);  // comp_moments over a selection
     if (chained) {
         if (!recs) hipLaunchKernelGGL(comp_stats_many_kernel, dim3(gl, G), dim3(256), 0, ctx->stream, g, (int)rows, (int)cols, cols);
         hipLaunchKernelGGL(comp_select_many_kernel, dim3(G), dim3(kSelThreads), 0, ctx->stream, g);
-        hipLaunchKernelGGL(comp_moments_many_kernel, dim3((kSelCap + 4 * kMomPerWave - 1) / (4 * kMomPerWave), G), dim3(256), 0, ctx->stream, g, (int)cols, cols);
-        AB_HIP(ctx, hipGetLastError());
-        AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        bool redo[kGroupMax] = {};
-        // (what the trace prints is copied out BEFORE any frame is redone: the full path may regrow -- and free -- the pinned buffer
-        // selout lives in: ADVICE r5)
-        unsigned int sel_m[kGroupMax] = {}, sel_ncand[kGroupMax] = {}, sel_ncomp[kGroupMax] = {};
-        size_t sel_stars[kGroupMax] = {};
-        for (int f = 0; f < G; ++f) {
-            const unsigned int m = selout[8 * f], ncand = selout[8 * f + 1], ncomp = selout[8 * f + 2], cut_key = selout[8 * f + 3];
-            if (bg_tiles) ab_count_fallback(ctx, AB_FB_LABEL_TILES_DENSE, selout[8 * f + 4]);
-            sel_m[f] = m;
-            sel_ncand[f] = ncand;
-            sel_ncomp[f] = ncomp;
-            AB_CHECK(ctx, m <= kSelCap, "detect_stars: the selection of frame %d holds %u components", f, m);
-            AB_CHECK(ctx, ncomp <= root_cap, "detect_stars: %u components exceed the table capacity", ncomp);
-            if (ncomp > comp_cap) {  // more components than the chained table holds (or a tile with more components than record slots)
-                redo[f] = true;
-                ab_count_fallback(ctx, recs && ncomp == comp_cap + 1u ? AB_FB_TILE_SLOTS : AB_FB_COMPONENT_TABLE);
-                continue;
-            }
-            finish_stars(g.rec[f], m, bg[f][1], max_keep, &stars[f]);
-            sel_stars[f] = stars[f].size();
-            redo[f] = stars[f].size() < max_keep && ncand > m;  // (see below)
-            if (redo[f]) ab_count_fallback(ctx, AB_FB_SELECTION_SHORT);
-            if (!redo[f] && selection_cut_too_close(stars[f], max_keep, m, ncand, cut_key)) {
-                redo[f] = true;
-                ab_count_fallback(ctx, AB_FB_SELECTION_CUT);
-            }
-        }
-        for (int f = 0; f < G; ++f) {
-            if (!redo[f]) continue;
-            static const bool trace = ab_env("AB_TRACE") != nullptr;
-            if (trace)
-                fprintf(stderr, "[ab_trace] detect_stars: frame %d of the group redone in full (%u components, %u candidates, %u selected, %zu stars of them)\n", f,
-                        sel_ncomp[f], sel_ncand[f], sel_m[f], sel_stars[f]);
-            double m0 = 0.0, s0 = 0.0;
-            AB_TRY(ab_detect_stars_device(ctx, imgs[f], rows, cols, cols, sigma_threshold, &stars[f], &m0, &s0, xf[f], max_keep, false, bg[f]));
-            ab_count_fallback(ctx, AB_FB_FRAMES_REDONE);
-        }
-        return AB_OK;
-    }
-    AB_TRY(ab_pinned(ctx, (size_t)G * 4 * sizeof(unsigned int), &pin));
-    AB_HIP(ctx, hipMemcpyAsync(pin, counters, (size_t)G * 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
-    AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    size_t total = 0, off[kGroupMax + 1];
-    unsigned int max_nc = 0;
-    for (int f = 0; f < G; ++f) {
-        g.ncomp[f] = ((const unsigned int *)pin)[4 * f];
-        AB_CHECK(ctx, g.ncomp[f] <= root_cap, "detect_stars: %u components exceed the table capacity", g.ncomp[f]);
-        off[f] = total;
-        total += g.ncomp[f];
-        max_nc = std::max(max_nc, g.ncomp[f]);
-    }
-    off[G] = total;
-    if (total == 0) return AB_OK;
-    void *cbuf = nullptr;
-    AB_TRY(ab_workspace(ctx, AB_WS_DETECT_COMPS, total * sizeof(CompStat) + (size_t)G * kSelCap * sizeof(unsigned int), &cbuf));
-    CompStat *dstat = (CompStat *)cbuf;
-    unsigned int *dsel = (unsigned int *)(dstat + total);
-    // the component records (72 B each, written once, by one lane, never read on the device) go STRAIGHT into pinned host memory
-    const size_t rec_count = select ? (size_t)G * kSelCap : total;
-    AB_TRY(ab_pinned(ctx, rec_count * sizeof(CompRec) + (size_t)G * 4 * sizeof(unsigned int), &pin));
-    selout = (unsigned int *)((CompRec *)pin + rec_count);
-    for (int f = 0; f < G; ++f) {
-        g.rec[f] = (CompRec *)pin + (select ? (size_t)f * kSelCap : off[f]);
-        g.st[f] = dstat + off[f];
-        g.sel[f] = select ? dsel + (size_t)f * kSelCap : nullptr;
-        g.selout[f] = selout + 4 * f;
-        selout[4 * f] = selout[4 * f + 1] = selout[4 * f + 3] = 0;
-    }
-    hipLaunchKernelGGL(comp_init_many_kernel, dim3((max_nc + 255) / 256, G), dim3(256), 0, ctx->stream, g);
-    hipLaunchKernelGGL(comp_stats_many_kernel, dim3(gl, G), dim3(256), 0, ctx->stream, g, (int)rows, (int)cols, cols);
-#ifdef AB_DEV_ABLATION
-    if (ab_dev_env("AB_ABLATE_MOMENTS")) {
-        const int v = atoi(ab_dev_env("AB_ABLATE_MOMENTS"));
-        AB_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_mom_ablate), &v, sizeof v));
-    }
-#endif
-    if (select) {
-        hipLaunchKernelGGL(comp_select_many_kernel, dim3(G), dim3(kSelThreads), 0, ctx->stream, g);
-        hipLaunchKernelGGL(comp_moments_many_kernel, dim3((kSelCap + 4 * kMomPerWave - 1) / (4 * kMomPerWave), G), dim3(256), 0, ctx->stream, g, (int)cols, cols);
+        hipLaunchKernelGGL(comp_moments_many_kernel, sel_grid, dim3(256), 0, ctx->stream, g, (int)cols, cols);
     } else {
-        hipLaunchKernelGGL(comp_moments_many_kernel, dim3((max_nc + 4 * kMomPerWave - 1) / (4 * kMomPerWave), G), dim3(256), 0, ctx->stream, g, (int)cols, cols);
+        // the join after the root numbering: the host sizes the component table and the grids
+        AB_TRY(ab_pinned(ctx, (size_t)G * 4 * sizeof(unsigned int), &pin));
+        AB_HIP(ctx, hipMemcpyAsync(pin, counters, (size_t)G * 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+        AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        size_t total = 0, off[kGroupMax + 1];
+        unsigned int max_nc = 0;
+        for (int f = 0; f < G; ++f) {
+            g.ncomp[f] = ((const unsigned int *)pin)[4 * f];
+            AB_CHECK(ctx, g.ncomp[f] <= root_cap, "detect_stars: %u components exceed the table capacity", g.ncomp[f]);
+            off[f] = total;
+            total += g.ncomp[f];
+            max_nc = std::max(max_nc, g.ncomp[f]);
+        }
+        off[G] = total;
+        if (total == 0) return AB_OK;
+        void *cbuf = nullptr;
+        AB_TRY(ab_workspace(ctx, AB_WS_DETECT_COMPS, total * sizeof(CompStat) + (size_t)G * kSelCap * sizeof(unsigned int), &cbuf));
+        CompStat *dstat = (CompStat *)cbuf;
+        unsigned int *dsel = (unsigned int *)(dstat + total);
+        // the component records (72 B each, written once, by one lane, never read on the device) go STRAIGHT into pinned host memory
+        const size_t rec_count = select ? (size_t)G * kSelCap : total;
+        AB_TRY(ab_pinned(ctx, rec_count * sizeof(CompRec) + (size_t)G * 8 * sizeof(unsigned int), &pin));
+        selout = (unsigned int *)((CompRec *)pin + rec_count);
+        for (int f = 0; f < G; ++f) {
+            g.rec[f] = (CompRec *)pin + (select ? (size_t)f * kSelCap : off[f]);
+            g.st[f] = dstat + off[f];
+            g.sel[f] = select ? dsel + (size_t)f * kSelCap : nullptr;
+            g.selout[f] = selout + 8 * f;
+            for (int k = 0; k < 8; ++k) selout[8 * f + k] = 0;
+            selout[8 * f + 2] = g.ncomp[f];  // (the chained form's selection kernel reports it; here the host knows it already)
+        }
+        hipLaunchKernelGGL(comp_init_many_kernel, dim3((max_nc + 255) / 256, G), dim3(256), 0, ctx->stream, g);
+        hipLaunchKernelGGL(comp_stats_many_kernel, dim3(gl, G), dim3(256), 0, ctx->stream, g, (int)rows, (int)cols, cols);
+#ifdef AB_DEV_ABLATION
+        if (ab_dev_env("AB_ABLATE_MOMENTS")) {
+            const int v = atoi(ab_dev_env("AB_ABLATE_MOMENTS"));
+            AB_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_mom_ablate), &v, sizeof v));
+        }
+#endif
+        if (select) {
+            hipLaunchKernelGGL(comp_select_many_kernel, dim3(G), dim3(kSelThreads), 0, ctx->stream, g);
+            hipLaunchKernelGGL(comp_moments_many_kernel, sel_grid, dim3(256), 0, ctx->stream, g, (int)cols, cols);
+        } else {
+            hipLaunchKernelGGL(comp_moments_many_kernel, dim3((max_nc + 4 * kMomPerWave - 1) / (4 * kMomPerWave), G), dim3(256), 0, ctx->stream, g, (int)cols, cols);
+        }
     }
     AB_HIP(ctx, hipGetLastError());
     AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // Every frame's records are read (and what the trace prints is copied out) BEFORE any frame is redone: the full form re-carves
+    // the workspaces and may regrow -- and free -- the pinned buffer the records and selout live in
     bool redo[kGroupMax] = {};
+    unsigned int sel_m[kGroupMax] = {}, sel_ncand[kGroupMax] = {}, sel_ncomp[kGroupMax] = {};
+    size_t sel_stars[kGroupMax] = {};
     for (int f = 0; f < G; ++f) {
         if (!select) {
-            finish_stars((const CompRec *)pin + off[f], g.ncomp[f], bg[f][1], max_keep, &stars[f]);
+            finish_stars(g.rec[f], g.ncomp[f], bg[f][1], max_keep, &stars[f]);
             continue;
         }
-        const unsigned int m = selout[4 * f], ncand = selout[4 * f + 1], cut_key = selout[4 * f + 3];
+        const unsigned int m = selout[8 * f], ncand = selout[8 * f + 1], ncomp = selout[8 * f + 2], cut_key = selout[8 * f + 3];
+        if (bg_tiles) ab_count_fallback(ctx, AB_FB_LABEL_TILES_DENSE, selout[8 * f + 4]);
+        sel_m[f] = m;
+        sel_ncand[f] = ncand;
+        sel_ncomp[f] = ncomp;
         AB_CHECK(ctx, m <= kSelCap, "detect_stars: the selection of frame %d holds %u components", f, m);
+        AB_CHECK(ctx, ncomp <= root_cap, "detect_stars: %u components exceed the table capacity", ncomp);
+        if (chained && ncomp > comp_cap) {  // more components than the chained table holds (or a tile with more components than record slots)
+            redo[f] = true;
+            ab_count_fallback(ctx, recs && ncomp == comp_cap + 1u ? AB_FB_TILE_SLOTS : AB_FB_COMPONENT_TABLE);
+            continue;
+        }
         finish_stars(g.rec[f], m, bg[f][1], max_keep, &stars[f]);
+        sel_stars[f] = stars[f].size();
         // the brightest kSelKeep did not yield max_keep survivors and fainter candidates exist (a crowded field whose dedup eats
         // hundreds, or a crowd of equal fluxes at the cut): the whole list decides
         redo[f] = stars[f].size() < max_keep && ncand > m;
@@ -3161,39 +2898,54 @@ int ab_detect_stars_group_device(ab_ctx *ctx, const float *const *imgs, int G, i
             ab_count_fallback(ctx, AB_FB_SELECTION_CUT);
         }
     }
-    for (int f = 0; f < G; ++f) {  // (after every frame's records have been read: the full path re-carves the workspaces and the pinned buffer)
+    for (int f = 0; f < G; ++f) {
         if (!redo[f]) continue;
-        double m0 = 0.0, s0 = 0.0;
-        AB_TRY(ab_detect_stars_device(ctx, imgs[f], rows, cols, cols, sigma_threshold, &stars[f], &m0, &s0, xf[f], max_keep, false, bg[f]));
+        static const bool trace = ab_env("AB_TRACE") != nullptr;
+        if (trace)
+            fprintf(stderr, "[ab_trace] detect_stars: frame %d of the group redone in full (%u components, %u candidates, %u selected, %zu stars of them)\n", f,
+                    sel_ncomp[f], sel_ncand[f], sel_m[f], sel_stars[f]);
+        // (`full` is what keeps max_keep = 120 from choosing the selection again)
+        AB_TRY(detect_group(ctx, &imgs[f], 1, rows, cols, sigma_threshold, &xf[f], &bg[f], max_keep, &stars[f], nullptr, /*full=*/true));
         ab_count_fallback(ctx, AB_FB_FRAMES_REDONE);
     }
     return AB_OK;
 }
 
-int ab_normalize_params_device(ab_ctx *ctx, const float *img, int64_t len, ab_pixel_xf *xf) {
-    AB_HIP(ctx, hipSetDevice(ctx->device));
-    *xf = ab_pixel_xf();
-    if (len == 0) return AB_OK;
-    const int64_t step = std::max<int64_t>(len / 100000, 1);
-    const int64_t ns = (len + step - 1) / step;
-    void *pin = nullptr;  // the kernel writes its 16 bytes straight into pinned host memory
-    AB_TRY(ab_pinned(ctx, sizeof(PercentileOut), &pin));
-    ab_trace trace("normalize_params");
-    float *sub = nullptr;
-    AB_TRY(ab_workspace(ctx, AB_WS_SUBSAMPLE, (size_t)ns * sizeof(float), (void **)&sub));
-    hipLaunchKernelGGL(subsample_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, ctx->stream, img, len, step, sub, ns);
-    if (ns <= (int64_t)kPctPer * 1024)
-        hipLaunchKernelGGL(percentiles_reg_kernel, dim3(1), dim3(1024), 0, ctx->stream, sub, (unsigned int)ns, (PercentileOut *)pin, (FrameDev *)nullptr);
-    else
-        hipLaunchKernelGGL(percentiles_mem_kernel, dim3(1), dim3(1024), 0, ctx->stream, sub, (unsigned int)ns, (PercentileOut *)pin, (FrameDev *)nullptr);
-    AB_HIP(ctx, hipGetLastError());
-    AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    trace.mark("subsample+percentiles+sync");
-    *xf = xf_from_percentiles(*(const PercentileOut *)pin);
+int ab_detect_stars_group_device(ab_ctx *ctx, const float *const *imgs, int G, int64_t rows, int64_t cols, double sigma_threshold, const ab_pixel_xf *xf,
+                                 const double (*bg)[2], size_t max_keep, std::vector<ab_detected_star> *stars /* [G] */, const ab_frame_cand *cand) {
+    return detect_group(ctx, imgs, G, rows, cols, sigma_threshold, xf, bg, max_keep, stars, cand, /*full=*/false);
+}
+
+// detect_stars (star_detection.rs:86-258) on a device plane; stars sorted by flux, deduplicated: a group of one, every record
+int ab_detect_stars_device(ab_ctx *ctx, const float *img, int64_t rows, int64_t cols, double sigma_threshold, std::vector<ab_detected_star> *stars,
+                           double *bg_median_out, double *bg_sigma_out, ab_pixel_xf xf, size_t max_keep, bool normalize_first, const double *bg_known) {
+    stars->clear();
+    *bg_median_out = 0.0;
+    *bg_sigma_out = 1.0;
+    if (rows < 3 || cols < 3) return AB_OK;  // :89-98
+    ab_trace trace("detect_stars");
+    double bg[1][2];
+    if (bg_known) {  // the caller has estimate_background's result for this plane and transform already
+        bg[0][0] = bg_known[0];
+        bg[0][1] = bg_known[1];
+    } else {
+        if (normalize_first) AB_TRY(ab_normalize_params_device(ctx, img, rows * cols, &xf));
+        const int64_t tile_size = std::min<int64_t>(std::max<int64_t>(std::min(rows, cols) / 8, 32), 256);  // :100
+        AB_TRY(ab_estimate_background_device(ctx, img, rows, cols, cols, tile_size, &bg[0][0], &bg[0][1], xf));
+        trace.mark("background");
+    }
+    AB_TRY(detect_group(ctx, &img, 1, rows, cols, sigma_threshold, &xf, bg, max_keep, stars, nullptr, /*full=*/true));
+    trace.mark("label+moments+sort+dedup");
+    *bg_median_out = bg[0][0];
+    *bg_sigma_out = bg[0][1];
     return AB_OK;
 }
 
-// the same for n planes of `len` pixels each (device pointers), two launches and one synchronisation for all of them
+int ab_normalize_params_device(ab_ctx *ctx, const float *img, int64_t len, ab_pixel_xf *xf) {
+    return ab_normalize_params_many_device(ctx, &img, 1, len, xf);
+}
+
+// normalize_for_detection's parameters of n planes of `len` pixels each (device pointers), two launches and one synchronisation for all of them
 int ab_normalize_params_many_device(ab_ctx *ctx, const float *const *planes, size_t n, int64_t len, ab_pixel_xf *xf) {
     AB_HIP(ctx, hipSetDevice(ctx->device));
     for (size_t i = 0; i < n; ++i) xf[i] = ab_pixel_xf();
@@ -3283,7 +3035,7 @@ int ab_detect_stars(ab_ctx *ctx, const ab_plane *img, double sigma_threshold, ab
     AB_TRY(ab_stage_in(ctx, img, &in));
     std::vector<ab_detected_star> stars;
     double m = 0.0, s = 1.0;
-    const int rc = ab_detect_stars_device(ctx, in.dptr, in.rows, in.cols, in.cols, sigma_threshold, &stars, &m, &s);
+    const int rc = ab_detect_stars_device(ctx, in.dptr, in.rows, in.cols, sigma_threshold, &stars, &m, &s);
     ab_stage_release(ctx, &in);
     if (rc != AB_OK) return rc;
     const size_t n = std::min(cap, stars.size());

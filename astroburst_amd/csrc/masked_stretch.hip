@@ -196,7 +196,7 @@ int star_mask_device(ab_ctx *ctx, const float *img, int64_t rows, int64_t cols, 
 int detect_discs(ab_ctx *ctx, const float *img, int64_t rows, int64_t cols, double sigma, std::vector<StarDisc> *out) {
     std::vector<ab_detected_star> stars;
     double m, s;
-    AB_TRY(ab_detect_stars_device(ctx, img, rows, cols, cols, sigma, &stars, &m, &s));
+    AB_TRY(ab_detect_stars_device(ctx, img, rows, cols, sigma, &stars, &m, &s));
     out->clear();
     for (const ab_detected_star &st : stars) out->push_back({st.x, st.y, st.fwhm});
     return AB_OK;

@@ -299,7 +299,7 @@ int ab_spcc_calibrate_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, con
     memcpy(&lum_max_f, &bits, sizeof lum_max_f);
     const double lum_max = bits ? (double)lum_max_f : 0.0;  // compute_image_stats(lum).max (:88)
     double bm, bs;
-    if (rc == AB_OK) rc = ab_detect_stars_device(ctx, lum, h, w, w, 5.0, &stars, &bm, &bs);  // :86
+    if (rc == AB_OK) rc = ab_detect_stars_device(ctx, lum, h, w, 5.0, &stars, &bm, &bs);  // :86
     (void)hipStreamSynchronize(ctx->stream);
     if (rc != AB_OK) return rc;
     return spcc_from_detection(ctx, st.p[0].dptr, st.p[1].dptr, st.p[2].dptr, h, w, stars, lum_max, pixel_scale_arcsec, *cfg, res);

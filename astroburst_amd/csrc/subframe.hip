@@ -40,7 +40,7 @@ int analyze_one(ab_ctx *ctx, const ab_plane *img, const ab_subframe_weight_confi
     AB_TRY(ab_stage_in(ctx, img, &in));
     std::vector<ab_detected_star> stars;
     double bm = 0.0, bs = 1.0;
-    const int rc = ab_detect_stars_device(ctx, in.dptr, in.rows, in.cols, in.cols, kDetectionSigma, &stars, &bm, &bs, ab_pixel_xf(), (size_t)-1, false, bg);
+    const int rc = ab_detect_stars_device(ctx, in.dptr, in.rows, in.cols, kDetectionSigma, &stars, &bm, &bs, ab_pixel_xf(), (size_t)-1, false, bg);
     ab_stage_release(ctx, &in);
     if (rc != AB_OK) return rc;
     *out = ab_subframe_metrics{};
