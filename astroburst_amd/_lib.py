@@ -197,6 +197,42 @@ PSF_OUTCOME_MESSAGES = {AB_PSF_NO_STARS_DETECTED: "No stars detected in image", 
                         AB_PSF_NO_CUTOUTS: "Failed to extract star cutouts"}  # the reference's Err strings (:65, :87, :108)
 
 
+class SynthStarC(C.Structure):  # Star (core/synth/star_field.rs:4-10)
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("z", C.c_double), ("flux", C.c_double), ("temperature", C.c_double)]
+
+
+class SynthFieldConfigC(C.Structure):  # FieldConfig (star_field.rs:13-20)
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_stars", C.c_size_t), ("flux_min", C.c_double), ("flux_max", C.c_double),
+                ("seed", C.c_uint64)]
+
+
+class SynthFieldTypeC(C.Structure):  # FieldType (pipeline.rs:11-21): kind + the variant's two parameters
+    _fields_ = [("kind", C.c_int32), ("a", C.c_double), ("b", C.c_double)]
+
+
+class SynthPsfTypeC(C.Structure):  # PsfType (pipeline.rs:24-28): fwhm holds lambda_over_d for Airy
+    _fields_ = [("kind", C.c_int32), ("fwhm", C.c_double), ("beta", C.c_double)]
+
+
+class SynthNoiseParamsC(C.Structure):  # NoiseParams (noise.rs:8-16)
+    _fields_ = [("gain", C.c_double), ("readout_noise", C.c_double), ("sky_background", C.c_double), ("dark_current", C.c_double),
+                ("exposure_time", C.c_double), ("bias_level", C.c_double), ("seed", C.c_uint64)]
+
+
+class SynthConfigC(C.Structure):  # SynthConfig (pipeline.rs:31-39)
+    _fields_ = [("field", SynthFieldConfigC), ("field_type", SynthFieldTypeC), ("psf_type", SynthPsfTypeC), ("noise", SynthNoiseParamsC),
+                ("apply_vignette", C.c_int32), ("vignette_strength", C.c_double), ("n_frames", C.c_uint32)]
+
+
+class SynthResultC(C.Structure):
+    _fields_ = [("star_count", C.c_size_t), ("frames_on_host", C.c_size_t)]
+
+
+AB_SYNTH_FIELD_UNIFORM, AB_SYNTH_FIELD_KING_CLUSTER, AB_SYNTH_FIELD_EXPONENTIAL_DISK = range(3)
+AB_SYNTH_PSF_GAUSSIAN, AB_SYNTH_PSF_MOFFAT, AB_SYNTH_PSF_AIRY = range(3)
+AB_SYNTH_MAX_PSF_RADIUS = 512
+
+
 class WaveletConfigC(C.Structure):  # WaveletConfig (wavelet.rs:10-15): the threshold list as pointer + count
     _fields_ = [("num_scales", C.c_size_t), ("thresholds", C.POINTER(C.c_float)), ("num_thresholds", C.c_size_t),
                 ("linear_denoise", C.c_int32)]
@@ -442,6 +478,18 @@ def lib() -> C.CDLL:
     L.ab_psf_select_stars.argtypes = [C.POINTER(PsfStarC), C.c_size_t, C.POINTER(PsfEstimationConfigC), C.c_double, C.c_int64, C.c_int64,
                                       C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.ab_estimate_psf.argtypes = [vp, pp, C.POINTER(PsfEstimationConfigC), pp, C.POINTER(PsfStarC), C.c_size_t, C.POINTER(PsfResultC)]
+    scp, ssp, srp = C.POINTER(SynthConfigC), C.POINTER(SynthStarC), C.POINTER(SynthResultC)
+    L.ab_synth_config_default.argtypes = [scp]
+    L.ab_synth_config_default.restype = None
+    L.ab_synth_rng_f64.argtypes = [C.c_uint64, C.c_uint64, C.c_size_t, C.POINTER(C.c_double)]
+    L.ab_synth_chacha_block.argtypes = [C.POINTER(C.c_uint32), C.c_uint64, C.c_int, C.POINTER(C.c_uint32)]
+    L.ab_synth_star_field.argtypes = [scp, ssp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.ab_synth_render_stars.argtypes = [vp, ssp, C.c_size_t, C.POINTER(SynthPsfTypeC), pp]
+    L.ab_synth_flat_field.argtypes = [vp, C.c_uint64, C.c_double, pp]
+    L.ab_synth_apply_flat_field.argtypes = [vp, pp, pp]
+    L.ab_synth_apply_noise.argtypes = [vp, pp, C.POINTER(SynthNoiseParamsC), pp, srp]
+    L.ab_synth_generate.argtypes = [vp, scp, pp, pp, ssp, C.c_size_t, srp]
+    L.ab_synth_generate_stack.argtypes = [vp, scp, pp, pp, ssp, C.c_size_t, srp]
     L.ab_wavelet_scale_thresholds.argtypes = [C.c_double, C.POINTER(WaveletConfigC), C.POINTER(C.c_float)]
     L.ab_wavelet_denoise.argtypes = [vp, pp, C.POINTER(WaveletConfigC), pp, C.POINTER(WaveletResultC)]
     f32p = C.POINTER(C.c_float)

@@ -308,6 +308,99 @@ def psf_select_stars(stars, max_val: float, rows: int, cols: int, **config):
     return [int(idx[i]) for i in range(sel.value)], int(flt.value)
 
 
+_SYNTH_FIELDS = {"uniform": _lib.AB_SYNTH_FIELD_UNIFORM, "king_cluster": _lib.AB_SYNTH_FIELD_KING_CLUSTER,
+                 "exponential_disk": _lib.AB_SYNTH_FIELD_EXPONENTIAL_DISK}
+_SYNTH_PSFS = {"gaussian": _lib.AB_SYNTH_PSF_GAUSSIAN, "moffat": _lib.AB_SYNTH_PSF_MOFFAT, "airy": _lib.AB_SYNTH_PSF_AIRY}
+
+
+def synth_psf_type(psf) -> "_lib.SynthPsfTypeC":
+    """PsfType (core/synth/pipeline.rs:24-28) from ("gaussian", fwhm), ("moffat", fwhm, beta) or ("airy", lambda_over_d)"""
+    if isinstance(psf, _lib.SynthPsfTypeC):
+        return psf
+    kind, *par = psf
+    par = [float(v) for v in par] + [0.0, 0.0]
+    return _lib.SynthPsfTypeC(_SYNTH_PSFS[kind] if isinstance(kind, str) else int(kind), par[0], par[1])
+
+
+def synth_noise_params(**fields) -> "_lib.SynthNoiseParamsC":
+    """NoiseParams::default() (noise.rs:18-30, filled in by the library) with the given fields replaced"""
+    cfg = _lib.SynthConfigC()
+    _lib.lib().ab_synth_config_default(C.byref(cfg))
+    p = _lib.SynthNoiseParamsC.from_buffer_copy(cfg.noise)
+    for name, val in fields.items():
+        setattr(p, name, int(val) & (2 ** 64 - 1) if name == "seed" else float(val))
+    return p
+
+
+def synth_config(field_type=("uniform",), psf=None, noise=None, apply_vignette=None, vignette_strength=None, n_frames=None,
+                 **field) -> "_lib.SynthConfigC":
+    """SynthConfig::default() (pipeline.rs:41-53, filled in by the library) with the given parts replaced.  field_type: ("uniform",),
+    ("king_cluster", core_radius, tidal_radius) or ("exponential_disk", scale_length, inclination_deg); psf: see synth_psf_type;
+    noise: a dict of NoiseParams fields; the remaining keywords are FieldConfig's (width, height, n_stars, flux_min, flux_max, seed)."""
+    cfg = _lib.SynthConfigC()
+    _lib.lib().ab_synth_config_default(C.byref(cfg))
+    kind, *par = field_type
+    par = [float(v) for v in par] + [0.0, 0.0]
+    cfg.field_type = _lib.SynthFieldTypeC(_SYNTH_FIELDS[kind] if isinstance(kind, str) else int(kind), par[0], par[1])
+    if psf is not None:
+        cfg.psf_type = synth_psf_type(psf)
+    if noise is not None:
+        cfg.noise = synth_noise_params(**noise)
+    if apply_vignette is not None:
+        cfg.apply_vignette = 1 if apply_vignette else 0
+    if vignette_strength is not None:
+        cfg.vignette_strength = float(vignette_strength)
+    if n_frames is not None:
+        cfg.n_frames = int(n_frames)
+    for name, val in field.items():
+        if name not in ("width", "height", "n_stars", "flux_min", "flux_max", "seed"):
+            raise TypeError(f"unknown FieldConfig field {name}")
+        setattr(cfg.field, name, float(val) if name.startswith("flux") else int(val) & (2 ** 64 - 1) if name == "seed" else int(val))
+    return cfg
+
+
+def synth_rng_f64(seed: int, skip: int, n: int) -> np.ndarray:
+    """draws skip .. skip + n - 1 (gen::<f64>()) of rand 0.8.5's StdRng::seed_from_u64(seed); host-only"""
+    out = np.empty(int(n), np.float64)
+    rc = _lib.lib().ab_synth_rng_f64(int(seed) & (2 ** 64 - 1), int(skip), int(n), out.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc != _lib.AB_OK:
+        raise AstroBurstError(rc, "ab_synth_rng_f64: bad arguments")
+    return out
+
+
+def synth_chacha_block(key, counter: int, rounds: int = 12) -> np.ndarray:
+    """test hook: the 16 output words of one ChaCha block (key: eight u32 words; 64-bit counter; zero stream id); host-only"""
+    k = np.ascontiguousarray(key, dtype=np.uint32)
+    assert k.shape == (8,)
+    out = np.empty(16, np.uint32)
+    u32p = C.POINTER(C.c_uint32)
+    rc = _lib.lib().ab_synth_chacha_block(k.ctypes.data_as(u32p), int(counter), int(rounds), out.ctypes.data_as(u32p))
+    if rc != _lib.AB_OK:
+        raise AstroBurstError(rc, "ab_synth_chacha_block: rounds must be 12 or 20")
+    return out
+
+
+def synth_star_field(cfg=None, **config) -> np.ndarray:
+    """gen_field (pipeline.rs:126-138) of a SynthConfig (or of synth_config(**config)) -> float64 array (n_stars, 5): x, y, z, flux,
+    temperature per star.  Host scalar maths in the library: no GPU."""
+    cfg = cfg if cfg is not None else synth_config(**config)
+    n = int(cfg.field.n_stars)
+    out = np.zeros((max(n, 1), 5), np.float64)
+    got = C.c_size_t(0)
+    rc = _lib.lib().ab_synth_star_field(C.byref(cfg), out.ctypes.data_as(C.POINTER(_lib.SynthStarC)), n, C.byref(got))
+    if rc != _lib.AB_OK:
+        raise AstroBurstError(rc, "ab_synth_star_field: the field would not terminate (king_cluster radii) or its kind is unknown")
+    return out[:n]
+
+
+@dataclass
+class SynthFrames:  # what generate / generate_stack return (pipeline.rs:63, :84) + the library's route count
+    frames: list
+    truth: object
+    stars: np.ndarray   # (star_count, 5): x, y, z, flux, temperature
+    frames_on_host: int
+
+
 def power_spectrum_dims(rows: int, cols: int):
     """(original_size, display_size) of compute_power_spectrum (core/analysis/fft.rs:24-25, :53-57): the next power of two of the
     longer side, and that capped at 1024.  Host-only; images beyond 16384 a side raise AB_ERR_UNSUPPORTED."""
@@ -1990,6 +2083,89 @@ class Context:
         low; always for "zncc"), then drizzle_frames."""
         cfg = _drizzle_config(scale, pixfrac, kernel, sigma_low, sigma_high, sigma_iterations, align, alignment_method, num_threads)
         return self._drizzle(frames, None, cfg, out, out_weight, want_weight)
+
+    # ---- core/synth (generate_synth_cmd, generate_synth_stack_cmd) ----------------------------------------
+    synth_config = staticmethod(synth_config)
+    synth_star_field = staticmethod(synth_star_field)
+    synth_rng_f64 = staticmethod(synth_rng_f64)
+
+    def _synth_out(self, out, rows, cols, device, keep):
+        """(array or tensor, ab_plane_mut) of a synth output: `out` if given, else a new CUDA tensor (device) or numpy array"""
+        if out is None:
+            out = torch.empty((rows, cols), dtype=torch.float32, device=f"cuda:{self.device}") if device else np.empty((rows, cols), np.float32)
+        if not _is_torch(out) and (out.dtype != np.float32 or not out.flags.c_contiguous or out.ndim != 2):
+            raise AstroBurstError(_lib.AB_ERR_INVALID, "outputs are contiguous 2-D float32 arrays")
+        return out, self._out_plane(out, keep, int(out.shape[0]), int(out.shape[1]))
+
+    @staticmethod
+    def _synth_stars(stars):
+        a = np.ascontiguousarray(stars, dtype=np.float64).reshape(-1, 5)
+        return a, a.ctypes.data_as(C.POINTER(_lib.SynthStarC)), a.shape[0]
+
+    def synth_render_stars(self, stars, psf, rows, cols, out=None, device=False):
+        """render_stars (core/synth/psf.rs:123-158): stars (n, 5) as synth_star_field returns them, psf as synth_psf_type takes it ->
+        the rows x cols f32 plane (numpy, or a CUDA tensor with device=True / a tensor `out`)"""
+        keep = []
+        out, po = self._synth_out(out, int(rows), int(cols), device, keep)
+        a, ptr, n = self._synth_stars(stars)
+        pt = synth_psf_type(psf)
+        self._check(self._L.ab_synth_render_stars(self._h, ptr, n, C.byref(pt), C.byref(po)))
+        return out
+
+    def synth_flat_field(self, rows, cols, seed, vignette_strength, out=None, device=False):
+        """generate_flat_field (noise.rs:81-99), bit for bit"""
+        keep = []
+        out, po = self._synth_out(out, int(rows), int(cols), device, keep)
+        self._check(self._L.ab_synth_flat_field(self._h, int(seed) & (2 ** 64 - 1), float(vignette_strength), C.byref(po)))
+        return out
+
+    def synth_apply_flat_field(self, image, flat):
+        """apply_flat_field (noise.rs:101-111): image /= flat where flat > 1e-6, in place (a float32 numpy array or a CUDA tensor)"""
+        keep = []
+        if not _is_torch(image) and not (isinstance(image, np.ndarray) and image.dtype == np.float32 and image.flags.c_contiguous and image.ndim == 2):
+            raise AstroBurstError(_lib.AB_ERR_INVALID, "the in-place image must be a contiguous 2-D float32 array")
+        pi = self._out_plane(image, keep, int(image.shape[0]), int(image.shape[1]))
+        pf = self._plane(flat, keep)
+        self._check(self._L.ab_synth_apply_flat_field(self._h, C.byref(pi), C.byref(pf)))
+        return image
+
+    def synth_apply_noise(self, image, out=None, **noise):
+        """apply_noise (noise.rs:62-79) -> (noisy plane of the image's kind, frames_on_host: 1 if the general host route ran, else 0).
+        noise: NoiseParams' fields (gain, readout_noise, sky_background, dark_current, exposure_time, bias_level, seed)."""
+        keep = []
+        pi = self._plane(image, keep)
+        out, po = self._synth_out(out, pi.rows, pi.cols, _is_torch(image) and image.is_cuda, keep)
+        p = synth_noise_params(**noise)
+        res = _lib.SynthResultC()
+        self._check(self._L.ab_synth_apply_noise(self._h, C.byref(pi), C.byref(p), C.byref(po), C.byref(res)))
+        return out, int(res.frames_on_host)
+
+    def _synth_generate(self, cfg, n, stack, device, want_truth):
+        keep = []
+        rows, cols = int(cfg.field.height), int(cfg.field.width)
+        outs = [self._synth_out(None, rows, cols, device, keep) for _ in range(n)]
+        frames = (Plane * max(n, 1))(*[po for _, po in outs])
+        truth, pt = self._synth_out(None, rows, cols, device, keep) if want_truth else (None, None)
+        cap = int(cfg.field.n_stars)
+        stars = np.zeros((max(cap, 1), 5), np.float64)
+        res = _lib.SynthResultC()
+        fn = self._L.ab_synth_generate_stack if stack else self._L.ab_synth_generate
+        self._check(fn(self._h, C.byref(cfg), frames, C.byref(pt) if pt is not None else None, stars.ctypes.data_as(C.POINTER(_lib.SynthStarC)),
+                       cap, C.byref(res)))
+        return SynthFrames([o for o, _ in outs], truth, stars[:min(cap, int(res.star_count))], int(res.frames_on_host))
+
+    def synth_generate(self, cfg=None, device=False, want_truth=True, **config) -> SynthFrames:
+        """generate (pipeline.rs:63-82) of a SynthConfig (or synth_config(**config)): one noisy frame, the ground truth, the stars"""
+        cfg = cfg if cfg is not None else synth_config(**config)
+        return self._synth_generate(cfg, 1, False, device, want_truth)
+
+    def synth_generate_stack(self, cfg=None, device=False, want_truth=True, **config) -> SynthFrames:
+        """generate_stack (pipeline.rs:84-108): cfg.n_frames noisy frames of one rendering; device frames go straight into
+        stack_sigma_clip"""
+        cfg = cfg if cfg is not None else synth_config(**config)
+        if int(cfg.n_frames) == 0:
+            raise AstroBurstError(_lib.AB_ERR_INVALID, "n_frames must be at least 1")
+        return self._synth_generate(cfg, int(cfg.n_frames), True, device, want_truth)
 
     # ---- bench support -----------------------------------------------------------------------------
     def bench_copy(self, src, dst):

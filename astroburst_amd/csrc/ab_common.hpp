@@ -62,6 +62,7 @@ enum {
     AB_WS_FFT_B,              // its transpose, which the second line pass transforms in place (spectrum.hip)
     AB_WS_CUBE,               // the device copy of a host-resident spectral cube, for the length of one call (cube.hip)
     AB_WS_PSF,                // PSF estimation: statistics partials, the candidate counter, the f64 / f32 kernel and its scalars (psf.hip)
+    AB_WS_SYNTH,              // synthetic generator: star records, norms, tile lists, the frames' route flags (synth.hip)
     AB_WS_SLOTS
 };
 

@@ -46,6 +46,9 @@ use crate::core::imaging::psf_estimation::{PsfEstimationConfig, PsfResult, StarC
 use crate::core::imaging::star_mask::{StarMaskConfig, StarMaskResult};
 use crate::core::imaging::wavelet::{WaveletConfig, WaveletResult};
 use crate::core::stacking::calibration::CalibrationConfig;
+use crate::core::synth::noise::NoiseParams;
+use crate::core::synth::pipeline::{FieldType, PsfType, SynthConfig};
+use crate::core::synth::star_field::{FieldConfig, Star};
 use crate::infra::progress::ProgressHandle;
 use crate::types::compose::{AlignMethod, ChannelStats, DimensionHarmonize, RgbComposeConfig, WhiteBalance};
 use crate::types::image::{AutoStfConfig, ImageStats, ScnrConfig, ScnrMethod, StfParams};
@@ -804,6 +807,158 @@ pub fn psf_to_kernel(psf: &PsfResult) -> Array2<f32> {
         }
     }
     kernel
+}
+
+// ---- core/synth (generate_synth_cmd, generate_synth_stack_cmd) --------------------------------------------------------------------------------------------
+fn synth_psf(p: &PsfType) -> sys::ab_synth_psf_type {
+    match *p {
+        PsfType::Gaussian { fwhm } => sys::ab_synth_psf_type { kind: sys::AB_SYNTH_PSF_GAUSSIAN, fwhm, beta: 0.0 },
+        PsfType::Moffat { fwhm, beta } => sys::ab_synth_psf_type { kind: sys::AB_SYNTH_PSF_MOFFAT, fwhm, beta },
+        PsfType::Airy { lambda_over_d } => sys::ab_synth_psf_type { kind: sys::AB_SYNTH_PSF_AIRY, fwhm: lambda_over_d, beta: 0.0 },
+    }
+}
+fn synth_noise(n: &NoiseParams) -> sys::ab_synth_noise_params {
+    sys::ab_synth_noise_params {
+        gain: n.gain,
+        readout_noise: n.readout_noise,
+        sky_background: n.sky_background,
+        dark_current: n.dark_current,
+        exposure_time: n.exposure_time,
+        bias_level: n.bias_level,
+        seed: n.seed,
+    }
+}
+fn synth_cfg(c: &SynthConfig) -> sys::ab_synth_config {
+    let field_type = match c.field_type {
+        FieldType::Uniform => sys::ab_synth_field_type { kind: sys::AB_SYNTH_FIELD_UNIFORM, a: 0.0, b: 0.0 },
+        FieldType::KingCluster { core_radius, tidal_radius } => sys::ab_synth_field_type { kind: sys::AB_SYNTH_FIELD_KING_CLUSTER, a: core_radius, b: tidal_radius },
+        FieldType::ExponentialDisk { scale_length, inclination_deg } => {
+            sys::ab_synth_field_type { kind: sys::AB_SYNTH_FIELD_EXPONENTIAL_DISK, a: scale_length, b: inclination_deg }
+        }
+    };
+    sys::ab_synth_config {
+        field: sys::ab_synth_field_config {
+            width: c.field.width,
+            height: c.field.height,
+            n_stars: c.field.n_stars,
+            flux_min: c.field.flux_min,
+            flux_max: c.field.flux_max,
+            seed: c.field.seed,
+        },
+        field_type,
+        psf_type: synth_psf(&c.psf_type),
+        noise: synth_noise(&c.noise),
+        apply_vignette: c.apply_vignette as i32,
+        vignette_strength: c.vignette_strength,
+        n_frames: c.n_frames,
+    }
+}
+fn synth_stars_in(stars: &[Star]) -> Vec<sys::ab_synth_star> {
+    stars.iter().map(|s| sys::ab_synth_star { x: s.x, y: s.y, z: s.z, flux: s.flux, temperature: s.temperature }).collect()
+}
+fn synth_stars_out(stars: &[sys::ab_synth_star]) -> Vec<Star> {
+    stars.iter().map(|s| Star { x: s.x, y: s.y, z: s.z, flux: s.flux, temperature: s.temperature }).collect()
+}
+/// SynthConfig::default() (pipeline.rs:41-53) as the library fills it in
+pub fn synth_config_default() -> SynthConfig {
+    let mut c: sys::ab_synth_config = unsafe { std::mem::zeroed() };
+    unsafe { sys::ab_synth_config_default(&mut c) };
+    SynthConfig {
+        field: FieldConfig { width: c.field.width, height: c.field.height, n_stars: c.field.n_stars, flux_min: c.field.flux_min, flux_max: c.field.flux_max, seed: c.field.seed },
+        field_type: FieldType::Uniform,
+        psf_type: PsfType::Gaussian { fwhm: c.psf_type.fwhm },
+        noise: NoiseParams {
+            gain: c.noise.gain,
+            readout_noise: c.noise.readout_noise,
+            sky_background: c.noise.sky_background,
+            dark_current: c.noise.dark_current,
+            exposure_time: c.noise.exposure_time,
+            bias_level: c.noise.bias_level,
+            seed: c.noise.seed,
+        },
+        apply_vignette: c.apply_vignette != 0,
+        vignette_strength: c.vignette_strength,
+        n_frames: c.n_frames,
+    }
+}
+/// draws skip .. skip + n - 1 of StdRng::seed_from_u64(seed) as gen::<f64>(): what the generator's kernels compute per pixel
+pub fn synth_rng_f64(seed: u64, skip: u64, n: usize) -> Vec<f64> {
+    let mut out = vec![0.0f64; n];
+    unsafe { sys::ab_synth_rng_f64(seed, skip, n, out.as_mut_ptr()) };
+    out
+}
+/// test hook: one block of the ChaCha block function behind the stream (rounds = 12 or 20)
+pub fn synth_chacha_block(key: &[u32; 8], counter: u64, rounds: i32) -> Result<[u32; 16]> {
+    let mut out = [0u32; 16];
+    let rc = unsafe { sys::ab_synth_chacha_block(key.as_ptr(), counter, rounds, out.as_mut_ptr()) };
+    if rc != sys::AB_OK {
+        bail!("synth_chacha_block: rounds must be 12 or 20");
+    }
+    Ok(out)
+}
+/// drop-in for gen_field (pipeline.rs:126-138): uniform_field / king_cluster / exponential_disk; an Err where the reference would not return
+pub fn synth_star_field(config: &SynthConfig) -> Result<Vec<Star>> {
+    let cap = config.field.n_stars;
+    let mut stars: Vec<sys::ab_synth_star> = vec![unsafe { std::mem::zeroed() }; cap.max(1)];
+    let mut n = 0usize;
+    let rc = unsafe { sys::ab_synth_star_field(&synth_cfg(config), stars.as_mut_ptr(), cap, &mut n) };
+    if rc != sys::AB_OK {
+        bail!("star field: king_cluster needs positive finite radii and a profile that can accept (status {rc})");
+    }
+    Ok(synth_stars_out(&stars[..n.min(cap)]))
+}
+/// drop-in for render_stars (psf.rs:123-158)
+pub fn render_stars(hip: &Hip, stars: &[Star], psf: &PsfType, width: u32, height: u32) -> Result<Array2<f32>> {
+    let mut image = Array2::<f32>::zeros((height as usize, width as usize));
+    let c = synth_stars_in(stars);
+    let mut po = image.ab_mut();
+    hip.check(unsafe { sys::ab_synth_render_stars(hip.ctx, c.as_ptr(), c.len(), &synth_psf(psf), &mut po) })?;
+    Ok(image)
+}
+/// drop-in for generate_flat_field (noise.rs:81-99)
+pub fn generate_flat_field(hip: &Hip, width: u32, height: u32, seed: u64, vignette_strength: f64) -> Result<Array2<f32>> {
+    let mut flat = Array2::<f32>::zeros((height as usize, width as usize));
+    let mut po = flat.ab_mut();
+    hip.check(unsafe { sys::ab_synth_flat_field(hip.ctx, seed, vignette_strength, &mut po) })?;
+    Ok(flat)
+}
+/// drop-in for apply_flat_field (noise.rs:101-111)
+pub fn apply_flat_field(hip: &Hip, image: &mut impl PlaneDst, flat: &impl PlaneSrc) -> Result<()> {
+    let mut pi = image.ab_mut();
+    hip.check(unsafe { sys::ab_synth_apply_flat_field(hip.ctx, &mut pi, &flat.ab()) })
+}
+/// drop-in for apply_noise (noise.rs:62-79)
+pub fn apply_noise(hip: &Hip, image: &impl PlaneSrc, params: &NoiseParams) -> Result<Array2<f32>> {
+    let mut out = Array2::<f32>::zeros(image.dims());
+    let mut po = out.ab_mut();
+    hip.check(unsafe { sys::ab_synth_apply_noise(hip.ctx, &image.ab(), &synth_noise(params), &mut po, std::ptr::null_mut()) })?;
+    Ok(out)
+}
+/// drop-in for generate (pipeline.rs:63-82): (noisy, ground_truth, stars)
+pub fn synth_generate(hip: &Hip, config: &SynthConfig) -> Result<(Array2<f32>, Array2<f32>, Vec<Star>)> {
+    let dims = (config.field.height as usize, config.field.width as usize);
+    let (mut noisy, mut truth) = (Array2::<f32>::zeros(dims), Array2::<f32>::zeros(dims));
+    let cap = config.field.n_stars;
+    let mut stars: Vec<sys::ab_synth_star> = vec![unsafe { std::mem::zeroed() }; cap.max(1)];
+    let mut res: sys::ab_synth_result = unsafe { std::mem::zeroed() };
+    let (mut pn, mut pt) = (noisy.ab_mut(), truth.ab_mut());
+    hip.check(unsafe { sys::ab_synth_generate(hip.ctx, &synth_cfg(config), &mut pn, &mut pt, stars.as_mut_ptr(), cap, &mut res) })?;
+    Ok((noisy, truth, synth_stars_out(&stars[..res.star_count.min(cap)])))
+}
+/// drop-in for generate_stack (pipeline.rs:84-108), progress ("synth", k, n) and cancel per frame: (frames, ground_truth, stars)
+pub fn synth_generate_stack(hip: &Hip, config: &SynthConfig, progress: Option<&ProgressHandle>) -> Result<(Vec<Array2<f32>>, Array2<f32>, Vec<Star>)> {
+    let dims = (config.field.height as usize, config.field.width as usize);
+    let mut frames: Vec<Array2<f32>> = (0..config.n_frames).map(|_| Array2::<f32>::zeros(dims)).collect();
+    let mut truth = Array2::<f32>::zeros(dims);
+    let cap = config.field.n_stars;
+    let mut stars: Vec<sys::ab_synth_star> = vec![unsafe { std::mem::zeroed() }; cap.max(1)];
+    let mut res: sys::ab_synth_result = unsafe { std::mem::zeroed() };
+    let mut planes: Vec<sys::ab_plane_mut> = frames.iter_mut().map(|f| f.ab_mut()).collect();
+    let mut pt = truth.ab_mut();
+    hip.with_progress(progress, || {
+        hip.check(unsafe { sys::ab_synth_generate_stack(hip.ctx, &synth_cfg(config), planes.as_mut_ptr(), &mut pt, stars.as_mut_ptr(), cap, &mut res) })
+    })?;
+    Ok((frames, truth, synth_stars_out(&stars[..res.star_count.min(cap)])))
 }
 
 // ---- core/imaging/wavelet.rs (wavelet_denoise_cmd) ------------------------------------------------------------------------------------------------------

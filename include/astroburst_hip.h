@@ -731,6 +731,114 @@ AB_API int ab_psf_select_stars(const ab_psf_star *stars, size_t n, const ab_psf_
 AB_API int ab_estimate_psf(ab_ctx *ctx, const ab_plane *img, const ab_psf_estimation_config *cfg, ab_plane_mut *kernel_out,
                            ab_psf_star *stars_out, size_t stars_cap, ab_psf_result *res);
 
+/* ---- the synthetic star-field generator, core/synth/{star_field,psf,noise,pipeline}.rs (generate_synth_cmd, generate_synth_stack_cmd) -- */
+typedef struct { /* Star (star_field.rs:4-10) */
+    double x, y, z, flux, temperature;
+} ab_synth_star;
+typedef struct { /* FieldConfig (star_field.rs:13-20); Default (:22-33): 2048 x 2048, 500 stars, flux 100 .. 50000, seed 42 */
+    uint32_t width, height;
+    size_t n_stars;
+    double flux_min, flux_max;
+    uint64_t seed;
+} ab_synth_field_config;
+typedef enum { /* FieldType (pipeline.rs:11-21) */
+    AB_SYNTH_FIELD_UNIFORM = 0,
+    AB_SYNTH_FIELD_KING_CLUSTER = 1,     /* a = core_radius, b = tidal_radius */
+    AB_SYNTH_FIELD_EXPONENTIAL_DISK = 2  /* a = scale_length, b = inclination_deg */
+} ab_synth_field_kind;
+typedef struct {
+    int32_t kind; /* an ab_synth_field_kind */
+    double a, b;  /* the variant's two parameters (ignored for Uniform) */
+} ab_synth_field_type;
+typedef enum { /* PsfType (pipeline.rs:24-28) */
+    AB_SYNTH_PSF_GAUSSIAN = 0, /* fwhm */
+    AB_SYNTH_PSF_MOFFAT = 1,   /* fwhm, beta */
+    AB_SYNTH_PSF_AIRY = 2      /* fwhm holds lambda_over_d */
+} ab_synth_psf_kind;
+typedef struct {
+    int32_t kind; /* an ab_synth_psf_kind */
+    double fwhm;  /* Gaussian / Moffat: fwhm; Airy: lambda_over_d (pixels) */
+    double beta;  /* Moffat only */
+} ab_synth_psf_type;
+typedef struct { /* NoiseParams (noise.rs:8-16); Default (:18-30): 1.5, 8.0, 200.0, 0.05, 300.0, 1000.0, seed 123 */
+    double gain, readout_noise, sky_background, dark_current, exposure_time, bias_level;
+    uint64_t seed;
+} ab_synth_noise_params;
+typedef struct { /* SynthConfig (pipeline.rs:31-39); Default (:41-53): Uniform, Gaussian fwhm 3, no vignette, strength 0.3, 1 frame */
+    ab_synth_field_config field;
+    ab_synth_field_type field_type;
+    ab_synth_psf_type psf_type;
+    ab_synth_noise_params noise;
+    int32_t apply_vignette; /* bool */
+    double vignette_strength;
+    uint32_t n_frames;
+} ab_synth_config;
+typedef struct {
+    size_t star_count;     /* SynthResult.star_count */
+    size_t frames_on_host; /* frames whose noise took the general (host) route, see ab_synth_apply_noise */
+} ab_synth_result;
+#define AB_SYNTH_MAX_PSF_RADIUS 512
+/* EXACTNESS of this section.  Every generator of the reference is StdRng::seed_from_u64(seed) of rand 0.8.5: ChaCha with 12 rounds
+ * (rand_chacha 0.3.1), keyed by eight PCG32 outputs over the seed (rand_core 0.6.4), 64-bit block counter from 0, stream id 0,
+ * words consumed in block order, gen::<f64>() = (next_u64() >> 11) * 2^-53.  A draw's position in the stream decides its value, so
+ * each pixel computes its own draws wherever the number of draws per pixel is fixed.
+ *   - the stream, the star fields, the flat field and apply_flat_field: bit for bit the reference's algorithm (IEEE + - * / sqrt on
+ *     the device, glibc pow / cos / sin / log on the host -- what Rust's f64 methods call on Linux).
+ *   - ab_synth_render_stars: the device's f64 exp / pow / sin / cos are not glibc's and psf_sum is a fixed tree sum, not a raster-order
+ *     one.  Relative differences of a few 2^-53 are far below half an f32 ulp, so each f32 addend is the reference's or its neighbour:
+ *     a pixel covered by k stars differs by at most 2 k ulp of its accumulated value, a pixel covered by none is exactly 0.0.  The
+ *     addends are accumulated in star order (a gather over per-tile lists in ascending star index, no atomics).
+ *   - ab_synth_apply_noise, fast route: given the same input plane the photon count is the reference's whenever
+ *     lambda + sqrt(lambda) * N(0, 1) is further from a half-integer than the f64 error of that product (below about 1e-9 for lambda up
+ *     to 1e6); the output is then within one f32 ulp.  General route: bit for bit.
+ *   - run to run every output is bit-identical.
+ *   - agreement with frames the reference actually writes rests on rand 0.8.5's published algorithms and has NOT been checked
+ *     against a Rust build (there is no rustc where this library is built, and the reference has no test or fixture for this
+ *     module) -- as for rustfft in ab_phase_correlate.  The ChaCha block function passes the published 20-round vector.
+ * One DELIBERATE difference: a star whose window lies wholly left of or above the image (x + psf_r < 0; king_cluster and
+ * exponential_disk can produce one) makes the reference's `as usize` bound wrap, and render_stars then loops over ~2^64 pixels and
+ * does not return.  The library skips such a star, as the reference itself skips one wholly right of or below the image. */
+AB_API void ab_synth_config_default(ab_synth_config *cfg);
+/* draws skip .. skip + n - 1 (as gen::<f64>()) of StdRng::seed_from_u64(seed); host-only */
+AB_API int ab_synth_rng_f64(uint64_t seed, uint64_t skip, size_t n, double *out);
+/* test hook: one 64-byte block of the ChaCha block function behind the stream -- key of eight u32 words, 64-bit counter, zero stream
+ * id; rounds = 12 (the generator's) or 20 (RFC 7539's known answers with a zero nonce); any other count -> AB_ERR_INVALID.  Host-only. */
+AB_API int ab_synth_chacha_block(const uint32_t *key, uint64_t counter, int rounds, uint32_t *out16);
+/* gen_field (pipeline.rs:126-138): uniform_field (star_field.rs:52-66), king_cluster (:68-93) or exponential_disk (:95-119) of
+ * cfg->field / cfg->field_type, in the reference's draw order; host-only scalar maths.  stars_out receives the first
+ * min(n_stars, cap) stars (nullable when cap = 0), *n_out = n_stars.  AB_ERR_INVALID for what would not terminate in the reference:
+ * king_cluster with a non-positive or non-finite core or tidal radius, or a profile that can never accept (its maximum, at r = 0,
+ * is not positive); also for an unknown kind. */
+AB_API int ab_synth_star_field(const ab_synth_config *cfg, ab_synth_star *stars_out, size_t cap, size_t *n_out);
+/* render_stars (psf.rs:123-158) of n host-side stars into out (host or device; its dims are the image's; every pixel is written).
+ * AB_ERR_INVALID: a non-finite x, y or flux (the reference writes NaN into pixel (0, 0) for those); a non-positive or non-finite
+ * PSF parameter.  AB_ERR_UNSUPPORTED: psf_r = ceil(radius) above AB_SYNTH_MAX_PSF_RADIUS (512 px: a star's window is then over a
+ * million pixels -- the default Gaussian has psf_r = 6).  Stars wholly outside the image on any side are skipped (see above). */
+AB_API int ab_synth_render_stars(ab_ctx *ctx, const ab_synth_star *stars, size_t n, const ab_synth_psf_type *psf, ab_plane_mut *out);
+/* generate_flat_field (noise.rs:81-99): pixel i (raster order) takes draw i of the seed's stream.  out host or device. */
+AB_API int ab_synth_flat_field(ab_ctx *ctx, uint64_t seed, double vignette_strength, ab_plane_mut *out);
+/* apply_flat_field (noise.rs:101-111): img /= flat where flat > 1e-6 (f32 division), in place; both host or device, equal dims. */
+AB_API int ab_synth_apply_flat_field(ab_ctx *ctx, ab_plane_mut *img_inout, const ab_plane *flat);
+/* apply_noise (noise.rs:62-79).  img and out host or device, equal dims, not overlapping.
+ * FAST ROUTE: where every pixel's signal_e.max(0) is finite and >= 30 (the default parameters give 90 015) each pixel takes
+ * exactly four draws, and one lane computes the ChaCha block of two adjacent pixels in raster order.  GENERAL ROUTE: the kernel
+ * raises a flag if any pixel is below 30 or non-finite; the frame is then recomputed on the host by the reference's serial walk
+ * (Knuth's product loop takes a data-dependent number of draws) over the same stream code.  Reading the flag makes the call
+ * synchronous.  res (nullable): frames_on_host = 1 if the general route ran, else 0.  The route is not an ab_fallback_kind. */
+AB_API int ab_synth_apply_noise(ab_ctx *ctx, const ab_plane *img, const ab_synth_noise_params *params, ab_plane_mut *out,
+                                ab_synth_result *res);
+/* generate (pipeline.rs:63-82): star field, render, optional flat (seed noise.seed + 999, wrapping), noise -- chained on the device.
+ * noisy_out and truth_out (nullable) host or device, height x width; stars_out receives min(star_count, cap) stars (nullable
+ * when cap = 0).  res (nullable).  The errors of the steps above, and AB_ERR_INVALID for planes that are not height x width. */
+AB_API int ab_synth_generate(ab_ctx *ctx, const ab_synth_config *cfg, ab_plane_mut *noisy_out, ab_plane_mut *truth_out,
+                             ab_synth_star *stars_out, size_t cap, ab_synth_result *res);
+/* generate_stack (pipeline.rs:84-108): rendered once; frame i uses flat seed noise.seed + 999 + i and noise seed
+ * noise.seed + i * 7919 (both wrapping, as a release build of the reference).  frames_out: cfg->n_frames planes (n_frames = 0 ->
+ * AB_ERR_INVALID); device frames can be handed straight to ab_stack_sigma_clip.  The progress callback is ticked ("synth", k, n)
+ * and cancellation seen before each frame; the frames' route flags are read once at the end. */
+AB_API int ab_synth_generate_stack(ab_ctx *ctx, const ab_synth_config *cfg, ab_plane_mut *frames_out, ab_plane_mut *truth_out,
+                                   ab_synth_star *stars_out, size_t cap, ab_synth_result *res);
+
 /* ---- drizzle stacking, core/stacking/drizzle.rs (calibration.rs:320 drizzle_from_paths, drizzle_rgb_cmd) ------------------- */
 typedef struct { /* DrizzleConfig (types/stacking.rs) */
     double scale;   /* clamped to [1, 4] (drizzle.rs:274) */
