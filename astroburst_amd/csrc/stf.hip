@@ -4,7 +4,8 @@
 // StfTransform (:60-87), apply_stf -> u8 (:89-102), apply_stf_f32 (:104-120) and
 // apply_stf_inplace (:147-155).
 //
-// Pure streaming map: 4 B read, 1 B (u8) or 4 B (f32) written per pixel, float4 / uchar4 wide.
+// Pure streaming map: 4 B read, 1 B (u8) or 4 B (f32) written per pixel, float4 / uchar4 wide where the planes' alignment allows it
+// (any 4-byte aligned f32 plane and any u8 pointer are accepted: the scalar loop takes what the wide accesses cannot).
 // The per-pixel arithmetic is f64 in the reference's evaluation order, so the u8 output is
 // bit-exact against the CPU restatement.
 #include "ab_common.hpp"
@@ -14,9 +15,11 @@
 
 namespace {
 
+// vec (uniform): `in` is 16-byte and `out` 4-byte aligned, so the float4 / uchar4 accesses are legal; otherwise the scalar loop
+// takes every pixel (a contiguous view that starts inside an allocation is a valid plane)
 __global__ __launch_bounds__(256) void stf_u8_kernel(const float *__restrict__ in, int64_t n, StfTx t,
-                                                     unsigned char *__restrict__ out) {
-    const int64_t n4 = n >> 2;
+                                                     unsigned char *__restrict__ out, int vec) {
+    const int64_t n4 = vec ? (n >> 2) : 0;
     const int64_t stride = (int64_t)gridDim.x * 256;
     const float4 *in4 = reinterpret_cast<const float4 *>(in);
     uchar4 *out4 = reinterpret_cast<uchar4 *>(out);
@@ -29,18 +32,15 @@ __global__ __launch_bounds__(256) void stf_u8_kernel(const float *__restrict__ i
         r.w = to_u8(v.w, t);
         out4[i] = r;
     }
-    if (blockIdx.x == 0) {
-        const int64_t i = (n4 << 2) + threadIdx.x;
-        if (i < n) out[i] = to_u8(in[i], t);
-    }
+    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) out[i] = to_u8(in[i], t);
 }
 
 // the same map with the transform read from HBM (written by the statistics chain, stats.hip): no host round trip between
 // compute_image_stats -> auto_stf -> apply_stf (cmd/common.rs:18-22)
 __global__ __launch_bounds__(256) void stf_u8_tx_kernel(const float *__restrict__ in, int64_t n, const StfTx *__restrict__ tx,
-                                                        unsigned char *__restrict__ out) {
+                                                        unsigned char *__restrict__ out, int vec) {
     const StfTx t = *tx;
-    const int64_t n4 = n >> 2;
+    const int64_t n4 = vec ? (n >> 2) : 0;
     const int64_t stride = (int64_t)gridDim.x * 256;
     const float4 *in4 = reinterpret_cast<const float4 *>(in);
     uchar4 *out4 = reinterpret_cast<uchar4 *>(out);
@@ -53,14 +53,11 @@ __global__ __launch_bounds__(256) void stf_u8_tx_kernel(const float *__restrict_
         r.w = to_u8(v.w, t);
         out4[i] = r;
     }
-    if (blockIdx.x == 0) {
-        const int64_t i = (n4 << 2) + threadIdx.x;
-        if (i < n) out[i] = to_u8(in[i], t);
-    }
+    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) out[i] = to_u8(in[i], t);
 }
 
-__global__ __launch_bounds__(256) void stf_f32_kernel(const float *in, int64_t n, StfTx t, float *out) {
-    const int64_t n4 = n >> 2;
+__global__ __launch_bounds__(256) void stf_f32_kernel(const float *in, int64_t n, StfTx t, float *out, int vec) {
+    const int64_t n4 = vec ? (n >> 2) : 0;
     const int64_t stride = (int64_t)gridDim.x * 256;
     const float4 *in4 = reinterpret_cast<const float4 *>(in);
     float4 *out4 = reinterpret_cast<float4 *>(out);
@@ -73,10 +70,7 @@ __global__ __launch_bounds__(256) void stf_f32_kernel(const float *in, int64_t n
         r.w = to_f32(v.w, t);
         out4[i] = r;
     }
-    if (blockIdx.x == 0) {
-        const int64_t i = (n4 << 2) + threadIdx.x;
-        if (i < n) out[i] = to_f32(in[i], t);
-    }
+    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) out[i] = to_f32(in[i], t);
 }
 
 // the streaming ceiling probe behind bench.py's `measured_copy_GBs`: four 16-byte loads in flight per lane (a workgroup moves 16 KiB
@@ -113,16 +107,17 @@ int stream_grid(ab_ctx *ctx, int64_t n4) {
 int ab_stf_u8_device(ab_ctx *ctx, const float *in, int64_t n, const ab_stf_params *p, const ab_image_stats *st,
                      uint8_t *out) {
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    AB_CHECK(ctx, ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 3) == 0, "apply_stf: planes must be 16-byte aligned");
-    hipLaunchKernelGGL(stf_u8_kernel, dim3(stream_grid(ctx, n >> 2)), dim3(256), 0, ctx->stream, in, n, make_tx(p, st), out);
+    const int vec = ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 3) == 0;
+    hipLaunchKernelGGL(stf_u8_kernel, dim3(stream_grid(ctx, vec ? (n >> 2) : n)), dim3(256), 0, ctx->stream, in, n, make_tx(p, st), out, vec);
     AB_HIP(ctx, hipGetLastError());
     return AB_OK;
 }
 
 int ab_stf_u8_device_tx(ab_ctx *ctx, const float *in, int64_t n, const void *tx_dev, uint8_t *out) {
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    AB_CHECK(ctx, ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 3) == 0, "apply_stf: planes must be 16-byte aligned");
-    hipLaunchKernelGGL(stf_u8_tx_kernel, dim3(stream_grid(ctx, n >> 2)), dim3(256), 0, ctx->stream, in, n, (const StfTx *)tx_dev, out);
+    const int vec = ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 3) == 0;
+    hipLaunchKernelGGL(stf_u8_tx_kernel, dim3(stream_grid(ctx, vec ? (n >> 2) : n)), dim3(256), 0, ctx->stream, in, n, (const StfTx *)tx_dev, out,
+                       vec);
     AB_HIP(ctx, hipGetLastError());
     return AB_OK;
 }
@@ -130,8 +125,8 @@ int ab_stf_u8_device_tx(ab_ctx *ctx, const float *in, int64_t n, const void *tx_
 int ab_stf_f32_device(ab_ctx *ctx, const float *in, int64_t n, const ab_stf_params *p, const ab_image_stats *st,
                       float *out) {
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    AB_CHECK(ctx, ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0, "apply_stf: planes must be 16-byte aligned");
-    hipLaunchKernelGGL(stf_f32_kernel, dim3(stream_grid(ctx, n >> 2)), dim3(256), 0, ctx->stream, in, n, make_tx(p, st), out);
+    const int vec = (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
+    hipLaunchKernelGGL(stf_f32_kernel, dim3(stream_grid(ctx, vec ? (n >> 2) : n)), dim3(256), 0, ctx->stream, in, n, make_tx(p, st), out, vec);
     AB_HIP(ctx, hipGetLastError());
     return AB_OK;
 }

@@ -314,7 +314,9 @@ typedef struct { double shadow, midtone, highlight; } ab_stf_params;        /* t
 typedef struct { double target_bg, shadow_k; } ab_auto_stf_config;          /* types/image.rs:52-65 */
 /* auto_stf (stf.rs:13-39) -- host scalar maths, kept in the library so callers get one ABI */
 AB_API int ab_auto_stf(const ab_image_stats *stats, const ab_auto_stf_config *cfg, ab_stf_params *out);
-/* apply_stf -> Vec<u8> (stf.rs:89-102) */
+/* apply_stf -> Vec<u8> (stf.rs:89-102).  Device planes need no alignment beyond their element's: any 4-byte aligned f32 plane and
+ * any u8 pointer are accepted, here, in ab_apply_stf_f32 and in ab_auto_stretch_preview (16-byte aligned f32 planes and 4-byte
+ * aligned u8 planes take the wide accesses, the rest is read and written pixel by pixel -- the same bytes either way). */
 AB_API int ab_apply_stf_u8(ab_ctx *ctx, const ab_plane *img, const ab_stf_params *p, const ab_image_stats *st,
                            uint8_t *out, int32_t out_on_device);
 /* apply_stf_f32 (stf.rs:104-120); out may alias img.data (apply_stf_inplace, stf.rs:147-155) */
