@@ -254,6 +254,10 @@ class CubeStatsC(C.Structure):  # GlobalCubeStats (core/cube/eager.rs:160-166)
     _fields_ = [("median", C.c_float), ("sigma", C.c_float), ("low", C.c_float), ("high", C.c_float)]
 
 
+class AsinhStatsC(C.Structure):  # ab_asinh_stats: what asinh_normalize_simd takes from the valid pixels (math/simd.rs:163-180)
+    _fields_ = [("median", C.c_float), ("sigma", C.c_float), ("low", C.c_float), ("high", C.c_float), ("valid_count", C.c_uint64)]
+
+
 class DrizzleConfigC(C.Structure):  # DrizzleConfig (types/stacking.rs) + the affine estimate's num_threads
     _fields_ = [("scale", C.c_double), ("pixfrac", C.c_double), ("kernel", C.c_int32), ("sigma_low", C.c_float), ("sigma_high", C.c_float),
                 ("sigma_iterations", C.c_size_t), ("align", C.c_int32), ("alignment_method", C.c_int32), ("num_threads", C.c_int32)]
@@ -508,6 +512,13 @@ def lib() -> C.CDLL:
     L.ab_cube_normalize_frame.argtypes = [vp, pp, csp, pmp]
     L.ab_cube_export_frames.argtypes = [vp, cp, csp, C.c_int64, vp, C.c_int32, i64p]
     L.ab_cube_extract_spectrum.argtypes = [vp, cp, C.c_int64, C.c_int64, vp, C.c_int32]
+    asp = C.POINTER(AsinhStatsC)
+    L.ab_asinh_preview_stats.argtypes = [vp, pp, asp]
+    L.ab_asinh_normalize_with_stats.argtypes = [vp, pp, asp, C.c_int32, pmp]
+    L.ab_robust_asinh_preview.argtypes = [vp, pp, C.c_int32, pmp, asp]
+    L.ab_render_asinh_preview.argtypes = [vp, pp, C.c_int32, vp, C.c_int32, asp]
+    L.ab_render_grayscale.argtypes = [vp, pp, C.c_int32, vp, C.c_int32, f32p, f32p]
+    L.ab_render_stretched.argtypes = [vp, pp, C.c_int32, vp, C.c_int32]
     L.ab_drizzle_output_dims.argtypes = [pp, C.c_size_t, C.POINTER(DrizzleConfigC), i64p, i64p, i64p, i64p]
     L.ab_drizzle_frames.argtypes = [vp, pp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(DrizzleConfigC), pp, pp, C.POINTER(DrizzleResultC)]
     L.ab_drizzle_stack.argtypes = [vp, pp, C.c_size_t, C.POINTER(DrizzleConfigC), pp, pp, C.POINTER(C.c_double), C.POINTER(DrizzleResultC)]

@@ -164,6 +164,18 @@ class GlobalCubeStats:  # core/cube/eager.rs:160-166
 CUBE_VALID_NONZERO, CUBE_VALID_ABOVE_PADDING = 0, 1  # ab_cube_valid_rule: the eager path's rule, the lazy path's
 
 
+@dataclass
+class AsinhStats:  # what asinh_normalize_simd takes from the valid pixels (math/simd.rs:163-180)
+    median: float
+    sigma: float
+    low: float
+    high: float
+    valid_count: int
+
+
+ASINH_ROUTE_AVX2, ASINH_ROUTE_SCALAR = 0, 1  # ab_asinh_route: the reference's AVX2 route (+ its scalar remainder), its scalar loop
+
+
 def cube_streaming_step(depth: int) -> int:
     """The frame stride of compute_global_stats_streaming (core/cube/lazy.rs:334-335).  Host-only."""
     return int(_lib.lib().ab_cube_streaming_step(int(depth)))
@@ -2027,6 +2039,92 @@ class Context:
             assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == pc.depth
             ptr, on_dev = out.ctypes.data, 0
         self._check(self._L.ab_cube_extract_spectrum(self._h, C.byref(pc), int(y), int(x), C.c_void_p(ptr), on_dev))
+        return out
+
+    # ---- render_asinh_and_save (cmd/common.rs:242-261), infra/render/grayscale.rs ------------------------------
+    @staticmethod
+    def _asinh_stats_c(stats):
+        if isinstance(stats, AsinhStats):
+            stats = (stats.median, stats.sigma, stats.low, stats.high, stats.valid_count)
+        return _lib.AsinhStatsC(*[float(np.float32(v)) for v in stats[:4]], int(stats[4]))
+
+    @staticmethod
+    def _asinh_stats(st):
+        return AsinhStats(st.median, st.sigma, st.low, st.high, int(st.valid_count))
+
+    def _samples_out(self, image, rows, cols, bits, out):
+        """(array or tensor, pointer, on_device) of a renderer's output: uint8 (rows, cols), or (rows, cols, 2) big-endian pairs for
+        16 bits; of the image's kind unless `out` is given"""
+        per = 2 if bits == 16 else 1   # (any other depth is the library's AB_ERR_INVALID)
+        shape = (rows, cols, 2) if per == 2 else (rows, cols)
+        if out is None:
+            dev = _is_torch(image) and image.is_cuda
+            out = torch.empty(shape, dtype=torch.uint8, device=image.device) if dev else np.empty(shape, np.uint8)
+        if _is_torch(out):
+            ok = out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == rows * cols * per
+            ptr, on_dev = out.data_ptr(), 1
+        else:
+            ok = out.dtype == np.uint8 and out.flags.c_contiguous and out.size == rows * cols * per
+            ptr, on_dev = out.ctypes.data, 0
+        if not ok:
+            raise AstroBurstError(_lib.AB_ERR_INVALID, f"the output must be contiguous uint8 of {rows * cols * per} bytes")
+        return out, ptr, on_dev
+
+    def asinh_preview_stats(self, image) -> AsinhStats:
+        """The statistics of asinh_normalize_simd (math/simd.rs:163-180) over the pixels with is_finite() && v > 1e-7: the f32 median
+        (mean of the two middle values for an even count), sigma = max(MAD * 1.4826f32, 1e-10), the 1 % and 99.9 % order statistics;
+        bit for bit.  No valid pixel: all zero."""
+        keep = []
+        pi = self._plane(image, keep)
+        st = _lib.AsinhStatsC()
+        self._check(self._L.ab_asinh_preview_stats(self._h, C.byref(pi), C.byref(st)))
+        return self._asinh_stats(st)
+
+    def asinh_normalize_with_stats(self, image, stats, route=ASINH_ROUTE_AVX2, out=None):
+        """The map of asinh_normalize_simd alone (simd.rs:115-158 / :203-211) with the caller's statistics; `out` may be `image`
+        itself.  Of the image's kind."""
+        st = self._asinh_stats_c(stats)
+        return self._unary(self._L.ab_asinh_normalize_with_stats, image, out, C.byref(st), int(route))
+
+    def robust_asinh_preview(self, image, route=ASINH_ROUTE_AVX2, out=None, want_stats=False):
+        """robust_asinh_preview = asinh_normalize_simd (math/simd.rs:160-214): the AVX2 route bit for bit, the scalar route bit for
+        bit below |x| = 0.5 and the f32 rounding of the f64 log above.  Of the image's kind; with want_stats also the AsinhStats."""
+        keep = []
+        pi = self._plane(image, keep)
+        if out is None:
+            out = self._new_like(image, pi.rows, pi.cols)
+        po = self._out_plane(out, keep, pi.rows, pi.cols)
+        st = _lib.AsinhStatsC()
+        self._check(self._L.ab_robust_asinh_preview(self._h, C.byref(pi), int(route), C.byref(po), C.byref(st)))
+        return (out, self._asinh_stats(st)) if want_stats else out
+
+    def render_asinh_preview(self, image, route=ASINH_ROUTE_AVX2, out=None, want_stats=False):
+        """render_asinh_and_save (cmd/common.rs:242-261) up to the PNG encoder -> uint8 (rows, cols): render_grayscale of the robust
+        asinh preview in two launches after the statistics, the f32 preview never written.  Of the image's kind."""
+        keep = []
+        pi = self._plane(image, keep)
+        out, ptr, on_dev = self._samples_out(image, int(pi.rows), int(pi.cols), 8, out)
+        st = _lib.AsinhStatsC()
+        self._check(self._L.ab_render_asinh_preview(self._h, C.byref(pi), int(route), C.c_void_p(ptr), on_dev, C.byref(st)))
+        return (out, self._asinh_stats(st)) if want_stats else out
+
+    def render_grayscale(self, image, bits=8, out=None, want_range=False):
+        """render_grayscale / render_grayscale_16bit (infra/render/grayscale.rs:10-50) up to the PNG encoder -> uint8 (rows, cols), or
+        (rows, cols, 2) big-endian pairs for bits = 16 (`.view('>u2')`); with want_range also (min, max) of the finite pixels"""
+        keep = []
+        pi = self._plane(image, keep)
+        out, ptr, on_dev = self._samples_out(image, int(pi.rows), int(pi.cols), int(bits), out)
+        mn, mx = C.c_float(0), C.c_float(0)
+        self._check(self._L.ab_render_grayscale(self._h, C.byref(pi), int(bits), C.c_void_p(ptr), on_dev,
+                                                C.byref(mn) if want_range else None, C.byref(mx) if want_range else None))
+        return (out, mn.value, mx.value) if want_range else out
+
+    def render_stretched(self, image, bits=8, out=None):
+        """render_stretched_8bit / _16bit (grayscale.rs:52-74): (v.clamp(0, 1) * top) as uN, no validity test; bytes as above"""
+        keep = []
+        pi = self._plane(image, keep)
+        out, ptr, on_dev = self._samples_out(image, int(pi.rows), int(pi.cols), int(bits), out)
+        self._check(self._L.ab_render_stretched(self._h, C.byref(pi), int(bits), C.c_void_p(ptr), on_dev))
         return out
 
     # ---- core/stacking/drizzle.rs -------------------------------------------------------------------------

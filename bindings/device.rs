@@ -99,6 +99,15 @@ impl DevicePlane {
     pub fn as_ptr(&self) -> *const f32 {
         self.ptr as *const f32
     }
+    /// render_asinh_and_save (cmd/common.rs:242-261) of a plane that stays in HBM: the L8 bytes for write_png_l8 -- one byte per
+    /// pixel crosses PCIe, the f32 plane is not downloaded (the AVX2 route: what the reference's published hardware computes)
+    pub fn render_asinh_preview(&self, hip: &Hip) -> Result<Vec<u8>> {
+        let mut out = vec![0u8; self.rows * self.cols];
+        hip.check(unsafe {
+            sys::ab_render_asinh_preview(hip.ctx, &self.ab(), sys::AB_ASINH_ROUTE_AVX2 as i32, out.as_mut_ptr(), 0, std::ptr::null_mut())
+        })?;
+        Ok(out)
+    }
 }
 impl Drop for DevicePlane {
     fn drop(&mut self) {

@@ -1141,6 +1141,93 @@ pub fn extract_spectrum(hip: &Hip, cube: &Array3<f32>, y: usize, x: usize) -> Re
     Ok(out)
 }
 
+// ---- render_asinh_and_save (cmd/common.rs:242-261), math/simd.rs:160-214, infra/render/grayscale.rs -------------------------------------------------------------
+/// The two routes of asinh_normalize_simd: what an x86-64 host with AVX2 runs (the default: the reference's published hardware), and
+/// the scalar loop every other host runs
+#[derive(Clone, Copy, PartialEq, Eq, Debug)]
+pub enum AsinhRoute {
+    Avx2 = 0,
+    Scalar = 1,
+}
+/// what asinh_normalize_simd takes from the valid pixels (simd.rs:163-180)
+#[derive(Clone, Copy, Debug)]
+pub struct AsinhStats {
+    pub median: f32,
+    pub sigma: f32,
+    pub low: f32,
+    pub high: f32,
+    pub valid_count: u64,
+}
+fn asinh_stats_zeroed() -> sys::ab_asinh_stats {
+    sys::ab_asinh_stats { median: 0.0, sigma: 0.0, low: 0.0, high: 0.0, valid_count: 0 }
+}
+fn asinh_stats_from(st: &sys::ab_asinh_stats) -> AsinhStats {
+    AsinhStats { median: st.median, sigma: st.sigma, low: st.low, high: st.high, valid_count: st.valid_count }
+}
+/// the statistics alone: median, MAD sigma, the 1 % and 99.9 % order statistics; bit for bit
+pub fn asinh_preview_stats(hip: &Hip, data: &impl PlaneSrc) -> Result<AsinhStats> {
+    let mut st = asinh_stats_zeroed();
+    hip.check(unsafe { sys::ab_asinh_preview_stats(hip.ctx, &data.ab(), &mut st) })?;
+    Ok(asinh_stats_from(&st))
+}
+/// the map alone, with the caller's statistics
+pub fn asinh_normalize_with_stats(hip: &Hip, data: &impl PlaneSrc, stats: &AsinhStats, route: AsinhRoute) -> Result<Array2<f32>> {
+    let st = sys::ab_asinh_stats { median: stats.median, sigma: stats.sigma, low: stats.low, high: stats.high, valid_count: stats.valid_count };
+    let mut out = Array2::<f32>::zeros(data.dims());
+    let mut po = out.ab_mut();
+    hip.check(unsafe { sys::ab_asinh_normalize_with_stats(hip.ctx, &data.ab(), &st, route as i32, &mut po) })?;
+    Ok(out)
+}
+/// asinh_normalize_simd under either route
+pub fn robust_asinh_preview_route(hip: &Hip, data: &impl PlaneSrc, route: AsinhRoute) -> Result<Array2<f32>> {
+    let mut out = Array2::<f32>::zeros(data.dims());
+    let mut po = out.ab_mut();
+    hip.check(unsafe { sys::ab_robust_asinh_preview(hip.ctx, &data.ab(), route as i32, &mut po, std::ptr::null_mut()) })?;
+    Ok(out)
+}
+/// drop-in for robust_asinh_preview (core/imaging/normalize.rs = math::simd::asinh_normalize_simd, simd.rs:160-214), the AVX2 route:
+/// bit for bit
+pub fn robust_asinh_preview(hip: &Hip, data: &impl PlaneSrc) -> Result<Array2<f32>> {
+    robust_asinh_preview_route(hip, data, AsinhRoute::Avx2)
+}
+/// render_asinh_and_save (cmd/common.rs:242-261) up to the encoder: the L8 bytes of render_grayscale(robust_asinh_preview(data)), the
+/// f32 preview never written; the caller hands them to write_png_l8.  `data` is typically the DevicePlane a stack or a collapse left.
+pub fn render_asinh_preview(hip: &Hip, data: &impl PlaneSrc, route: AsinhRoute) -> Result<Vec<u8>> {
+    let (r, c) = data.dims();
+    let mut out = vec![0u8; r * c];
+    hip.check(unsafe { sys::ab_render_asinh_preview(hip.ctx, &data.ab(), route as i32, out.as_mut_ptr(), 0, std::ptr::null_mut()) })?;
+    Ok(out)
+}
+fn render_bytes(hip: &Hip, data: &impl PlaneSrc, bits: i32, stretched: bool) -> Result<Vec<u8>> {
+    let (r, c) = data.dims();
+    let mut out = vec![0u8; r * c * (bits as usize / 8)];
+    let p = out.as_mut_ptr() as *mut c_void;
+    hip.check(unsafe {
+        if stretched {
+            sys::ab_render_stretched(hip.ctx, &data.ab(), bits, p, 0)
+        } else {
+            sys::ab_render_grayscale(hip.ctx, &data.ab(), bits, p, 0, std::ptr::null_mut(), std::ptr::null_mut())
+        }
+    })?;
+    Ok(out)
+}
+/// drop-in for render_grayscale (grayscale.rs:10-29) up to write_png_l8: the L8 bytes
+pub fn render_grayscale(hip: &Hip, data: &impl PlaneSrc) -> Result<Vec<u8>> {
+    render_bytes(hip, data, 8, false)
+}
+/// drop-in for render_grayscale_16bit (grayscale.rs:31-50) up to the encoder: the big-endian byte pairs write_png_l16 builds
+pub fn render_grayscale_16bit(hip: &Hip, data: &impl PlaneSrc) -> Result<Vec<u8>> {
+    render_bytes(hip, data, 16, false)
+}
+/// drop-in for render_stretched_8bit (grayscale.rs:52-62) up to write_png_l8
+pub fn render_stretched_8bit(hip: &Hip, data: &impl PlaneSrc) -> Result<Vec<u8>> {
+    render_bytes(hip, data, 8, true)
+}
+/// drop-in for render_stretched_16bit (grayscale.rs:64-74) up to the encoder: big-endian byte pairs
+pub fn render_stretched_16bit(hip: &Hip, data: &impl PlaneSrc) -> Result<Vec<u8>> {
+    render_bytes(hip, data, 16, true)
+}
+
 // ---- core/stacking/drizzle.rs (calibration.rs:320 drizzle_from_paths, drizzle_rgb_cmd) ----------------------------------------------------------------------
 fn drizzle_cfg(config: &DrizzleConfig) -> sys::ab_drizzle_config {
     sys::ab_drizzle_config {

@@ -955,9 +955,9 @@ AB_API int ab_spectrum_to_u8(ab_ctx *ctx, const ab_plane *spectrum, uint8_t *out
  * released by ab_ctx_trim; AB_ERR_NOMEM when it cannot be had).  Every entry: NULL arguments, depth / rows / cols < 1 or output
  * dims that do not match -> AB_ERR_INVALID; so does depth >= 2^32 or more than 2^40 voxels (per-pixel counts and ranks are u32, as
  * the reference's are).  Cancellation (ab_ctx_request_cancel) is looked at before each pass over the cube;
- * there are no progress ticks (the reference has none here).  The collapsed previews' robust_asinh_preview (math/simd.rs:160-214)
- * is not part of this section: the host keeps it, with the PNG encoder, the mmap, the header parsing, classify_spectral_cube,
- * build_wavelength_axis and the LRU frame cache. */
+ * there are no progress ticks (the reference has none here).  The collapsed previews (eager.rs:288-295, lazy.rs:388-397) are a
+ * collapse into a device plane followed by ab_render_asinh_preview of that plane (the next section).  The host keeps the PNG
+ * encoder, the mmap, the header parsing, classify_spectral_cube, build_wavelength_axis and the LRU frame cache. */
 typedef struct {
     const float *data;
     int64_t depth, rows, cols;
@@ -1014,6 +1014,78 @@ AB_API int ab_cube_export_frames(ab_ctx *ctx, const ab_cube *cube, const ab_cube
  * for a device cube with a device output.  A host cube is read where it lies (nothing is uploaded): its column is gathered on
  * the host, and with a device output the call has synchronised the stream and finished the copy when it returns. */
 AB_API int ab_cube_extract_spectrum(ab_ctx *ctx, const ab_cube *cube, int64_t y, int64_t x, float *out, int32_t out_on_device);
+
+/* ---- the robust asinh preview and the byte renderers: render_asinh_and_save (cmd/common.rs:242-261), infra/render/grayscale.rs -- */
+/* robust_asinh_preview = math::simd::asinh_normalize_simd (math/simd.rs:160-214), then render_grayscale (grayscale.rs:10-29): how
+ * the stack, calibrate and resample commands and both cube commands finish; the export command's four renderers (grayscale.rs:10-74,
+ * cmd/export/mod.rs:233-240).  Everything stops at the PNG encoder.  Pixels are indexed flat, i = y * cols + x, n = rows * cols.
+ * Every entry: a NULL argument (the ones marked nullable excepted), rows / cols < 1, an output whose dims do not match, a route
+ * outside ab_asinh_route or bits outside {8, 16} -> AB_ERR_INVALID.  Planes host or device; a device plane at any float-aligned
+ * address is served (the kernels peel to their 16-byte groups themselves).
+ *
+ * Statistics (simd.rs:163-180) over the m pixels with is_finite() && v > 1e-7f, sorted into s:
+ *   median = median_f32_mut (math/median.rs:46-63): s[m / 2], or for even m (s[m / 2 - 1] + s[m / 2]) / 2.0 in f32 (NOT the cube's
+ *            upper median);
+ *   sigma  = max(median_f32_mut(|v - median| in f32) * 1.4826f32, 1e-10f32);
+ *   low    = s[(m as f64 * 0.01) as usize], high = s[min((m as f64 * 0.999) as usize, m - 1)].
+ * All four bit for bit: exact order statistics by radix select, no sort.  m == 0: all four are 0, and the preview is a copy of the
+ * input (simd.rs:165-167).
+ *
+ * The map, with isa = 10f32 / sigma.  The reference has two routes; both are here, selected by `route`:
+ *   AB_ASINH_ROUTE_AVX2 (simd.rs:115-158, what an x86-64 host with AVX2 runs).  For i < 8 * (n / 8), counted from flat index 0:
+ *     valid = v == v && v > 1e-7f (so +inf IS valid; NaN and -inf are not); clamped = min(max(v, low), high); scaled = (clamped -
+ *     median) * isa; a = |scaled|; inner = a + sqrt(a * a + 1); the result is fast_log_avx2(inner) (simd.rs:28-84: mantissa | 0x3F000000,
+ *     e = exponent field - 0x7E, the doubling below FRAC_1_SQRT_2, the nine-coefficient Horner chain with separate mul and add,
+ *     (f - 0.5 f^2) + f^3 r, e * LN_2 + that) with scaled's sign bit OR-ed in; an invalid pixel gives 0.  Every operation is f32 and
+ *     unfused, the sqrt correctly rounded, subnormals kept: BIT FOR BIT for every input, quirks included (a * a overflowing gives
+ *     +-128 * LN_2 = +-88.72284; |scaled| below 2^-24 gives +-0 because inner rounds to 1).  The last n % 8 pixels take the
+ *     scalar route's formula.
+ *   AB_ASINH_ROUTE_SCALAR (simd.rs:203-211 with fast_asinh_scalar :9-18, what every pixel takes on a host without AVX2, e.g. aarch64).
+ *     valid = is_finite() && v > 1e-7f (+inf is NOT valid); x = isa * (clamp(v, low, high) - median); for |x| < 0.5 the result is
+ *     x * (1 - x2 * (1f32 / 6f32 - (x2 * 3) / 40)) with x2 = x * x, in f32 in that order: bit for bit.  Otherwise sign * ln(|x| +
+ *     sqrt(|x| * |x| + 1)), the argument formed in f32.  ln is the platform libm's logf, whose bits are not a target: the result is
+ *     DEFINED (as ab_cube_normalize_frame defines its asinh) as the f32 rounding of the f64 log of that f32 argument, computed in f64
+ *     on the device.  An overflowing |x|^2 gives +-inf, as in the reference.
+ * These are the two places where the contract is a definition and not a particular host's bits: the scalar route's ln, and
+ * infinities in find_minmax (below). */
+typedef enum {
+    AB_ASINH_ROUTE_AVX2 = 0,  /* normalize_chunk_avx2 + the scalar remainder */
+    AB_ASINH_ROUTE_SCALAR = 1 /* the scalar loop for every pixel */
+} ab_asinh_route;
+typedef struct {
+    float median, sigma, low, high;
+    uint64_t valid_count; /* m */
+} ab_asinh_stats;
+/* The statistics above.  One select request for the ranks m / 2 - 1 (even m), m / 2, low and high, which descend together, then one
+ * select of the deviations.  Not asynchronous: the histograms are read back. */
+AB_API int ab_asinh_preview_stats(ab_ctx *ctx, const ab_plane *img, ab_asinh_stats *out);
+/* The map alone, with the caller's statistics (isa = 10f32 / stats->sigma).  A NaN statistic or !(low <= high) -> AB_ERR_INVALID (the
+ * scalar route's f32::clamp would panic).  stats->valid_count == 0 copies the input.  out: img's dims; exactly img (in place), or
+ * not overlapping it.  Asynchronous for device planes. */
+AB_API int ab_asinh_normalize_with_stats(ab_ctx *ctx, const ab_plane *img, const ab_asinh_stats *stats, int32_t route, ab_plane_mut *out);
+/* asinh_normalize_simd itself: the statistics, then the map (or the copy).  out as above; stats_out nullable. */
+AB_API int ab_robust_asinh_preview(ab_ctx *ctx, const ab_plane *img, int32_t route, ab_plane_mut *out, ab_asinh_stats *stats_out);
+/* render_asinh_and_save up to the PNG encoder: out_u8 (rows * cols bytes, host or device: out_on_device) = render_grayscale's bytes of
+ * robust_asinh_preview(img).  The f32 preview is never written: after the statistics, one launch recomputes the map and reduces
+ * the min / max (an invalid pixel contributes its 0), a second finishes the range, recomputes the map, quantises and stores packed
+ * bytes.  Byte for byte what ab_robust_asinh_preview followed by ab_render_grayscale gives.  valid_count == 0: every byte is 0.
+ * stats_out nullable.  The statistics synchronise; the two launches (and nothing after them) are asynchronous for a device output. */
+AB_API int ab_render_asinh_preview(ab_ctx *ctx, const ab_plane *img, int32_t route, uint8_t *out_u8, int32_t out_on_device,
+                                   ab_asinh_stats *stats_out);
+/* render_grayscale (bits = 8, grayscale.rs:10-29) and render_grayscale_16bit (bits = 16, :31-50).  (min, max) over the pixels with
+ * is_finite(): find_minmax_simd's scalar statement (simd.rs:263-271), the one ab_cube_export_frames cites.  range = max(max - min,
+ * 1e-10), inv = 255f32 / range (65535f32), sample = (is_finite() && v > 1e-7f) ? ((v - min) * inv).clamp(0, top) as u8 / u16 : 0
+ * (`as` truncates and saturates; NaN -> 0).  16-bit samples are written as BIG-ENDIAN byte pairs, which is what write_png_l16 hands
+ * the encoder (:95).  out: rows * cols * bits / 8 bytes, host or device.  min_out / max_out nullable; asking for either synchronises.
+ * With no finite pixel min = f32::MAX and max = f32::MIN = -f32::MAX: max - min is -inf, range is 1e-10, no pixel passes the validity
+ * test and every sample is 0; min_out / max_out receive those two values.
+ * Infinities: the reference's AVX2 find_minmax (simd.rs:274-315) masks with v == v, so it COUNTS +-inf among the first 8 * (n / 8)
+ * values; the range becomes inf, inv 0 (or the difference NaN), and the whole plane renders 0.  Here, as in the scalar statement,
+ * an infinity is skipped.  A plane holding +-inf is therefore outside the bit-for-bit claim against an AVX2 host. */
+AB_API int ab_render_grayscale(ab_ctx *ctx, const ab_plane *img, int32_t bits, void *out, int32_t out_on_device, float *min_out, float *max_out);
+/* render_stretched_8bit / _16bit (grayscale.rs:52-74): (v.clamp(0, 1) * 255f32) as u8 (65535f32, u16; big-endian pairs).  There is no
+ * validity test: NaN -> 0, +inf -> top, -inf -> 0.  One launch; asynchronous for a device plane with a device output. */
+AB_API int ab_render_stretched(ab_ctx *ctx, const ab_plane *img, int32_t bits, void *out, int32_t out_on_device);
 
 /* ---- bench support: a plain float4 device copy, the measured HBM ceiling ---- */
 AB_API int ab_bench_copy(ab_ctx *ctx, const float *src_dev, float *dst_dev, size_t n_floats);
