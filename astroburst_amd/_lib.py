@@ -263,6 +263,24 @@ class DrizzleConfigC(C.Structure):  # DrizzleConfig (types/stacking.rs) + the af
                 ("sigma_iterations", C.c_size_t), ("align", C.c_int32), ("alignment_method", C.c_int32), ("num_threads", C.c_int32)]
 
 
+class RgbExportConfigC(C.Structure):  # ab_rgb_export_config: the STF choice of stretch_and_render (cmd/export/mod.rs:357-409)
+    _fields_ = [("bits", C.c_int32), ("has_stf", C.c_int32), ("stf", StfParamsC * 3)]
+
+
+class RgbExportInfoC(C.Structure):  # ab_rgb_export_info
+    _fields_ = [("rows", C.c_uint64), ("cols", C.c_uint64), ("resampled", C.c_int32), ("stats", ImageStatsC * 3), ("stf", StfParamsC * 3)]
+
+
+class DrizzleRgbConfigC(C.Structure):  # DrizzleRgbConfig (types/compose.rs) without its DrizzleConfig
+    _fields_ = [("white_balance", C.c_int32), ("wb_manual", C.c_double * 3), ("auto_stretch", C.c_int32), ("linked_stf", C.c_int32),
+                ("has_scnr", C.c_int32), ("scnr", ScnrConfigC)]
+
+
+class ProcessedDrizzleRgbInfoC(C.Structure):  # the scalars of ProcessedDrizzleRgb (drizzle_rgb.rs:24-39)
+    _fields_ = [("rows", C.c_uint64), ("cols", C.c_uint64), ("wb", C.c_double * 3), ("stf", StfParamsC * 3), ("chan_stats", (C.c_double * 4) * 3),
+                ("stats_wb", ImageStatsC * 3), ("scnr_applied", C.c_int32)]
+
+
 class DrizzleResultC(C.Structure):  # DrizzleResult's scalars (drizzle.rs:335-344)
     _fields_ = [("frame_count", C.c_size_t), ("output_scale", C.c_double), ("in_rows", C.c_int64), ("in_cols", C.c_int64),
                 ("out_rows", C.c_int64), ("out_cols", C.c_int64), ("rejected_pixels", C.c_uint64)]
@@ -519,6 +537,14 @@ def lib() -> C.CDLL:
     L.ab_render_asinh_preview.argtypes = [vp, pp, C.c_int32, vp, C.c_int32, asp]
     L.ab_render_grayscale.argtypes = [vp, pp, C.c_int32, vp, C.c_int32, f32p, f32p]
     L.ab_render_stretched.argtypes = [vp, pp, C.c_int32, vp, C.c_int32]
+    stp, isp = C.POINTER(StfParamsC), C.POINTER(ImageStatsC)
+    L.ab_rgb_packed_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]
+    L.ab_render_rgb.argtypes = [vp, pp, pp, pp, C.c_int32, vp, C.c_int32]
+    L.ab_render_rgb_stf.argtypes = [vp, pp, pp, pp, stp, isp, C.c_int32, vp, C.c_int32]
+    L.ab_export_rgb.argtypes = [vp, pp, pp, pp, C.POINTER(RgbExportConfigC), vp, C.c_int32, C.POINTER(RgbExportInfoC)]
+    L.ab_process_drizzle_rgb.argtypes = [vp, pp, pp, pp, C.POINTER(DrizzleRgbConfigC), pmp, pmp, vp, C.c_int32, C.POINTER(ProcessedDrizzleRgbInfoC)]
+    L.ab_drizzle_rgb.argtypes = [vp, pp, C.c_size_t, pp, C.c_size_t, pp, C.c_size_t, C.POINTER(DrizzleConfigC), C.POINTER(DrizzleRgbConfigC), pmp, vp,
+                                 C.c_int32, C.POINTER(DrizzleResultC), C.POINTER(ProcessedDrizzleRgbInfoC)]
     L.ab_drizzle_output_dims.argtypes = [pp, C.c_size_t, C.POINTER(DrizzleConfigC), i64p, i64p, i64p, i64p]
     L.ab_drizzle_frames.argtypes = [vp, pp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(DrizzleConfigC), pp, pp, C.POINTER(DrizzleResultC)]
     L.ab_drizzle_stack.argtypes = [vp, pp, C.c_size_t, C.POINTER(DrizzleConfigC), pp, pp, C.POINTER(C.c_double), C.POINTER(DrizzleResultC)]

@@ -176,6 +176,47 @@ class AsinhStats:  # what asinh_normalize_simd takes from the valid pixels (math
 ASINH_ROUTE_AVX2, ASINH_ROUTE_SCALAR = 0, 1  # ab_asinh_route: the reference's AVX2 route (+ its scalar remainder), its scalar loop
 
 
+RGB_PACK_8, RGB_PACK_8_ROUND, RGB_PACK_16BE = 0, 1, 2  # ab_rgb_pack: render_rgb's truncation, drizzle_rgb's rounding, render_rgb_16bit's big-endian pairs
+
+
+def rgb_packed_bytes(rows: int, cols: int, pack: int = RGB_PACK_8) -> int:
+    """The size of an interleaved RGB buffer: rows * cols * 3, twice that for RGB_PACK_16BE.  Host-only."""
+    n = C.c_size_t(0)
+    rc = _lib.lib().ab_rgb_packed_bytes(int(rows), int(cols), int(pack), C.byref(n))
+    if rc != _lib.AB_OK:
+        raise AstroBurstError(rc, f"rgb_packed_bytes: bad dims {rows} x {cols} or packer {pack}")
+    return int(n.value)
+
+
+@dataclass
+class RgbExportInfo:  # what stretch_and_render derived on its way (cmd/export/mod.rs:357-409)
+    rows: int
+    cols: int
+    resampled: bool
+    stats: tuple  # 3 x ImageStats
+    stf: tuple    # 3 x StfParams
+
+
+@dataclass
+class ProcessedDrizzleRgb:  # drizzle_rgb.rs:24-39 (+ the bytes of :232-248 and the statistics the stretch used)
+    stretched: tuple   # (r, g, b) or None
+    wb: tuple          # (r_wb, g_wb, b_wb) or None
+    rgb8: object       # uint8 (rows, cols, 3) or None
+    rows: int
+    cols: int
+    wb_factors: tuple
+    stf: tuple         # 3 x StfParams
+    chan_stats: tuple  # 3 x (min, max, median, mean) before white balance
+    stats_wb: tuple    # 3 x ImageStats
+    scnr_applied: bool
+
+
+@dataclass
+class DrizzleRgbResult:  # types/compose.rs DrizzleRgbResult without its paths
+    processed: ProcessedDrizzleRgb
+    channels: tuple    # 3 x (frame_count, output_scale, in_dims, out_dims, rejected_pixels), None for a channel that is not there
+
+
 def cube_streaming_step(depth: int) -> int:
     """The frame stride of compute_global_stats_streaming (core/cube/lazy.rs:334-335).  Host-only."""
     return int(_lib.lib().ab_cube_streaming_step(int(depth)))
@@ -2126,6 +2167,145 @@ class Context:
         out, ptr, on_dev = self._samples_out(image, int(pi.rows), int(pi.cols), int(bits), out)
         self._check(self._L.ab_render_stretched(self._h, C.byref(pi), int(bits), C.c_void_p(ptr), on_dev))
         return out
+
+    # ---- infra/render/rgb.rs, cmd/export/mod.rs, core/compose/drizzle_rgb.rs ------------------------------------
+    rgb_packed_bytes = staticmethod(rgb_packed_bytes)
+
+    def _rgb_bytes_out(self, like, rows, cols, pack, out):
+        """(array or tensor, pointer, on_device) of an interleaved RGB output: uint8 (rows, cols, 3), or (rows, cols, 6) for
+        RGB_PACK_16BE (`.view('>u2')` gives the samples); of `like`'s kind unless `out` is given"""
+        per = 6 if pack == RGB_PACK_16BE else 3   # (a packer outside the enum is the library's AB_ERR_INVALID)
+        if out is None:
+            dev = _is_torch(like) and like.is_cuda
+            out = torch.empty((rows, cols, per), dtype=torch.uint8, device=like.device) if dev else np.empty((rows, cols, per), np.uint8)
+        if _is_torch(out):
+            ok = out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == rows * cols * per
+            ptr, on_dev = out.data_ptr(), 1
+        else:
+            ok = out.dtype == np.uint8 and out.flags.c_contiguous and out.size == rows * cols * per
+            ptr, on_dev = out.ctypes.data, 0
+        if not ok:
+            raise AstroBurstError(_lib.AB_ERR_INVALID, f"the output must be contiguous uint8 of {rows * cols * per} bytes")
+        return out, C.c_void_p(ptr), on_dev
+
+    def render_rgb(self, r, g, b, pack=RGB_PACK_8, out=None):
+        """render_rgb (rgb.rs:7-47) at full size, render_rgb_16bit (:49-91) or the drizzle packer (drizzle_rgb.rs:232-248) of three
+        stretched planes, up to the encoder -> uint8 (rows, cols, 3) or (rows, cols, 6); of r's kind"""
+        keep = []
+        pr, pg, pb = (self._plane(x, keep) for x in (r, g, b))
+        out, ptr, dev = self._rgb_bytes_out(r, int(pr.rows), int(pr.cols), pack, out)
+        self._check(self._L.ab_render_rgb(self._h, C.byref(pr), C.byref(pg), C.byref(pb), int(pack), ptr, dev))
+        return out
+
+    def render_rgb_stf(self, r, g, b, stf, stats, pack=RGB_PACK_8, out=None):
+        """apply_stf_f32 x 3 and the packer in one launch (export/mod.rs:189-207, :321-328, :362-382); stf, stats: three each"""
+        keep = []
+        pr, pg, pb = (self._plane(x, keep) for x in (r, g, b))
+        out, ptr, dev = self._rgb_bytes_out(r, int(pr.rows), int(pr.cols), pack, out)
+        p, s = self._stf3(stf, stats)
+        self._check(self._L.ab_render_rgb_stf(self._h, C.byref(pr), C.byref(pg), C.byref(pb), p, s, int(pack), ptr, dev))
+        return out
+
+    def export_rgb(self, r, g, b, bits=16, stf=None, out=None):
+        """stretch_and_render (cmd/export/mod.rs:357-409): resample to the largest dims where they differ, statistics per channel, the
+        explicit STF (stf = three StfParams) or compute_linked_stf of the three statistics, render_rgb / render_rgb_16bit
+        -> (bytes, RgbExportInfo)"""
+        keep = []
+        planes = [self._plane(x, keep) for x in (r, g, b)]
+        rows, cols = max(int(p.rows) for p in planes), max(int(p.cols) for p in planes)
+        cfg = _lib.RgbExportConfigC()
+        cfg.bits = int(bits)
+        if stf is not None:
+            cfg.has_stf = 1
+            for c, p in enumerate(stf):
+                cfg.stf[c] = StfParamsC(p.shadow, p.midtone, p.highlight)
+        out, ptr, dev = self._rgb_bytes_out(r, rows, cols, RGB_PACK_16BE if int(bits) == 16 else RGB_PACK_8, out)
+        info = _lib.RgbExportInfoC()
+        self._check(self._L.ab_export_rgb(self._h, *[C.byref(p) for p in planes], C.byref(cfg), ptr, dev, C.byref(info)))
+        return out, RgbExportInfo(int(info.rows), int(info.cols), bool(info.resampled), tuple(self._stats_out(s) for s in info.stats),
+                                  tuple(StfParams(p.shadow, p.midtone, p.highlight) for p in info.stf))
+
+    @staticmethod
+    def _drizzle_rgb_config(white_balance, auto_stretch, linked_stf, scnr):
+        cfg = _lib.DrizzleRgbConfigC()
+        if isinstance(white_balance, str):
+            cfg.white_balance = {"auto": 0, "none": 2}[white_balance]
+        else:
+            cfg.white_balance = 1
+            cfg.wb_manual[:] = [float(v) for v in white_balance]
+        cfg.auto_stretch, cfg.linked_stf = int(bool(auto_stretch)), int(bool(linked_stf))
+        if scnr is not None:
+            cfg.has_scnr = 1
+            m = scnr.get("method", "average")
+            cfg.scnr = _lib.ScnrConfigC(0 if m in ("average", "AverageNeutral", 0) else 1, scnr.get("amount", 1.0),
+                                        int(bool(scnr.get("preserve_luminance", False))))
+        return cfg
+
+    def _plane3(self, like, rows, cols, keep):
+        """three new planes of `like`'s kind and their ab_plane_mut[3]"""
+        arrs = tuple(self._new_like(like, rows, cols) for _ in range(3))
+        return arrs, (Plane * 3)(*[self._out_plane(a, keep, rows, cols) for a in arrs])
+
+    def _processed_drizzle_rgb(self, stretched, wb, rgb8, info):
+        return ProcessedDrizzleRgb(stretched, wb, rgb8, int(info.rows), int(info.cols), tuple(info.wb),
+                                   tuple(StfParams(p.shadow, p.midtone, p.highlight) for p in info.stf), tuple(tuple(row) for row in info.chan_stats),
+                                   tuple(self._stats_out(s) for s in info.stats_wb), bool(info.scnr_applied))
+
+    def process_drizzle_rgb(self, r, g, b, white_balance="auto", auto_stretch=True, linked_stf=False, scnr=None, want_stretched=True,
+                            want_wb=True, want_rgb8=True) -> ProcessedDrizzleRgb:
+        """process_drizzle_rgb (drizzle_rgb.rs:41-145) and the packer of drizzle_rgb (:232-248).  Absent channels are None; the output
+        has the minimum rows and cols of the present ones.  white_balance: "auto" | "none" | (r, g, b); scnr: None or
+        dict(method=, amount=, preserve_luminance=).  Outputs are of the first present channel's kind."""
+        keep = []
+        chans = [None if x is None else self._plane(x, keep) for x in (r, g, b)]
+        present = [p for p in chans if p is not None]
+        first = next((x for x in (r, g, b) if x is not None), None)
+        if first is None:
+            raise AstroBurstError(_lib.AB_ERR_INVALID, "at least one channel must be present")
+        rows, cols = min(int(p.rows) for p in present), min(int(p.cols) for p in present)
+        cfg = self._drizzle_rgb_config(white_balance, auto_stretch, linked_stf, scnr)
+        stretched, ps = self._plane3(first, rows, cols, keep) if want_stretched else (None, None)
+        wb, pw = self._plane3(first, rows, cols, keep) if want_wb else (None, None)
+        rgb8, ptr, dev = self._rgb_bytes_out(first, rows, cols, RGB_PACK_8_ROUND, None) if want_rgb8 else (None, None, 0)
+        info = _lib.ProcessedDrizzleRgbInfoC()
+        self._check(self._L.ab_process_drizzle_rgb(self._h, *[None if p is None else C.byref(p) for p in chans], C.byref(cfg), ps, pw, ptr, dev,
+                                                   C.byref(info)))
+        return self._processed_drizzle_rgb(stretched, wb, rgb8, info)
+
+    def drizzle_rgb(self, r_frames, g_frames, b_frames, scale=2.0, pixfrac=0.7, kernel="square", sigma_low=3.0, sigma_high=3.0,
+                    sigma_iterations=5, align=True, alignment_method="phase_correlation", num_threads=8, white_balance="auto", auto_stretch=True,
+                    linked_stf=False, scnr=None, want_wb=True, want_rgb8=True) -> DrizzleRgbResult:
+        """drizzle_rgb (drizzle_rgb.rs:159-286) up to the PNG / FITS writers: each list of frames (None: no such channel; fewer than two
+        frames: treated as absent) is drizzled into an image that stays on the device, then process_drizzle_rgb."""
+        lists = [r_frames, g_frames, b_frames]
+        given = sum(f is not None for f in lists)
+        if given < 2:
+            raise AstroBurstError(_lib.AB_ERR_INVALID, f"Need at least 2 channels for RGB drizzle (got {given})")
+        dcfg = _drizzle_config(scale, pixfrac, kernel, sigma_low, sigma_high, sigma_iterations, align, alignment_method, num_threads)
+        keep, arrays, counts, dims, first = [], [], [], [], None
+        for frames in lists:
+            if frames is None:
+                arrays.append(None), counts.append(0)
+                continue
+            arrays.append(self._planes(frames, keep)), counts.append(len(frames))
+            if len(frames) >= 2:
+                first = frames[0] if first is None else first
+                d = [C.c_int64(0) for _ in range(4)]
+                self._check_noctx(self._L.ab_drizzle_output_dims(arrays[-1], len(frames), C.byref(dcfg), *[C.byref(x) for x in d]), len(frames))
+                dims.append((int(d[2].value), int(d[3].value)))
+        if first is None:
+            raise AstroBurstError(_lib.AB_ERR_INVALID, "All channels failed or have fewer than 2 frames")
+        rows, cols = min(d[0] for d in dims), min(d[1] for d in dims)
+        cfg = self._drizzle_rgb_config(white_balance, auto_stretch, linked_stf, scnr)
+        wb, pw = self._plane3(first, rows, cols, keep) if want_wb else (None, None)
+        rgb8, ptr, dev = self._rgb_bytes_out(first, rows, cols, RGB_PACK_8_ROUND, None) if want_rgb8 else (None, None, 0)
+        res = (_lib.DrizzleResultC * 3)()
+        info = _lib.ProcessedDrizzleRgbInfoC()
+        self._check(self._L.ab_drizzle_rgb(self._h, arrays[0], counts[0], arrays[1], counts[1], arrays[2], counts[2], C.byref(dcfg), C.byref(cfg), pw, ptr,
+                                           dev, res, C.byref(info)))
+        chans = tuple(None if x.frame_count == 0 else (int(x.frame_count), float(x.output_scale), (int(x.in_rows), int(x.in_cols)),
+                                                       (int(x.out_rows), int(x.out_cols)), int(x.rejected_pixels)) for x in res)
+        return DrizzleRgbResult(self._processed_drizzle_rgb(None, wb, rgb8, info), chans)
 
     # ---- core/stacking/drizzle.rs -------------------------------------------------------------------------
     drizzle_output_dims = staticmethod(drizzle_output_dims)

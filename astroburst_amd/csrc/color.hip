@@ -13,6 +13,7 @@
 // separate f32 operations in weight order (no FMA contraction) so the result is bit-identical to
 // the reference's `rv += v * rw`.  The curve LUT (4096 f32 = 16 KiB) is staged in LDS.
 #include "ab_common.hpp"
+#include "scnr_device.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -29,24 +30,7 @@ int stream_grid(ab_ctx *ctx, int64_t n4) {
     return (int)std::max<int64_t>(1, std::min(want, cap));
 }
 
-// ---- SCNR (scnr.rs:36-52) ---------------------------------------------------------------------
-__device__ __forceinline__ void scnr_px(float &rv, float &gv, float &bv, int method, float amount, int preserve) {
-    const float LUM_R = 0.2126f, LUM_G = 0.7152f, LUM_B = 0.0722f;
-    const float INV_RB_WEIGHT = 1.0f / (LUM_R + LUM_B);
-    const float limit = method == 0 ? (rv + bv) * 0.5f : fmaxf(rv, bv);
-    const float g_corrected = fminf(gv, limit);
-    const float g_new = gv + amount * (g_corrected - gv);
-    const float delta_g = gv - g_new;
-    if (preserve && delta_g > 1e-10f && rv <= 1.0f && bv <= 1.0f) {
-        const float lum_lost = LUM_G * delta_g;
-        const float boost = lum_lost * INV_RB_WEIGHT;
-        const float rn = rv + boost, bn = bv + boost;
-        rv = rn > 1.0f ? 1.0f : rn;
-        bv = bn > 1.0f ? 1.0f : bn;
-    }
-    gv = g_new;
-}
-
+// ---- SCNR (scnr.rs:36-52): the per-pixel closure is scnr_device.hpp's scnr_px, shared with rgb_export.hip ----
 __global__ __launch_bounds__(kBlock) void scnr_kernel(float *r, float *g, float *b, int64_t n, int method, float amount,
                                                       int preserve, int vec) {
     const int64_t n4 = vec ? (n >> 2) : 0, stride = (int64_t)gridDim.x * kBlock;

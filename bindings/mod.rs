@@ -35,6 +35,7 @@ use crate::core::analysis::subframe::{SubframeMetrics, SubframeWeightConfig};
 use crate::core::astrometry::spcc::{SpccConfig, SpccResult, WhiteReference};
 use crate::core::compose::channel_blend::BlendWeight;
 use crate::core::cube::eager::GlobalCubeStats;
+use crate::core::compose::drizzle_rgb::ProcessedDrizzleRgb;
 use crate::core::compose::rgb::ProcessedRgb;
 use crate::core::imaging::background::{BackgroundConfig, BackgroundResult};
 use crate::core::imaging::calibration_pipeline::{
@@ -50,7 +51,7 @@ use crate::core::synth::noise::NoiseParams;
 use crate::core::synth::pipeline::{FieldType, PsfType, SynthConfig};
 use crate::core::synth::star_field::{FieldConfig, Star};
 use crate::infra::progress::ProgressHandle;
-use crate::types::compose::{AlignMethod, ChannelStats, DimensionHarmonize, RgbComposeConfig, WhiteBalance};
+use crate::types::compose::{AlignMethod, ChannelStats, DimensionHarmonize, DrizzleRgbConfig, RgbComposeConfig, WhiteBalance};
 use crate::types::image::{AutoStfConfig, ImageStats, ScnrConfig, ScnrMethod, StfParams};
 use crate::types::stacking::{AlignmentMethod, DrizzleConfig, DrizzleKernel, DrizzleResult, RLConfig, RLResult, StackConfig, StackResult};
 
@@ -1300,6 +1301,198 @@ pub fn drizzle_stack<P: PlaneSrc>(hip: &Hip, images: &[P], config: &DrizzleConfi
 /// registration of an earlier run, a plate solution, a dither log
 pub fn drizzle_frames<P: PlaneSrc>(hip: &Hip, images: &[P], offsets: &[(f64, f64)], config: &DrizzleConfig) -> Result<DrizzleResult> {
     drizzle_run(hip, images, Some(offsets), config)
+}
+
+// ---- the colour finish: core/compose/drizzle_rgb.rs, infra/render/rgb.rs, cmd/export/mod.rs (export_png, export_rgb_png) --------------------------------------
+/// the three packers of the reference's colour writers: render_rgb's truncation, drizzle_rgb's rounding, render_rgb_16bit's big-endian pairs
+#[derive(Clone, Copy, PartialEq, Eq, Debug)]
+pub enum RgbPack {
+    U8 = 0,
+    U8Round = 1,
+    U16Be = 2,
+}
+/// rows * cols * 3 bytes, twice that for RgbPack::U16Be; host-only
+pub fn rgb_packed_bytes(rows: usize, cols: usize, pack: RgbPack) -> Result<usize> {
+    let mut n = 0usize;
+    if unsafe { sys::ab_rgb_packed_bytes(rows as i64, cols as i64, pack as i32, &mut n) } != 0 {
+        bail!("an RGB buffer of {} x {} pixels cannot be sized (an empty image, or 2^31 pixels or more)", cols, rows);
+    }
+    Ok(n)
+}
+/// the packer alone on three stretched planes of one size: the interleaved bytes the reference hands its encoder
+pub fn render_rgb_packed(hip: &Hip, r: &impl PlaneSrc, g: &impl PlaneSrc, b: &impl PlaneSrc, pack: RgbPack) -> Result<Vec<u8>> {
+    let (rows, cols) = r.dims();
+    let mut out = vec![0u8; rgb_packed_bytes(rows, cols, pack)?];
+    hip.check(unsafe { sys::ab_render_rgb(hip.ctx, &r.ab(), &g.ab(), &b.ab(), pack as i32, out.as_mut_ptr() as *mut c_void, 0) })?;
+    Ok(out)
+}
+/// drop-in for render_rgb (infra/render/rgb.rs:7-47) up to the encoder: Rgb8 bytes at full size
+pub fn render_rgb(hip: &Hip, r: &impl PlaneSrc, g: &impl PlaneSrc, b: &impl PlaneSrc) -> Result<Vec<u8>> {
+    render_rgb_packed(hip, r, g, b, RgbPack::U8)
+}
+/// drop-in for render_rgb_16bit (rgb.rs:49-91) up to the encoder: the big-endian byte pairs its flat_map(to_be_bytes) builds
+pub fn render_rgb_16bit(hip: &Hip, r: &impl PlaneSrc, g: &impl PlaneSrc, b: &impl PlaneSrc) -> Result<Vec<u8>> {
+    render_rgb_packed(hip, r, g, b, RgbPack::U16Be)
+}
+/// apply_stf_f32 x 3 and the packer in one launch (export/mod.rs:189-207, :321-328): the three stretched planes are never written
+pub fn render_rgb_stf(hip: &Hip, r: &impl PlaneSrc, g: &impl PlaneSrc, b: &impl PlaneSrc, stf: &[StfParams; 3], stats: &[ImageStats; 3], pack: RgbPack) -> Result<Vec<u8>> {
+    let (rows, cols) = r.dims();
+    let mut out = vec![0u8; rgb_packed_bytes(rows, cols, pack)?];
+    let p = [stf_to_sys(&stf[0]), stf_to_sys(&stf[1]), stf_to_sys(&stf[2])];
+    let s = [stats_to_sys(&stats[0]), stats_to_sys(&stats[1]), stats_to_sys(&stats[2])];
+    hip.check(unsafe { sys::ab_render_rgb_stf(hip.ctx, &r.ab(), &g.ab(), &b.ab(), p.as_ptr(), s.as_ptr(), pack as i32, out.as_mut_ptr() as *mut c_void, 0) })?;
+    Ok(out)
+}
+/// what export_rgb_png's stretch_and_render (cmd/export/mod.rs:357-409) derives on its way to the encoder
+pub struct RgbExport {
+    pub pixels: Vec<u8>,
+    pub rows: usize,
+    pub cols: usize,
+    pub resampled: bool,
+    pub stats: [ImageStats; 3],
+    pub stf: [StfParams; 3],
+}
+/// stretch_and_render whole: resample to the largest dims where they differ, statistics, the explicit STF or the linked one, the bytes
+/// of render_rgb (bit_depth 8) / render_rgb_16bit (16)
+pub fn export_rgb(hip: &Hip, r: &impl PlaneSrc, g: &impl PlaneSrc, b: &impl PlaneSrc, bit_depth: u8, explicit_stf: Option<&[StfParams; 3]>) -> Result<RgbExport> {
+    let dims = [r.dims(), g.dims(), b.dims()];
+    let rows = dims.iter().map(|d| d.0).max().unwrap();
+    let cols = dims.iter().map(|d| d.1).max().unwrap();
+    let mut cfg: sys::ab_rgb_export_config = unsafe { std::mem::zeroed() };
+    cfg.bits = bit_depth as i32;
+    if let Some(p) = explicit_stf {
+        cfg.has_stf = 1;
+        cfg.stf = [stf_to_sys(&p[0]), stf_to_sys(&p[1]), stf_to_sys(&p[2])];
+    }
+    let mut pixels = vec![0u8; rgb_packed_bytes(rows, cols, if bit_depth == 16 { RgbPack::U16Be } else { RgbPack::U8 })?];
+    let mut info: sys::ab_rgb_export_info = unsafe { std::mem::zeroed() };
+    hip.check(unsafe { sys::ab_export_rgb(hip.ctx, &r.ab(), &g.ab(), &b.ab(), &cfg, pixels.as_mut_ptr() as *mut c_void, 0, &mut info) })?;
+    Ok(RgbExport {
+        pixels,
+        rows: info.rows as usize,
+        cols: info.cols as usize,
+        resampled: info.resampled != 0,
+        stats: [stats_from_sys(&info.stats[0]), stats_from_sys(&info.stats[1]), stats_from_sys(&info.stats[2])],
+        stf: [stf_from_sys(&info.stf[0]), stf_from_sys(&info.stf[1]), stf_from_sys(&info.stf[2])],
+    })
+}
+fn drizzle_rgb_cfg(config: &DrizzleRgbConfig) -> sys::ab_drizzle_rgb_config {
+    let mut cfg: sys::ab_drizzle_rgb_config = unsafe { std::mem::zeroed() };
+    match config.white_balance {
+        WhiteBalance::Auto => cfg.white_balance = 0,
+        WhiteBalance::Manual(x, y, z) => {
+            cfg.white_balance = 1;
+            cfg.wb_manual = [x, y, z];
+        }
+        WhiteBalance::None => cfg.white_balance = 2,
+    }
+    cfg.auto_stretch = config.auto_stretch as i32;
+    cfg.linked_stf = config.linked_stf as i32;
+    if let Some(s) = config.scnr.as_ref() {
+        cfg.has_scnr = 1;
+        cfg.scnr = scnr_to_sys(s);
+    }
+    cfg
+}
+fn planes3(rows: usize, cols: usize) -> [Array2<f32>; 3] {
+    [Array2::<f32>::zeros((rows, cols)), Array2::<f32>::zeros((rows, cols)), Array2::<f32>::zeros((rows, cols))]
+}
+fn processed_drizzle_rgb(stretched: [Array2<f32>; 3], wb: [Array2<f32>; 3], info: &sys::ab_processed_drizzle_rgb_info) -> ProcessedDrizzleRgb {
+    let cs = |i: usize| ChannelStats { min: info.chan_stats[i][0], max: info.chan_stats[i][1], median: info.chan_stats[i][2], mean: info.chan_stats[i][3] };
+    let [r_stretched, g_stretched, b_stretched] = stretched;
+    let [r_wb, g_wb, b_wb] = wb;
+    ProcessedDrizzleRgb {
+        r_stretched,
+        g_stretched,
+        b_stretched,
+        r_wb,
+        g_wb,
+        b_wb,
+        output_dims: (info.rows as usize, info.cols as usize),
+        stf_r: stf_from_sys(&info.stf[0]),
+        stf_g: stf_from_sys(&info.stf[1]),
+        stf_b: stf_from_sys(&info.stf[2]),
+        stats_r: cs(0),
+        stats_g: cs(1),
+        stats_b: cs(2),
+        scnr_applied: info.scnr_applied != 0,
+    }
+}
+/// drop-in for process_drizzle_rgb (core/compose/drizzle_rgb.rs:41-145) on the three optional channel images (the reference takes them
+/// inside DrizzleRgbChannels, whose other fields it does not read) -- and the Rgb8 bytes drizzle_rgb builds from the result (:232-248)
+pub fn process_drizzle_rgb(hip: &Hip, r: Option<&Array2<f32>>, g: Option<&Array2<f32>>, b: Option<&Array2<f32>>, config: &DrizzleRgbConfig) -> Result<(ProcessedDrizzleRgb, Vec<u8>)> {
+    if r.is_none() && g.is_none() && b.is_none() {
+        bail!("process_drizzle_rgb: at least one channel must be present");
+    }
+    let rows = [r, g, b].iter().flatten().map(|a| a.nrows()).min().unwrap();
+    let cols = [r, g, b].iter().flatten().map(|a| a.ncols()).min().unwrap();
+    let (pr, pg, pb) = (opt_plane(r), opt_plane(g), opt_plane(b));
+    let (mut s, mut w) = (planes3(rows, cols), planes3(rows, cols));
+    let mut ps = [s[0].ab_mut(), s[1].ab_mut(), s[2].ab_mut()];
+    let mut pw = [w[0].ab_mut(), w[1].ab_mut(), w[2].ab_mut()];
+    let mut pixels = vec![0u8; rgb_packed_bytes(rows, cols, RgbPack::U8Round)?];
+    let mut info: sys::ab_processed_drizzle_rgb_info = unsafe { std::mem::zeroed() };
+    hip.check(unsafe {
+        sys::ab_process_drizzle_rgb(hip.ctx, opt_ptr(&pr), opt_ptr(&pg), opt_ptr(&pb), &drizzle_rgb_cfg(config), ps.as_mut_ptr(), pw.as_mut_ptr(), pixels.as_mut_ptr(), 0, &mut info)
+    })?;
+    Ok((processed_drizzle_rgb(s, w, &info), pixels))
+}
+/// what drizzle_rgb (drizzle_rgb.rs:159-286) holds when it reaches its writers: the Rgb8 bytes for RgbImage::from_raw, the three
+/// white-balanced planes for write_fits_rgb, and DrizzleRgbResult's scalars
+pub struct DrizzleRgbOutput {
+    pub pixels: Vec<u8>,
+    pub wb: [Array2<f32>; 3],
+    pub input_dims: (usize, usize),
+    pub output_dims: (usize, usize),
+    pub scale: f64,
+    pub frame_counts: [usize; 3],
+    pub rejected_pixels: u64,
+    pub stf: [StfParams; 3],
+    pub stats: [ChannelStats; 3],
+    pub scnr_applied: bool,
+}
+/// drop-in for drizzle_rgb (drizzle_rgb.rs:159-286) up to the PNG / FITS writers, with the channels' frames in place of their paths: each
+/// channel's drizzle stays on the device and only the bytes and the white-balanced planes come back
+pub fn drizzle_rgb<P: PlaneSrc>(hip: &Hip, r: Option<&[P]>, g: Option<&[P]>, b: Option<&[P]>, config: &DrizzleRgbConfig) -> Result<DrizzleRgbOutput> {
+    let lists = [r, g, b];
+    let given = lists.iter().filter(|l| l.is_some()).count();
+    if given < 2 {
+        bail!("Need at least 2 channels for RGB drizzle (got {})", given); // :171-173
+    }
+    let mut dims = Vec::new();
+    for l in lists.iter().flatten().filter(|l| l.len() >= 2) {
+        dims.push(drizzle_output_dims(l, &config.drizzle)?.1);
+    }
+    if dims.is_empty() {
+        bail!("All channels failed or have fewer than 2 frames"); // :203-205
+    }
+    let rows = dims.iter().map(|d| d.0).min().unwrap();
+    let cols = dims.iter().map(|d| d.1).min().unwrap();
+    let planes: Vec<Option<Vec<sys::ab_plane>>> = lists.iter().map(|l| l.map(|f| f.iter().map(|i| i.ab()).collect())).collect();
+    let ptr = |i: usize| planes[i].as_ref().map_or(std::ptr::null(), |v| v.as_ptr());
+    let len = |i: usize| planes[i].as_ref().map_or(0, |v| v.len());
+    let mut w = planes3(rows, cols);
+    let mut pw = [w[0].ab_mut(), w[1].ab_mut(), w[2].ab_mut()];
+    let mut pixels = vec![0u8; rgb_packed_bytes(rows, cols, RgbPack::U8Round)?];
+    let mut res: [sys::ab_drizzle_result; 3] = unsafe { std::mem::zeroed() };
+    let mut info: sys::ab_processed_drizzle_rgb_info = unsafe { std::mem::zeroed() };
+    hip.check(unsafe {
+        sys::ab_drizzle_rgb(hip.ctx, ptr(0), len(0), ptr(1), len(1), ptr(2), len(2), &drizzle_cfg(&config.drizzle), &drizzle_rgb_cfg(config), pw.as_mut_ptr(), pixels.as_mut_ptr(), 0, res.as_mut_ptr(), &mut info)
+    })?;
+    let first = res.iter().find(|x| x.frame_count > 0).unwrap(); // :207-213
+    let cs = |i: usize| ChannelStats { min: info.chan_stats[i][0], max: info.chan_stats[i][1], median: info.chan_stats[i][2], mean: info.chan_stats[i][3] };
+    Ok(DrizzleRgbOutput {
+        pixels,
+        wb: w,
+        input_dims: (first.in_rows as usize, first.in_cols as usize),
+        output_dims: (info.rows as usize, info.cols as usize),
+        scale: first.output_scale,
+        frame_counts: [res[0].frame_count, res[1].frame_count, res[2].frame_count],
+        rejected_pixels: res.iter().map(|x| x.rejected_pixels).sum(),
+        stf: [stf_from_sys(&info.stf[0]), stf_from_sys(&info.stf[1]), stf_from_sys(&info.stf[2])],
+        stats: [cs(0), cs(1), cs(2)],
+        scnr_applied: info.scnr_applied != 0,
+    })
 }
 
 // ---- a13  core/imaging/star_mask.rs, masked_stretch.rs -------------------------------------------------------------------------------------------------

@@ -1087,6 +1087,85 @@ AB_API int ab_render_grayscale(ab_ctx *ctx, const ab_plane *img, int32_t bits, v
  * validity test: NaN -> 0, +inf -> top, -inf -> 0.  One launch; asynchronous for a device plane with a device output. */
 AB_API int ab_render_stretched(ab_ctx *ctx, const ab_plane *img, int32_t bits, void *out, int32_t out_on_device);
 
+/* ---- the colour finish: core/compose/drizzle_rgb.rs, infra/render/rgb.rs, cmd/export/mod.rs (export_png, export_rgb_png) ------ */
+/* What the export and drizzle commands do to three channels once they exist, up to the PNG / FITS writers.  One fused kernel family
+ * (csrc/rgb_export.hip) computes per pixel and channel: the load through the source's own row stride (a top-left crop costs no
+ * copy; an absent channel reads as 0), the white-balance multiply v * (wb as f32) (drizzle_rgb.rs:82-84), stf::apply_stf_f32's value
+ * (stf.rs:104-120, which MULTIPLIES by inv_clip: not process_rgb's compose-local stretch, which divides by clip_range, rgb.rs:199-206 --
+ * the two differ in the last bit), SCNR on the three stretched values in registers (scnr.rs:28-52), and one of three packers:
+ *   AB_RGB_PACK_8        (v.clamp(0, 1) * 255f32) as u8              render_rgb, rgb.rs:29-31
+ *   AB_RGB_PACK_8_ROUND  (v.clamp(0, 1) * 255f32).round() as u8      drizzle_rgb.rs:244-246 (half away from zero)
+ *   AB_RGB_PACK_16BE     (v.clamp(0, 1) * 65535f32) as u16           render_rgb_16bit, rgb.rs:71-77: high byte first
+ * interleaved R, G, B.  f32::clamp keeps a NaN and `as` truncates, saturates and sends NaN to 0: NaN -> 0, -inf -> 0, +inf -> top.
+ * Every operation is an IEEE basic operation, unfused: every plane and every byte is the reference's, bit for bit.  Planes host or
+ * device at any float-aligned address; a device byte output at ANY address (whole dwords are stored wherever it allows).  An output
+ * may not overlap an input.  rows * cols >= 2^31 -> AB_ERR_INVALID. */
+typedef enum { AB_RGB_PACK_8 = 0, AB_RGB_PACK_8_ROUND = 1, AB_RGB_PACK_16BE = 2 } ab_rgb_pack;
+/* host-only: rows * cols * 3 * (pack == AB_RGB_PACK_16BE ? 2 : 1); a pack outside the enum, rows or cols < 1 or rows * cols >= 2^31
+ * -> AB_ERR_INVALID */
+AB_API int ab_rgb_packed_bytes(int64_t rows, int64_t cols, int32_t pack, size_t *bytes);
+/* render_rgb (rgb.rs:7-47) at full size, render_rgb_16bit (:49-91) and the drizzle packer (drizzle_rgb.rs:232-248) on planes that are
+ * already stretched: the packer alone.  r, g, b of one size; out: ab_rgb_packed_bytes.  One launch, asynchronous for device planes
+ * with a device output.  AB_RGB_PACK_8 gives what ab_render_rgb_preview gives when max_dim covers the image. */
+AB_API int ab_render_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, int32_t pack, void *out, int32_t out_on_device);
+/* apply_stf_f32(c, &stf[c], &stats[c]) x 3 and then the packer, fused: what export/mod.rs:189-207, :321-328 and :362-382 do once their
+ * statistics and STF are known.  One launch; the three stretched f32 planes are never written.  Byte for byte ab_apply_stf_f32 x 3
+ * followed by ab_render_rgb. */
+AB_API int ab_render_rgb_stf(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, const ab_stf_params stf[3],
+                             const ab_image_stats stats[3], int32_t pack, void *out, int32_t out_on_device);
+typedef struct {
+    int32_t bits;    /* 8 (render_rgb) | 16 (render_rgb_16bit); anything else -> AB_ERR_INVALID */
+    int32_t has_stf; /* 1: stf[3] as given (the explicit branch, :362-370); 0: compute_linked_stf of the three statistics with
+                        AutoStfConfig::default() for all three channels (:371-378) */
+    ab_stf_params stf[3];
+} ab_rgb_export_config;
+typedef struct {
+    uint64_t rows, cols;
+    int32_t resampled;
+    ab_image_stats stats[3]; /* compute_image_stats per channel (after the resampling) */
+    ab_stf_params stf[3];    /* what was applied */
+} ab_rgb_export_info;
+/* stretch_and_render whole (export/mod.rs:357-409): channels of differing dims are first resampled (bicubic, ab_resample_image) to
+ * the largest rows and the largest cols (:396-407); compute_image_stats per channel; the STF choice; ab_render_rgb_stf with
+ * AB_RGB_PACK_8 / AB_RGB_PACK_16BE.  out: the largest dims.  Not asynchronous: the statistics are read back. */
+AB_API int ab_export_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, const ab_rgb_export_config *cfg, void *out,
+                         int32_t out_on_device, ab_rgb_export_info *info);
+typedef struct { /* DrizzleRgbConfig (types/compose.rs) without its DrizzleConfig, which is an argument of its own */
+    int32_t white_balance; /* as ab_rgb_compose_config: 0 Auto, 1 Manual(wb_manual), 2 None */
+    double wb_manual[3];
+    int32_t auto_stretch, linked_stf;
+    int32_t has_scnr; /* Option<ScnrConfig> */
+    ab_scnr_config scnr;
+} ab_drizzle_rgb_config;
+typedef struct { /* the scalars of ProcessedDrizzleRgb (drizzle_rgb.rs:24-39) */
+    uint64_t rows, cols;
+    double wb[3];               /* the multipliers (:76-80), applied as f32 */
+    ab_stf_params stf[3];
+    double chan_stats[3][4];    /* ChannelStats {min, max, median, mean} BEFORE white balance (:72-74) */
+    ab_image_stats stats_wb[3]; /* the statistics the STF is applied with */
+    int32_t scnr_applied;       /* a configuration was given (:122-127), whether or not its amount did anything */
+} ab_processed_drizzle_rgb_info;
+/* process_drizzle_rgb (drizzle_rgb.rs:41-145).  Absent channels NULL (a zero plane, :63-66: its statistics are all 0); at least one
+ * present.  Output dims = the minimum rows and the minimum cols over the present channels (a top-left crop, :54-61).  Statistics of
+ * the cropped planes; white balance (every channel is multiplied, even by 1; where (float)wb == 1 the second statistics are the
+ * first); auto_stretch && linked_stf: auto_stf of the statistics of ((r + g) + b) / 3f32 -- a true division, not process_rgb's
+ * multiplication by 1 / 3 -- shared by the channels, each applied with its OWN statistics (:89-96); auto_stretch alone: per channel
+ * (:97-105); neither: {0, 0.5, 1} (:106-116); apply_stf_f32; SCNR.  out_stretched[3], out_wb[3] (arrays of three planes of the
+ * output dims, host or device) and out_rgb8 (rows * cols * 3 bytes, AB_RGB_PACK_8_ROUND of the stretched planes, :232-248) are each
+ * nullable.  After the statistics the white-balanced planes are written by one launch and everything else by one more. */
+AB_API int ab_process_drizzle_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, const ab_drizzle_rgb_config *cfg,
+                                  ab_plane_mut *out_stretched, ab_plane_mut *out_wb, uint8_t *out_rgb8, int32_t out_on_device,
+                                  ab_processed_drizzle_rgb_info *info);
+/* drizzle_rgb (drizzle_rgb.rs:159-286) up to the PNG / FITS writers, with frames in place of paths.  Fewer than two of the three
+ * lists non-NULL: AB_ERR_INVALID "Need at least 2 channels for RGB drizzle (got N)" (:171-173); a list of fewer than two frames is
+ * no channel (:178); none left: "All channels failed or have fewer than 2 frames" (:203-205).  Each remaining channel goes through
+ * ab_drizzle_stack into an image that stays on the device (its error is returned as it is), then ab_process_drizzle_rgb.  res[c]
+ * is zeroed for a channel that is not there.  out_wb[3] (what write_fits_rgb receives) and out_rgb8 (what RgbImage::from_raw
+ * receives) are nullable and sized by ab_drizzle_output_dims per channel, the minimum per axis. */
+AB_API int ab_drizzle_rgb(ab_ctx *ctx, const ab_plane *r_frames, size_t n_r, const ab_plane *g_frames, size_t n_g, const ab_plane *b_frames,
+                          size_t n_b, const ab_drizzle_config *dcfg, const ab_drizzle_rgb_config *cfg, ab_plane_mut *out_wb, uint8_t *out_rgb8,
+                          int32_t out_on_device, ab_drizzle_result res[3], ab_processed_drizzle_rgb_info *info);
+
 /* ---- bench support: a plain float4 device copy, the measured HBM ceiling ---- */
 AB_API int ab_bench_copy(ab_ctx *ctx, const float *src_dev, float *dst_dev, size_t n_floats);
 
