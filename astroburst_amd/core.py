@@ -1208,8 +1208,20 @@ class Context:
         return ((StfParamsC * 3)(*[StfParamsC(p.shadow, p.midtone, p.highlight) for p in stf]),
                 (_lib.ImageStatsC * 3)(*[self._stats_in(s) for s in stats]) if stats is not None else None)
 
-    def _bytes_out(self, like, shape):
-        """u8 output next to the input: a CUDA tensor for device planes, a numpy array for host planes -> (array, ptr, on_device)"""
+    def _bytes_out(self, like, shape, out=None):
+        """u8 output next to the input: a CUDA tensor for device planes, a numpy array for host planes -> (array, ptr, on_device);
+        or the caller's `out` (contiguous uint8 of that many bytes, CUDA tensor or numpy array)"""
+        if out is not None:
+            n = int(np.prod(shape))
+            if _is_torch(out):
+                ok = out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n
+                ptr, dev = out.data_ptr(), 1
+            else:
+                ok = isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.size == n
+                ptr, dev = (out.ctypes.data, 0) if ok else (0, 0)
+            if not ok:
+                raise AstroBurstError(_lib.AB_ERR_INVALID, f"the output must be contiguous uint8 of {n} bytes")
+            return out, C.c_void_p(ptr), dev
         if _is_torch(like):
             out = torch.empty(shape, dtype=torch.uint8, device=like.device)
             return out, C.c_void_p(out.data_ptr()), 1
@@ -1222,27 +1234,27 @@ class Context:
             raise AstroBurstError(_lib.AB_ERR_INVALID, "ab_preview_dims: bad arguments")
         return ph.value, pw.value
 
-    def render_rgb_preview(self, r, g, b, max_dim: int, stf=None, stats=None):
+    def render_rgb_preview(self, r, g, b, max_dim: int, stf=None, stats=None, out=None):
         """render_rgb_preview / render_rgb (stf None) or render_rgb_preview_with_stf (stf, stats = 3 each)
-        (cmd/helpers.rs:204-322) -> (ph, pw, 3) u8"""
+        (cmd/helpers.rs:204-322) -> (ph, pw, 3) u8 (or `out`, contiguous uint8 of that size)"""
         keep = []
         pr, pg, pb = (self._plane(x, keep) for x in (r, g, b))
         ph, pw = self.preview_dims(pr.rows, pr.cols, max_dim) if max_dim > 0 else (1, 1)
-        out, ptr, dev = self._bytes_out(r, (ph, pw, 3))
+        out, ptr, dev = self._bytes_out(r, (ph, pw, 3), out)
         p, s = self._stf3(stf, stats)
         self._check(self._L.ab_render_rgb_preview(self._h, C.byref(pr), C.byref(pg), C.byref(pb), max_dim, p, s, ptr, dev))
         return out
 
-    def ipc_encode_with_header(self, image, max_dim: int = 0):
+    def ipc_encode_with_header(self, image, max_dim: int = 0, out=None):
         """encode_with_header / encode_with_header_downsampled (infra/ipc.rs:93-148) -> u8 buffer (header + f32 LE pixels)"""
         keep = []
         pi = self._plane(image, keep)
         full = max_dim <= 0 or (pi.rows <= max_dim and pi.cols <= max_dim)
         ph, pw = (pi.rows, pi.cols) if full else self.preview_dims(pi.rows, pi.cols, max_dim)
-        out, ptr, dev = self._bytes_out(image, (16 + 4 * ph * pw,))
+        out, ptr, dev = self._bytes_out(image, (16 + 4 * ph * pw,), out)
         n = C.c_size_t(0)
         self._check(self._L.ab_ipc_encode_with_header(self._h, C.byref(pi), max_dim, ptr, dev, C.byref(n)))
-        assert n.value == out.shape[0]
+        assert n.value == 16 + 4 * ph * pw
         return out
 
     def tile_compute_num_levels(self, width: int, height: int, tile_size: int) -> int:
@@ -1269,22 +1281,22 @@ class Context:
         self._check(self._L.ab_tile_percentile_bounds(self._h, C.byref(pi), low_pct, high_pct, C.byref(lo), C.byref(hi)))
         return lo.value, hi.value
 
-    def generate_tile_pyramid(self, normalized, tile_size: int = 256):
+    def generate_tile_pyramid(self, normalized, tile_size: int = 256, out=None):
         """generate_tile_pyramid (infra/render/tiles.rs:180-255) up to the encoder -> (packed tiles u8, levels, (gmin, gmax))"""
         keep = []
         pi = self._plane(normalized, keep)
         levels, total = self.tile_pyramid_layout(pi.rows, pi.cols, tile_size, 1)
-        out, ptr, dev = self._bytes_out(normalized, (total,))
+        out, ptr, dev = self._bytes_out(normalized, (total,), out)
         lv, n, lo, hi = (_lib.TileLevelC * _lib.MAX_TILE_LEVELS)(), C.c_int32(), C.c_float(), C.c_float()
         self._check(self._L.ab_generate_tile_pyramid(self._h, C.byref(pi), tile_size, ptr, dev, lv, C.byref(n), C.byref(lo), C.byref(hi)))
         return out, levels, (lo.value, hi.value)
 
-    def generate_tile_pyramid_rgb(self, r, g, b, tile_size: int = 256, stf=None, stats=None):
+    def generate_tile_pyramid_rgb(self, r, g, b, tile_size: int = 256, stf=None, stats=None, out=None):
         """generate_tile_pyramid_rgb / _rgb_stf (tiles.rs:363-481) up to the encoder -> (packed tiles u8, levels)"""
         keep = []
         pr, pg, pb = (self._plane(x, keep) for x in (r, g, b))
         levels, total = self.tile_pyramid_layout(pr.rows, pr.cols, tile_size, 3)
-        out, ptr, dev = self._bytes_out(r, (total,))
+        out, ptr, dev = self._bytes_out(r, (total,), out)
         lv, n = (_lib.TileLevelC * _lib.MAX_TILE_LEVELS)(), C.c_int32()
         p, s = self._stf3(stf, stats)
         self._check(self._L.ab_generate_tile_pyramid_rgb(self._h, C.byref(pr), C.byref(pg), C.byref(pb), tile_size, p, s, ptr, dev, lv,

@@ -300,6 +300,13 @@ size_t layout(int64_t rows, int64_t cols, int64_t ts, int channels, ab_tile_leve
     return total;
 }
 
+/* Rust `f64 as usize`: saturating, NaN -> 0 (a C cast of an out-of-range double is undefined) */
+static inline uint64_t sat_usize(double v) {
+    if (!(v > 0.0)) return 0;
+    if (v >= 18446744073709551615.0) return UINT64_MAX;
+    return (uint64_t)v;
+}
+
 int percentile_bounds(ab_ctx *ctx, const float *data, int64_t n, double low_pct, double high_pct, float *lo, float *hi) {  // tiles.rs:149-178
     ab_plane_sel s;
     s.data = data;
@@ -310,8 +317,8 @@ int percentile_bounds(ab_ctx *ctx, const float *data, int64_t n, double low_pct,
     AB_TRY(ab_plane_select_ranks(
         ctx, s, 2,
         [&](uint64_t m, uint64_t *ranks) {
-            ranks[0] = std::min<uint64_t>((uint64_t)((double)m * low_pct), m - 1);
-            ranks[1] = std::min<uint64_t>((uint64_t)((double)m * high_pct), m - 1);
+            ranks[0] = std::min<uint64_t>(sat_usize((double)m * low_pct), m - 1);  // tiles.rs:162-163
+            ranks[1] = std::min<uint64_t>(sat_usize((double)m * high_pct), m - 1);
             return 2;
         },
         &count, v));

@@ -623,7 +623,10 @@ AB_API int ab_render_rgb_preview(ab_ctx *ctx, const ab_plane *r, const ab_plane 
                                  const ab_stf_params *stf, const ab_image_stats *stats, uint8_t *out_rgb, int32_t out_on_device);
 /* encode_with_header (infra/ipc.rs:93-103; max_dim == 0) / encode_with_header_downsampled (:105-148): 16-byte header
  * (u32 width, u32 height, f32 data_min, f32 data_max, little-endian) + cleaned f32 pixels (non-finite -> 0).
- * out holds 16 + 4 * preview_rows * preview_cols bytes; *out_len (nullable) = the length written. */
+ * out holds 16 + 4 * preview_rows * preview_cols bytes; *out_len (nullable) = the length written.
+ * The SIGN of a data_min / data_max that is zero is unspecified: on a plane that holds both +0.0 and -0.0 the reference keeps
+ * the first zero of each 65536-pixel chunk and merges the chunks with f32::min / f32::max, which fix no sign either.  Compare
+ * those two header fields by value; the pixel bytes keep every -0.0 as it is. */
 AB_API int ab_ipc_encode_with_header(ab_ctx *ctx, const ab_plane *img, int64_t max_dim, void *out, int32_t out_on_device, size_t *out_len);
 #define AB_MAX_TILE_LEVELS 32
 typedef struct { /* TileLevel (infra/render/tiles.rs:21-29) + where the level's tiles start in the packed buffer */
@@ -637,7 +640,9 @@ AB_API int ab_tile_compute_num_levels(int64_t width, int64_t height, int64_t til
 AB_API int ab_tile_pyramid_layout(int64_t rows, int64_t cols, int64_t tile_size, int32_t channels, ab_tile_level *levels,
                                   int32_t *num_levels, size_t *total_bytes);
 AB_API int ab_tile_downsample_2x(ab_ctx *ctx, const ab_plane *img, ab_plane_mut *out);      /* downsample_2x, tiles.rs:41-70 */
-/* percentile_bounds (tiles.rs:149-178): order statistics of the finite pixels > 1e-7; finite min / max if there are none */
+/* percentile_bounds (tiles.rs:149-178): order statistics of the finite pixels > 1e-7; finite min / max if there are none.
+ * The ranks are `((n as f64 * pct) as usize).min(n - 1)`, a saturating conversion: a negative or NaN pct selects the smallest
+ * valid pixel, a pct past 1 the largest. */
 AB_API int ab_tile_percentile_bounds(ab_ctx *ctx, const ab_plane *img, double low_pct, double high_pct, float *lo, float *hi);
 /* generate_tile_pyramid (tiles.rs:180-255) up to the encoder: percentile_bounds(0.001, 0.999), the 2x chain, and every
  * render_tile buffer (:72-113) into `tiles` (layout above, channels = 1; zero outside the image). */

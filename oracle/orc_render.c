@@ -106,6 +106,13 @@ void orc_tile_downsample_2x(const float *src, size_t rows, size_t cols, float *o
     }
 }
 
+/* Rust `f64 as usize`: saturating, NaN -> 0 (a C cast of an out-of-range double is undefined) */
+static inline uint64_t sat_usize(double v) {
+    if (!(v > 0.0)) return 0;
+    if (v >= 18446744073709551615.0) return UINT64_MAX;
+    return (uint64_t)v;
+}
+
 void orc_tile_percentile_bounds(const float *slice, size_t n, double low_pct, double high_pct, float *lo, float *hi) {  /* :149-178 */
     float *valid = (float *)malloc((n ? n : 1) * sizeof(float));
     size_t m = 0;
@@ -119,7 +126,7 @@ void orc_tile_percentile_bounds(const float *slice, size_t n, double low_pct, do
         free(valid);
         return;
     }
-    size_t hi_idx = (size_t)((double)m * high_pct), lo_idx = (size_t)((double)m * low_pct);
+    size_t hi_idx = (size_t)sat_usize((double)m * high_pct), lo_idx = (size_t)sat_usize((double)m * low_pct);   /* :162-163 */
     if (hi_idx > m - 1) hi_idx = m - 1;
     if (lo_idx > m - 1) lo_idx = m - 1;
     orc_select_nth_f32(valid, m, hi_idx);
