@@ -286,6 +286,20 @@ class DrizzleResultC(C.Structure):  # DrizzleResult's scalars (drizzle.rs:335-34
                 ("out_rows", C.c_int64), ("out_cols", C.c_int64), ("rejected_pixels", C.c_uint64)]
 
 
+class CropBoxC(C.Structure):  # ab_crop_box: rows [top, bottom), columns [left, right) (cmd/compose/crop.rs:14-62)
+    _fields_ = [("top", C.c_uint64), ("bottom", C.c_uint64), ("left", C.c_uint64), ("right", C.c_uint64)]
+
+
+class CropConfigC(C.Structure):  # crop_channels_cmd's arguments (crop.rs:77-81) + AUTO_THRESHOLD (:12)
+    _fields_ = [("auto_detect", C.c_int32), ("top", C.c_uint64), ("bottom", C.c_uint64), ("left", C.c_uint64), ("right", C.c_uint64),
+                ("threshold", C.c_float)]
+
+
+class CropPlanC(C.Structure):  # ab_crop_plan: the box and what the command's JSON reports (crop.rs:103-126, :170-183)
+    _fields_ = [("crop_box", CropBoxC), ("out_rows", C.c_uint64), ("out_cols", C.c_uint64), ("actual_top", C.c_uint64),
+                ("actual_bottom", C.c_uint64), ("actual_left", C.c_uint64), ("actual_right", C.c_uint64), ("auto_detected", C.c_int32)]
+
+
 class SubframeMetricsC(C.Structure):  # subframe.rs:9-22
     _fields_ = [("star_count", C.c_uint64), ("median_fwhm", C.c_double), ("median_eccentricity", C.c_double),
                 ("median_snr", C.c_double), ("background_median", C.c_double), ("background_sigma", C.c_double),
@@ -548,6 +562,14 @@ def lib() -> C.CDLL:
     L.ab_drizzle_output_dims.argtypes = [pp, C.c_size_t, C.POINTER(DrizzleConfigC), i64p, i64p, i64p, i64p]
     L.ab_drizzle_frames.argtypes = [vp, pp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(DrizzleConfigC), pp, pp, C.POINTER(DrizzleResultC)]
     L.ab_drizzle_stack.argtypes = [vp, pp, C.c_size_t, C.POINTER(DrizzleConfigC), pp, pp, C.POINTER(C.c_double), C.POINTER(DrizzleResultC)]
+    cbp = C.POINTER(CropBoxC)
+    L.ab_detect_valid_region.argtypes = [vp, pp, C.c_float, cbp]
+    L.ab_detect_valid_regions.argtypes = [vp, pp, C.c_size_t, C.c_float, cbp, cbp]
+    L.ab_crop_array.argtypes = [vp, pp, cbp, pmp]
+    L.ab_crop_config_default.argtypes = [C.POINTER(CropConfigC)]
+    L.ab_crop_config_default.restype = None
+    L.ab_crop_channels_plan.argtypes = [vp, pp, C.c_size_t, C.POINTER(CropConfigC), C.POINTER(CropPlanC), u64p]
+    L.ab_crop_channels.argtypes = [vp, pp, C.c_size_t, C.POINTER(CropPlanC), pmp, isp]
     for name in declared_symbols():
         fn = getattr(L, name)  # AttributeError here = header / library drift
         if fn.restype is C.c_int and name not in ("ab_last_error", "ab_version", "ab_ctx_get_stream", "ab_comm_collectives_issued"):

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 
@@ -215,6 +216,35 @@ class ProcessedDrizzleRgb:  # drizzle_rgb.rs:24-39 (+ the bytes of :232-248 and 
 class DrizzleRgbResult:  # types/compose.rs DrizzleRgbResult without its paths
     processed: ProcessedDrizzleRgb
     channels: tuple    # 3 x (frame_count, output_scale, in_dims, out_dims, rejected_pixels), None for a channel that is not there
+
+
+class CropBox(NamedTuple):  # detect_valid_region's tuple (cmd/compose/crop.rs:14-62): rows [top, bottom), columns [left, right)
+    top: int
+    bottom: int
+    left: int
+    right: int
+
+    def clamped(self, rows: int, cols: int) -> "CropBox":
+        """the window crop_array takes from a rows x cols plane (crop.rs:65-69)"""
+        t = min(self.top, rows)
+        l = min(self.left, cols)
+        return CropBox(t, max(min(self.bottom, rows), t), l, max(min(self.right, cols), l))
+
+
+CROP_AUTO_THRESHOLD = float(np.float32(1e-6))  # AUTO_THRESHOLD (crop.rs:12)
+
+
+@dataclass
+class CropPlan:  # what crop_channels_cmd decides and reports (crop.rs:103-126, :170-183)
+    crop_box: CropBox
+    out_rows: int          # plane 0's cropped dims ("dimensions" is [out_cols, out_rows])
+    out_cols: int
+    actual_top: int
+    actual_bottom: int
+    actual_left: int
+    actual_right: int
+    auto_detected: bool
+    out_dims: tuple        # (rows, cols) of each plane's cropped output
 
 
 def cube_streaming_step(depth: int) -> int:
@@ -2318,6 +2348,78 @@ class Context:
         chans = tuple(None if x.frame_count == 0 else (int(x.frame_count), float(x.output_scale), (int(x.in_rows), int(x.in_cols)),
                                                        (int(x.out_rows), int(x.out_cols)), int(x.rejected_pixels)) for x in res)
         return DrizzleRgbResult(self._processed_drizzle_rgb(None, wb, rgb8, info), chans)
+
+    # ---- cmd/compose/crop.rs ---------------------------------------------------------------------------------
+    @staticmethod
+    def _box_out(b) -> CropBox:
+        return CropBox(int(b.top), int(b.bottom), int(b.left), int(b.right))
+
+    def detect_valid_region(self, image, threshold: float = CROP_AUTO_THRESHOLD) -> CropBox:
+        """detect_valid_region(arr, threshold) (crop.rs:14-62): (top, bottom, left, right) of the pixels with |v| > threshold;
+        (rows, 0, cols, 0) when there is none."""
+        keep = []
+        pi = self._plane(image, keep)
+        box = _lib.CropBoxC()
+        self._check(self._L.ab_detect_valid_region(self._h, C.byref(pi), float(threshold), C.byref(box)))
+        return self._box_out(box)
+
+    def detect_valid_regions(self, images, threshold: float = CROP_AUTO_THRESHOLD, want_each=True, want_common=True):
+        """The loop crop.rs:109-116 over planes of any dims, one launch chain -> (each plane's CropBox or None, the running
+        (max top, min bottom, max left, min right) or None)."""
+        keep = []
+        arr, n = self._plane_array(images, keep)
+        each = (_lib.CropBoxC * max(n, 1))() if want_each else None
+        common = _lib.CropBoxC() if want_common else None
+        self._check(self._L.ab_detect_valid_regions(self._h, arr, n, float(threshold), each, C.byref(common) if want_common else None))
+        return ([self._box_out(each[i]) for i in range(n)] if want_each else None), (self._box_out(common) if want_common else None)
+
+    def crop_array(self, image, box, out=None):
+        """crop_array(arr, top, bottom, left, right) (crop.rs:64-71): the dense copy of the box, clamped to the plane as the reference
+        clamps it.  out: a plane of the clamped window's dims (allocated like the input when None)."""
+        keep = []
+        pi = self._plane(image, keep)
+        box = CropBox(*(int(v) for v in box))
+        w = box.clamped(int(pi.rows), int(pi.cols))
+        if out is None:
+            out = self._new_like(image, w.bottom - w.top, w.right - w.left)
+        po = self._out_plane(out, keep, out.shape[0], out.shape[1])
+        self._check(self._L.ab_crop_array(self._h, C.byref(pi), C.byref(_lib.CropBoxC(*box)), C.byref(po)))
+        return out
+
+    def crop_channels_plan(self, images, auto_detect=True, top=0, bottom=0, left=0, right=0, threshold=None) -> CropPlan:
+        """crop.rs:92-126: the box of crop_channels_cmd.  auto_detect: the intersection of the planes' valid regions (raises "Auto-crop
+        found no valid overlapping region"); else top / bottom / left / right are margins taken off plane 0's dims."""
+        keep = []
+        arr, n = self._plane_array(images, keep)
+        cfg = _lib.CropConfigC()
+        self._L.ab_crop_config_default(C.byref(cfg))
+        cfg.auto_detect = 1 if auto_detect else 0
+        cfg.top, cfg.bottom, cfg.left, cfg.right = int(top), int(bottom), int(left), int(right)
+        if threshold is not None:
+            cfg.threshold = float(threshold)
+        plan = _lib.CropPlanC()
+        dims = (C.c_uint64 * (2 * max(n, 1)))()
+        self._check(self._L.ab_crop_channels_plan(self._h, arr, n, C.byref(cfg), C.byref(plan), dims))
+        return CropPlan(self._box_out(plan.crop_box), int(plan.out_rows), int(plan.out_cols), int(plan.actual_top), int(plan.actual_bottom),
+                        int(plan.actual_left), int(plan.actual_right), bool(plan.auto_detected),
+                        tuple((int(dims[2 * i]), int(dims[2 * i + 1])) for i in range(n)))
+
+    def crop_channels(self, images, plan: CropPlan, want_stats=True, outs=None):
+        """crop.rs:133-168 without the files and the cache: every plane cropped to plan.crop_box (one launch) -> (the cropped planes, each
+        allocated like its input, and their ImageStats or None).  want_stats=False keeps the call asynchronous for device planes."""
+        keep = []
+        arr, n = self._plane_array(images, keep)
+        if outs is None:
+            outs = []
+            for i in range(n):
+                w = plan.crop_box.clamped(int(arr[i].rows), int(arr[i].cols))
+                outs.append(self._new_like(images[i], w.bottom - w.top, w.right - w.left))
+        po = (Plane * max(n, 1))(*[self._out_plane(o, keep, o.shape[0], o.shape[1]) for o in outs])
+        pc = _lib.CropPlanC(_lib.CropBoxC(*plan.crop_box), plan.out_rows, plan.out_cols, plan.actual_top, plan.actual_bottom, plan.actual_left,
+                            plan.actual_right, 1 if plan.auto_detected else 0)
+        st = (ImageStatsC * max(n, 1))() if want_stats else None
+        self._check(self._L.ab_crop_channels(self._h, arr, n, C.byref(pc), po, st))
+        return list(outs), ([self._stats_out(st[i]) for i in range(n)] if want_stats else None)
 
     # ---- core/stacking/drizzle.rs -------------------------------------------------------------------------
     drizzle_output_dims = staticmethod(drizzle_output_dims)

@@ -1661,6 +1661,104 @@ pub fn calibrate_channel_into(hip: &Hip, orig: &impl PlaneSrc, factor: f32, orig
     Ok(stats_from_sys(&st))
 }
 
+// ---- the compose wizard's crop step, cmd/compose/crop.rs -----------------------------------------------------------------------------------------------------
+fn box_to_sys(b: (usize, usize, usize, usize)) -> sys::ab_crop_box {
+    sys::ab_crop_box { top: b.0 as u64, bottom: b.1 as u64, left: b.2 as u64, right: b.3 as u64 }
+}
+fn box_from_sys(b: &sys::ab_crop_box) -> (usize, usize, usize, usize) {
+    (b.top as usize, b.bottom as usize, b.left as usize, b.right as usize)
+}
+/// crop_array's clamp (crop.rs:65-69): the dims of the plane it returns
+fn cropped_dims(b: &sys::ab_crop_box, (rows, cols): (usize, usize)) -> (usize, usize) {
+    let (t, l) = ((b.top as usize).min(rows), (b.left as usize).min(cols));
+    ((b.bottom as usize).min(rows).max(t) - t, (b.right as usize).min(cols).max(l) - l)
+}
+/// drop-in for detect_valid_region (crop.rs:14-62): (top, bottom, left, right); only the four bounds cross to the host
+pub fn detect_valid_region(hip: &Hip, arr: &impl PlaneSrc, threshold: f32) -> Result<(usize, usize, usize, usize)> {
+    let mut b = box_to_sys((0, 0, 0, 0));
+    hip.check(unsafe { sys::ab_detect_valid_region(hip.ctx, &arr.ab(), threshold, &mut b) })?;
+    Ok(box_from_sys(&b))
+}
+/// the loop crop.rs:109-116 over planes of any dims in one launch chain: every plane's box and the running
+/// (max top, min bottom, max left, min right)
+pub fn detect_valid_regions<P: PlaneSrc>(hip: &Hip, arrs: &[P], threshold: f32) -> Result<(Vec<(usize, usize, usize, usize)>, (usize, usize, usize, usize))> {
+    let planes: Vec<_> = arrs.iter().map(|a| a.ab()).collect();
+    let mut each = vec![box_to_sys((0, 0, 0, 0)); planes.len()];
+    let mut common = box_to_sys((0, 0, 0, 0));
+    hip.check(unsafe { sys::ab_detect_valid_regions(hip.ctx, planes.as_ptr(), planes.len(), threshold, each.as_mut_ptr(), &mut common) })?;
+    Ok((each.iter().map(box_from_sys).collect(), box_from_sys(&common)))
+}
+/// drop-in for crop_array (crop.rs:64-71) on a host array
+pub fn crop_array(hip: &Hip, arr: &impl PlaneSrc, top: usize, bottom: usize, left: usize, right: usize) -> Result<Array2<f32>> {
+    let b = box_to_sys((top, bottom, left, right));
+    let mut out = Array2::<f32>::zeros(cropped_dims(&b, arr.dims()));
+    hip.check(unsafe { sys::ab_crop_array(hip.ctx, &arr.ab(), &b, &mut out.ab_mut()) })?;
+    Ok(out)
+}
+/// the same from HBM to HBM (asynchronous on the context's stream)
+pub fn crop_array_device(hip: &Hip, arr: &DevicePlane, top: usize, bottom: usize, left: usize, right: usize) -> Result<DevicePlane> {
+    let b = box_to_sys((top, bottom, left, right));
+    let (rows, cols) = cropped_dims(&b, arr.dims());
+    let mut out = DevicePlane::alloc(rows, cols)?;
+    hip.check(unsafe { sys::ab_crop_array(hip.ctx, &arr.ab(), &b, &mut out.ab_mut()) })?;
+    Ok(out)
+}
+/// What crop_channels_cmd's JSON needs besides its paths and keys (crop.rs:185-195): `dimensions` = [out_cols, out_rows].
+pub struct CropChannels<P> {
+    pub cropped: Vec<P>,
+    pub stats: Vec<ImageStats>,
+    pub dimensions: [usize; 2],
+    pub crop_top: usize,
+    pub crop_bottom: usize,
+    pub crop_left: usize,
+    pub crop_right: usize,
+    pub auto_detected: bool,
+}
+fn crop_plan(hip: &Hip, planes: &[sys::ab_plane], top: usize, bottom: usize, left: usize, right: usize, auto_detect: Option<bool>) -> Result<(sys::ab_crop_plan, Vec<u64>)> {
+    let mut cfg: sys::ab_crop_config = unsafe { std::mem::zeroed() };
+    unsafe { sys::ab_crop_config_default(&mut cfg) }; // AUTO_THRESHOLD (:12)
+    cfg.auto_detect = auto_detect.unwrap_or(true) as i32; // :101
+    (cfg.top, cfg.bottom, cfg.left, cfg.right) = (top as u64, bottom as u64, left as u64, right as u64);
+    let mut plan: sys::ab_crop_plan = unsafe { std::mem::zeroed() };
+    let mut dims = vec![0u64; 2 * planes.len()];
+    hip.check(unsafe { sys::ab_crop_channels_plan(hip.ctx, planes.as_ptr(), planes.len(), &cfg, &mut plan, dims.as_mut_ptr()) })?;
+    Ok((plan, dims))
+}
+fn crop_result<P>(plan: &sys::ab_crop_plan, cropped: Vec<P>, stats: &[sys::ab_image_stats]) -> CropChannels<P> {
+    CropChannels {
+        cropped,
+        stats: stats.iter().map(stats_from_sys).collect(),
+        dimensions: [plan.out_cols as usize, plan.out_rows as usize],
+        crop_top: plan.actual_top as usize,
+        crop_bottom: plan.actual_bottom as usize,
+        crop_left: plan.actual_left as usize,
+        crop_right: plan.actual_right as usize,
+        auto_detected: plan.auto_detected != 0,
+    }
+}
+/// drop-in for the pixel work of crop_channels_cmd (crop.rs:92-183) on host arrays: the box (auto or manual margins), every plane
+/// cropped, compute_image_stats of each; Err "No paths provided for cropping" / "Auto-crop found no valid overlapping region"
+pub fn crop_channels<P: PlaneSrc>(hip: &Hip, arrs: &[P], top: usize, bottom: usize, left: usize, right: usize, auto_detect: Option<bool>) -> Result<CropChannels<Array2<f32>>> {
+    let planes: Vec<_> = arrs.iter().map(|a| a.ab()).collect();
+    let (plan, dims) = crop_plan(hip, &planes, top, bottom, left, right, auto_detect)?;
+    let mut cropped: Vec<_> = dims.chunks(2).map(|d| Array2::<f32>::zeros((d[0] as usize, d[1] as usize))).collect();
+    let mut outs: Vec<_> = cropped.iter_mut().map(|c| c.ab_mut()).collect();
+    let mut stats: Vec<sys::ab_image_stats> = vec![unsafe { std::mem::zeroed() }; planes.len()];
+    hip.check(unsafe { sys::ab_crop_channels(hip.ctx, planes.as_ptr(), planes.len(), &plan, outs.as_mut_ptr(), stats.as_mut_ptr()) })?;
+    Ok(crop_result(&plan, cropped, &stats))
+}
+/// the same between planes that stay in HBM (align_channels_cmd's outputs in, blend_channels_cmd's inputs out): one detection
+/// chain, one crop launch, the statistics; nothing but the boxes and the statistics crosses to the host
+pub fn crop_channels_device(hip: &Hip, arrs: &[&DevicePlane], top: usize, bottom: usize, left: usize, right: usize, auto_detect: Option<bool>) -> Result<CropChannels<DevicePlane>> {
+    let planes: Vec<_> = arrs.iter().map(|a| a.ab()).collect();
+    let (plan, dims) = crop_plan(hip, &planes, top, bottom, left, right, auto_detect)?;
+    let mut cropped = dims.chunks(2).map(|d| DevicePlane::alloc(d[0] as usize, d[1] as usize)).collect::<Result<Vec<_>>>()?;
+    let mut outs: Vec<_> = cropped.iter_mut().map(|c| c.ab_mut()).collect();
+    let mut stats: Vec<sys::ab_image_stats> = vec![unsafe { std::mem::zeroed() }; planes.len()];
+    hip.check(unsafe { sys::ab_crop_channels(hip.ctx, planes.as_ptr(), planes.len(), &plan, outs.as_mut_ptr(), stats.as_mut_ptr()) })?;
+    Ok(crop_result(&plan, cropped, &stats))
+}
+
 // ---- a18  core/astrometry/spcc.rs ---------------------------------------------------------------------------------------------------------------------------
 fn spcc_cfg(config: &SpccConfig) -> sys::ab_spcc_config {
     let (kind, custom) = match config.white_reference {

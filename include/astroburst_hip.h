@@ -522,6 +522,55 @@ AB_API int ab_calibrate_channel(ab_ctx *ctx, const ab_plane *orig, float factor,
 AB_API int ab_create_master(ab_ctx *ctx, int32_t kind, const ab_plane *frames, size_t n_frames, const ab_plane *master_bias,
                             const ab_plane *master_dark, ab_plane_mut *out);
 
+/* ---- the compose wizard's crop step, cmd/compose/crop.rs (crop_channels_cmd: between align_channels_cmd and blend_channels_cmd) -- */
+/* Boxes are half open: rows [top, bottom), columns [left, right).  Inputs may be host or device planes of any float-aligned
+ * address and any dims with rows * cols < 2^31; a device plane is never downloaded, only the boxes (4 x u32 per plane) cross to the
+ * host.  Nothing here rounds: every result is the reference's, bit for bit. */
+typedef struct { uint64_t top, bottom, left, right; } ab_crop_box;
+/* detect_valid_region(arr, threshold) (crop.rs:14-62).  A pixel is valid iff |v| > threshold, strictly and in f32 (:20): a NaN
+ * pixel never is, +-inf are (unless the threshold is +inf), -0.0 only for a negative threshold; a NaN threshold makes nothing
+ * valid, a negative one every non-NaN pixel.  top = the first row holding a valid pixel (rows if none), bottom = the last such
+ * row + 1 (0 if none), left / right the same over the columns: a plane without a valid pixel gives (rows, 0, cols, 0), which is
+ * what the reference's four loops leave.  Synchronous (returns scalars). */
+AB_API int ab_detect_valid_region(ab_ctx *ctx, const ab_plane *img, float threshold, ab_crop_box *out);
+/* the loop crop.rs:109-116 over n planes, each measured with its own dims, up to 16 planes per launch: out_each[n] (nullable) and
+ * the running (max top, min bottom, max left, min right) out_common (nullable; (0, UINT64_MAX, 0, UINT64_MAX) for n = 0, :104-107).
+ * Synchronous. */
+AB_API int ab_detect_valid_regions(ab_ctx *ctx, const ab_plane *imgs, size_t n, float threshold, ab_crop_box *out_each,
+                                   ab_crop_box *out_common);
+/* crop_array(arr, top, bottom, left, right) (crop.rs:64-71): the box is clamped to src's dims as the reference clamps it,
+ * t = min(top, rows), b = max(min(bottom, rows), t), l = min(left, cols), r = max(min(right, cols), l); out must be
+ * (b - t) x (r - l) and dense.  A zero-area window is legal: nothing is written (out->data may then be NULL).  A host source is
+ * staged as the window's rows only.  Asynchronous on the context's stream for device planes. */
+AB_API int ab_crop_array(ab_ctx *ctx, const ab_plane *src, const ab_crop_box *box, ab_plane_mut *out);
+typedef struct { /* crop_channels_cmd's arguments (crop.rs:77-81) + the threshold */
+    int32_t auto_detect;               /* auto_detect.unwrap_or(true) (:101) */
+    uint64_t top, bottom, left, right; /* manual MARGINS: pixels removed from each side (:123-126) */
+    float threshold;                   /* AUTO_THRESHOLD (:12) */
+} ab_crop_config;
+AB_API void ab_crop_config_default(ab_crop_config *cfg); /* auto_detect 1, margins 0, threshold 1e-6f */
+typedef struct {
+    ab_crop_box crop_box;        /* (crop_top, crop_bottom, crop_left, crop_right), crop.rs:103-126 */
+    uint64_t out_rows, out_cols; /* plane 0's cropped dims, crop.rs:170-175 (the JSON's "dimensions" is [out_cols, out_rows]) */
+    uint64_t actual_top, actual_bottom, actual_left, actual_right; /* crop.rs:179-183: crop_box.top, rows0 - crop_box.bottom, crop_box.left,
+                                                                      cols0 - crop_box.right, the subtractions saturating */
+    int32_t auto_detected;
+} ab_crop_plan;
+/* crop.rs:92-126: decide the box.  Auto mode intersects the planes' valid regions (ab_detect_valid_regions with cfg->threshold):
+ * AB_ERR_INVALID "Auto-crop found no valid overlapping region" when min_bottom <= max_top || min_right <= max_left (:118-120).
+ * Manual mode: (top, rows0.saturating_sub(bottom), left, cols0.saturating_sub(right)) with plane 0's dims and no emptiness check.
+ * n = 0: AB_ERR_INVALID "No paths provided for cropping" (:92-94).  out_dims (nullable) [2 n] = (rows, cols) of each plane's
+ * cropped output (crop_array clamps per plane: planes of different dims give outputs of different dims), so that the caller can
+ * allocate.  Synchronous in auto mode; host arithmetic in manual mode. */
+AB_API int ab_crop_channels_plan(ab_ctx *ctx, const ab_plane *imgs, size_t n, const ab_crop_config *cfg, ab_crop_plan *plan,
+                                 uint64_t *out_dims);
+/* crop.rs:133-168 without the file and cache traffic: outs[i] = crop_array(imgs[i], plan->crop_box), up to 16 planes per launch;
+ * stats (nullable, n entries) = compute_image_stats(&cropped) through ab_compute_image_stats' own engine (exact select at
+ * <= 4 000 000 cropped pixels, the histogram route above), ImageStats::default() -- all zero -- for a zero-area plane, without a
+ * launch.  With stats = NULL and device planes the call is asynchronous on the context's stream. */
+AB_API int ab_crop_channels(ab_ctx *ctx, const ab_plane *imgs, size_t n, const ab_crop_plan *plan, ab_plane_mut *outs,
+                            ab_image_stats *stats);
+
 /* ---- FITS pixel codecs, infra/fits/reader.rs + writer.rs ------------------------------------------- */
 /* decode_pixels(data, bitpix, bscale, bzero) (reader.rs:42-101): big-endian BITPIX 8 / 16 / 32 / -32 / -64 -> f32,
  * `v as f64 * bscale + bzero` unless is_identity_scaling (:36-39).  `data` = the HDU's data unit as it sits in the

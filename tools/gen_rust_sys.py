@@ -25,6 +25,16 @@ PRIM = {   # C type -> (Rust type, size, align)
     "void": ("c_void", 0, 1), "unsigned": ("c_uint", 4, 4),
 }
 OPAQUE = ("ab_ctx", "ab_comm")
+# strict and reserved keywords of Rust 2021: none may stand as a field or parameter name (`box` is reserved, `r#box` would be legal but
+# a renamed identifier reads better in the wrappers)
+RUST_KEYWORDS = frozenset("""as async await break const continue crate dyn else enum extern false fn for if impl in let loop match mod move
+mut pub ref return self Self static struct super trait true type unsafe use where while abstract become box do final macro override priv
+try typeof unsized virtual yield union""".split())
+
+
+def rust_ident(name):
+    """a C field or parameter name as a Rust identifier: a keyword gets a trailing underscore"""
+    return name + "_" if name in RUST_KEYWORDS else name
 
 
 def strip_comments(text):
@@ -167,7 +177,7 @@ def generate():
                           structs, enums)
             for d in reversed(dims):
                 t = f"[{t}; {d}]"
-            L.append(f"    pub {fname}: {t}, // offset {off}")
+            L.append(f"    pub {rust_ident(fname)}: {t}, // offset {off}")
         L.append("}")
         L.append("")
     L.append('#[link(name = "astroburst_hip")]')
@@ -175,9 +185,7 @@ def generate():
     for ret, name, params in funcs:
         ps = []
         for ctype, ptr, pname, const in params:
-            if pname in ("type", "ref", "in", "fn", "box", "loop", "match", "move", "mod", "impl"):
-                pname += "_"
-            ps.append(f"{pname}: {rust_type(ctype, ptr, const, structs, enums)}")
+            ps.append(f"{rust_ident(pname)}: {rust_type(ctype, ptr, const, structs, enums)}")
         rt = ret.replace("const ", "").strip()
         if rt == "void":
             r = ""
