@@ -8,6 +8,7 @@ from ._lib import AstroBurstError, LIB_PATH, build, declared_symbols, is_dev_bui
 from .core import Comm, Context, ImageStats, PlaneList, PsfResult, PsfStar, StackResult, StfParams, psf_select_stars  # noqa: F401
 from .core import ASINH_ROUTE_AVX2, ASINH_ROUTE_SCALAR, AsinhStats  # noqa: F401
 from .core import RGB_PACK_8, RGB_PACK_8_ROUND, RGB_PACK_16BE, DrizzleRgbResult, ProcessedDrizzleRgb, RgbExportInfo, rgb_packed_bytes  # noqa: F401
+from .core import ToneInfo, ToneResult  # noqa: F401
 from .core import CROP_AUTO_THRESHOLD, CropBox, CropPlan  # noqa: F401
 from .core import SynthFrames, synth_chacha_block, synth_config, synth_noise_params, synth_psf_type, synth_rng_f64, synth_star_field  # noqa: F401
 

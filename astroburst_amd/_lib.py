@@ -281,6 +281,17 @@ class ProcessedDrizzleRgbInfoC(C.Structure):  # the scalars of ProcessedDrizzleR
                 ("stats_wb", ImageStatsC * 3), ("scnr_applied", C.c_int32)]
 
 
+class ToneConfigC(C.Structure):  # ab_tone_config: apply_tone_composite_cmd's arguments (cmd/processing/curves.rs:58-71)
+    _fields_ = [("has_stf", C.c_int32 * 3), ("stf", StfParamsC * 3), ("linked_stf", C.c_int32), ("levels", LevelsParamsC * 3),
+                ("curve_xy", C.POINTER(C.c_double) * 3), ("n_curve", C.c_size_t * 3), ("has_scnr", C.c_int32), ("scnr", ScnrConfigC)]
+
+
+class ToneInfoC(C.Structure):  # ab_tone_info: what the command decided (curves.rs:163-189)
+    _fields_ = [("stf", StfParamsC * 3), ("norm", ImageStatsC * 3), ("levels_applied", C.c_int32), ("curves_applied", C.c_int32),
+                ("scnr_applied", C.c_int32), ("rows", C.c_uint64), ("cols", C.c_uint64), ("preview_rows", C.c_uint64),
+                ("preview_cols", C.c_uint64)]
+
+
 class DrizzleResultC(C.Structure):  # DrizzleResult's scalars (drizzle.rs:335-344)
     _fields_ = [("frame_count", C.c_size_t), ("output_scale", C.c_double), ("in_rows", C.c_int64), ("in_cols", C.c_int64),
                 ("out_rows", C.c_int64), ("out_cols", C.c_int64), ("rejected_pixels", C.c_uint64)]
@@ -570,6 +581,10 @@ def lib() -> C.CDLL:
     L.ab_crop_config_default.restype = None
     L.ab_crop_channels_plan.argtypes = [vp, pp, C.c_size_t, C.POINTER(CropConfigC), C.POINTER(CropPlanC), u64p]
     L.ab_crop_channels.argtypes = [vp, pp, C.c_size_t, C.POINTER(CropPlanC), pmp, isp]
+    L.ab_tone_config_default.argtypes = [C.POINTER(ToneConfigC)]
+    L.ab_tone_config_default.restype = None
+    L.ab_tone_plan.argtypes = [isp, C.POINTER(ToneConfigC), C.POINTER(ToneInfoC), f32p]
+    L.ab_apply_tone_composite.argtypes = [vp, pp, pp, pp, isp, C.POINTER(ToneConfigC), C.c_int64, pmp, vp, C.c_int32, C.POINTER(ToneInfoC)]
     for name in declared_symbols():
         fn = getattr(L, name)  # AttributeError here = header / library drift
         if fn.restype is C.c_int and name not in ("ab_last_error", "ab_version", "ab_ctx_get_stream", "ab_comm_collectives_issued"):

@@ -218,6 +218,77 @@ class DrizzleRgbResult:  # types/compose.rs DrizzleRgbResult without its paths
     channels: tuple    # 3 x (frame_count, output_scale, in_dims, out_dims, rejected_pixels), None for a channel that is not there
 
 
+@dataclass
+class ToneInfo:  # what apply_tone_composite_cmd decided and reports (cmd/processing/curves.rs:163-189)
+    stf: tuple             # 3 x StfParams: what was applied (RES_STF)
+    norm: tuple            # 3 x ImageStats: what each channel was normalised with (the combined ones x 3 when linked)
+    levels_applied: bool
+    curves_applied: bool
+    scnr_applied: bool
+    rows: int              # 0 from tone_plan, which sees no plane
+    cols: int
+    preview_rows: int
+    preview_cols: int
+
+
+@dataclass
+class ToneResult:
+    planes: tuple          # (r, g, b) toned f32 planes of full size, or None
+    rgb8: object           # uint8 (preview_rows, preview_cols, 3), or None
+    info: ToneInfo
+
+
+def _tone_config(stf, linked_stf, levels, curves, scnr, keep):
+    """ab_tone_config of apply_tone_composite_cmd's arguments (cmd/processing/curves.rs:58-71).  stf: None or three of (None |
+    StfParams | (shadow, midtone, highlight)); levels: None or three of (None | (black, gamma, white)); curves: None or three of
+    (None | a list of (x, y), which may be empty: Some(points)); scnr: None or dict(method=, amount=, preserve_luminance=).  The
+    point arrays the configuration points at are appended to `keep`."""
+    cfg = _lib.ToneConfigC()
+    _lib.lib().ab_tone_config_default(C.byref(cfg))
+    for c, p in enumerate(stf or ()):
+        if p is not None:
+            cfg.has_stf[c] = 1
+            cfg.stf[c] = StfParamsC(*(p if isinstance(p, (tuple, list)) else (p.shadow, p.midtone, p.highlight)))
+    cfg.linked_stf = int(bool(linked_stf))
+    for c, p in enumerate(levels or ()):
+        if p is not None:
+            cfg.levels[c] = _lib.LevelsParamsC(*[float(v) for v in p])
+    for c, pts in enumerate(curves or ()):
+        if pts is not None:
+            n = len(pts)
+            xy = (C.c_double * max(2 * n, 2))(*[float(v) for p in pts for v in p])   # (Some([]) is a pointer all the same)
+            keep.append(xy)
+            cfg.curve_xy[c] = C.cast(xy, C.POINTER(C.c_double))
+            cfg.n_curve[c] = n
+    if scnr is not None:
+        cfg.has_scnr = 1
+        m = scnr.get("method", "average")
+        cfg.scnr = _lib.ScnrConfigC(0 if m in ("average", "AverageNeutral", 0) else 1, scnr.get("amount", 1.0),
+                                    int(bool(scnr.get("preserve_luminance", False))))
+    return cfg
+
+
+def _tone_info(info) -> ToneInfo:
+    return ToneInfo(tuple(StfParams(p.shadow, p.midtone, p.highlight) for p in info.stf),
+                    tuple(ImageStats(s.min, s.max, s.median, s.mad, s.sigma, s.mean, int(s.valid_count)) for s in info.norm),
+                    bool(info.levels_applied), bool(info.curves_applied), bool(info.scnr_applied), int(info.rows), int(info.cols),
+                    int(info.preview_rows), int(info.preview_cols))
+
+
+def tone_plan(stats, stf=None, linked_stf=False, levels=None, curves=None, scnr=None, want_luts=True):
+    """The decisions of apply_tone_composite_cmd (cmd/processing/curves.rs:86-154) without its pixels -> (ToneInfo, the three LUTs it
+    would apply as float32 (3, 4096), or None when no curve runs).  Host-only."""
+    keep = []
+    cfg = _tone_config(stf, linked_stf, levels, curves, scnr, keep)
+    st = (_lib.ImageStatsC * 3)(*[ImageStatsC(s.min, s.max, s.median, s.mad, s.sigma, s.mean, s.valid_count) for s in stats])
+    info = _lib.ToneInfoC()
+    luts = np.zeros((3, 4096), np.float32) if want_luts else None
+    rc = _lib.lib().ab_tone_plan(st, C.byref(cfg), C.byref(info), luts.ctypes.data_as(C.POINTER(C.c_float)) if want_luts else None)
+    if rc != _lib.AB_OK:
+        raise AstroBurstError(rc, "ab_tone_plan: bad arguments")
+    return _tone_info(info), (luts if want_luts and info.curves_applied else None)
+
+
 class CropBox(NamedTuple):  # detect_valid_region's tuple (cmd/compose/crop.rs:14-62): rows [top, bottom), columns [left, right)
     top: int
     bottom: int
@@ -2348,6 +2419,31 @@ class Context:
         chans = tuple(None if x.frame_count == 0 else (int(x.frame_count), float(x.output_scale), (int(x.in_rows), int(x.in_cols)),
                                                        (int(x.out_rows), int(x.out_cols)), int(x.rejected_pixels)) for x in res)
         return DrizzleRgbResult(self._processed_drizzle_rgb(None, wb, rgb8, info), chans)
+
+    # ---- cmd/processing/curves.rs: the compose wizard's tone editor ---------------------------------------------
+    tone_plan = staticmethod(tone_plan)
+
+    def apply_tone_composite(self, r, g, b, stats, stf=None, linked_stf=False, levels=None, curves=None, scnr=None, max_dim=4096,
+                             want_planes=False, want_rgb8=True, out=None) -> ToneResult:
+        """apply_tone_composite_cmd (cmd/processing/curves.rs:57-191) from its loaded channels to the encoder's input, fused: STF,
+        levels, curves, SCNR and the preview's pick and pack in one launch (two with want_planes on an image above max_dim).
+        stats: the three channels' ImageStats; stf, levels, curves, scnr: as tone_plan takes them.  want_planes: the three toned
+        f32 planes of full size as well.  out: the caller's byte buffer (contiguous uint8 of preview_rows * preview_cols * 3, any
+        address).  Outputs are of r's kind: numpy in -> numpy out, CUDA tensors in -> CUDA tensors out."""
+        keep = []
+        pr, pg, pb = (self._plane(x, keep) for x in (r, g, b))
+        rows, cols = int(pr.rows), int(pr.cols)
+        cfg = _tone_config(stf, linked_stf, levels, curves, scnr, keep)
+        st = (_lib.ImageStatsC * 3)(*[self._stats_in(s) for s in stats])
+        planes, pp = self._plane3(r, rows, cols, keep) if want_planes else (None, None)
+        rgb8, ptr, dev = None, None, 0
+        if want_rgb8 or out is not None:
+            ph, pw = self.preview_dims(rows, cols, max_dim) if max_dim > 0 else (1, 1)   # (max_dim < 1 is the library's AB_ERR_INVALID)
+            rgb8, ptr, dev = self._bytes_out(r, (ph, pw, 3), out)
+        info = _lib.ToneInfoC()
+        self._check(self._L.ab_apply_tone_composite(self._h, C.byref(pr), C.byref(pg), C.byref(pb), st, C.byref(cfg), int(max_dim), pp, ptr, dev,
+                                                    C.byref(info)))
+        return ToneResult(planes, rgb8, _tone_info(info))
 
     # ---- cmd/compose/crop.rs ---------------------------------------------------------------------------------
     @staticmethod

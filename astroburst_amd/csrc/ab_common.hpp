@@ -63,6 +63,7 @@ enum {
     AB_WS_CUBE,               // the device copy of a host-resident spectral cube, for the length of one call (cube.hip)
     AB_WS_PSF,                // PSF estimation: statistics partials, the candidate counter, the f64 / f32 kernel and its scalars (psf.hip)
     AB_WS_SYNTH,              // synthetic generator: star records, norms, tile lists, the frames' route flags (synth.hip)
+    AB_WS_TONE,               // the tone editor's three curve LUTs, 3 x 4096 f32 (tone.hip)
     AB_WS_SLOTS
 };
 
@@ -175,6 +176,10 @@ struct ab_ctx {
     int pc_tab_dims[2][2] = {{0, 0}, {0, 0}};
     const void *pc_tab_ws = nullptr;
     const void *fft_tab_ws = nullptr;  // spectrum.hip: the workspace its twiddle tables were built in
+    // tone.hip: the pinned copy of the three curve LUTs last uploaded, the event behind that upload, the workspace they went to
+    void *tone_lut_host = nullptr;
+    hipEvent_t tone_lut_ev = nullptr;
+    const void *tone_lut_ws = nullptr;
 };
 
 // stage boundary: AB_ERR_CANCELLED ("Operation cancelled") if the host asked to stop, else ticks the callback (if any)

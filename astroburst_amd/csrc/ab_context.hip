@@ -163,6 +163,8 @@ void ab_ctx_destroy(ab_ctx *ctx) {
     for (hipEvent_t e : ctx->stack_ev)
         if (e) (void)hipEventDestroy(e);
     if (ctx->switch_ev) (void)hipEventDestroy(ctx->switch_ev);
+    if (ctx->tone_lut_ev) (void)hipEventDestroy(ctx->tone_lut_ev);
+    if (ctx->tone_lut_host) (void)hipHostFree(ctx->tone_lut_host);
     for (hipEvent_t e : ctx->shard_ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->shard_tm) (void)hipEventDestroy(e);
     if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
@@ -218,6 +220,7 @@ int ab_ctx_trim(ab_ctx *ctx) try {
     ctx->pc_tab_ws = nullptr;  // (phase_corr.hip rebuilds its tables when the workspace pointer changes)
     ctx->fft_tab_ws = nullptr; // (spectrum.hip: the same for its twiddle tables)
     ctx->stats_bar = nullptr;  // (stats.hip clears the resident kernel's barrier flags when its workspace is new)
+    ctx->tone_lut_ws = nullptr;  // (tone.hip uploads its curve LUTs again)
     drop(ctx->upload_buf, ctx->upload_bytes, false, "hipFree(upload_buf)");
     // the pinned read-back buffers (they grow with the frame-group size: G * kSelCap selection records) and the declined-tile lists
     drop(ctx->pinned, ctx->pinned_bytes, true, "hipHostFree(pinned)");

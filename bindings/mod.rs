@@ -1495,6 +1495,112 @@ pub fn drizzle_rgb<P: PlaneSrc>(hip: &Hip, r: Option<&[P]>, g: Option<&[P]>, b: 
     })
 }
 
+// ---- the compose wizard's tone editor: cmd/processing/curves.rs (apply_tone_composite_cmd) ---------------------------------------------------------------------
+/// apply_tone_composite_cmd's arguments (cmd/processing/curves.rs:58-71) as the command receives them, (r, g, b) each
+#[derive(Clone, Debug, Default)]
+pub struct ToneConfig {
+    pub stf: [Option<[f64; 3]>; 3],
+    pub linked_stf: Option<bool>,
+    pub levels: [Option<LevelsParams>; 3],
+    pub curves: [Option<Vec<[f64; 2]>>; 3],
+    pub scnr: Option<ScnrConfig>,
+}
+/// what the command decided and reports (RES_STF, RES_LEVELS_APPLIED, RES_CURVES_APPLIED, RES_SCNR_APPLIED, :163-189)
+#[derive(Clone, Debug)]
+pub struct ToneInfo {
+    pub stf: [StfParams; 3],
+    pub norm: [ImageStats; 3],
+    pub levels_applied: bool,
+    pub curves_applied: bool,
+    pub scnr_applied: bool,
+    pub dims: (usize, usize),
+    pub preview_dims: (usize, usize),
+}
+/// the preview the command encodes: preview_dims.0 x preview_dims.1 x 3 interleaved bytes (RgbImage::from_raw's input)
+pub struct TonePreview {
+    pub pixels: Vec<u8>,
+    pub info: ToneInfo,
+}
+// `flat` holds the curves' points for as long as the configuration that points into it is in use
+fn tone_cfg(config: &ToneConfig, flat: &mut [Vec<f64>; 3]) -> sys::ab_tone_config {
+    let mut cfg: sys::ab_tone_config = unsafe { std::mem::zeroed() };
+    unsafe { sys::ab_tone_config_default(&mut cfg) };
+    for c in 0..3 {
+        if let Some(a) = config.stf[c] {
+            cfg.has_stf[c] = 1;
+            cfg.stf[c] = sys::ab_stf_params { shadow: a[0], midtone: a[1], highlight: a[2] };
+        }
+        if let Some(l) = config.levels[c].as_ref() {
+            cfg.levels[c] = sys::ab_levels_params { black: l.black, gamma: l.gamma, white: l.white };
+        }
+        if let Some(points) = config.curves[c].as_ref() {
+            flat[c] = points.iter().flat_map(|p| [p[0], p[1]]).collect();
+            flat[c].reserve(1); // Some(vec![]) is a pointer all the same: NULL means None
+            cfg.curve_xy[c] = flat[c].as_mut_ptr();
+            cfg.n_curve[c] = points.len();
+        }
+    }
+    cfg.linked_stf = config.linked_stf.unwrap_or(false) as i32;
+    if let Some(s) = config.scnr.as_ref() {
+        cfg.has_scnr = 1;
+        cfg.scnr = scnr_to_sys(s);
+    }
+    cfg
+}
+fn tone_info(info: &sys::ab_tone_info) -> ToneInfo {
+    ToneInfo {
+        stf: [stf_from_sys(&info.stf[0]), stf_from_sys(&info.stf[1]), stf_from_sys(&info.stf[2])],
+        norm: [stats_from_sys(&info.norm[0]), stats_from_sys(&info.norm[1]), stats_from_sys(&info.norm[2])],
+        levels_applied: info.levels_applied != 0,
+        curves_applied: info.curves_applied != 0,
+        scnr_applied: info.scnr_applied != 0,
+        dims: (info.rows as usize, info.cols as usize),
+        preview_dims: (info.preview_rows as usize, info.preview_cols as usize),
+    }
+}
+/// the command's decisions without its pixels (:86-154); host-only
+pub fn tone_plan(stats: &[ImageStats; 3], config: &ToneConfig) -> Result<ToneInfo> {
+    let mut flat: [Vec<f64>; 3] = Default::default();
+    let cfg = tone_cfg(config, &mut flat);
+    let s = [stats_to_sys(&stats[0]), stats_to_sys(&stats[1]), stats_to_sys(&stats[2])];
+    let mut info: sys::ab_tone_info = unsafe { std::mem::zeroed() };
+    if unsafe { sys::ab_tone_plan(s.as_ptr(), &cfg, &mut info, std::ptr::null_mut()) } != 0 {
+        bail!("the tone plan could not be computed");
+    }
+    Ok(tone_info(&info))
+}
+/// apply_tone_composite_cmd (cmd/processing/curves.rs:57-191) from its loaded channels to the encoder's input in one launch: STF, levels,
+/// curves, SCNR and render_rgb_preview's pick and pack, only at the pixels the preview shows when the composite exceeds max_dim
+pub fn apply_tone_composite(hip: &Hip, r: &impl PlaneSrc, g: &impl PlaneSrc, b: &impl PlaneSrc, stats: &[ImageStats; 3], config: &ToneConfig, max_dim: usize) -> Result<TonePreview> {
+    let (rows, cols) = r.dims();
+    let (ph, pw) = preview_dims(rows, cols, max_dim);
+    let mut flat: [Vec<f64>; 3] = Default::default();
+    let cfg = tone_cfg(config, &mut flat);
+    let s = [stats_to_sys(&stats[0]), stats_to_sys(&stats[1]), stats_to_sys(&stats[2])];
+    let mut pixels = vec![0u8; ph * pw * 3];
+    let mut info: sys::ab_tone_info = unsafe { std::mem::zeroed() };
+    hip.check(unsafe {
+        sys::ab_apply_tone_composite(hip.ctx, &r.ab(), &g.ab(), &b.ab(), s.as_ptr(), &cfg, max_dim as i64, std::ptr::null_mut(), pixels.as_mut_ptr(), 0, &mut info)
+    })?;
+    Ok(TonePreview { pixels, info: tone_info(&info) })
+}
+/// the same with the three toned planes the command drops (r_img, g_img, b_img) as well: two launches when the composite exceeds max_dim
+pub fn apply_tone_composite_planes(hip: &Hip, r: &impl PlaneSrc, g: &impl PlaneSrc, b: &impl PlaneSrc, stats: &[ImageStats; 3], config: &ToneConfig, max_dim: usize) -> Result<([Array2<f32>; 3], TonePreview)> {
+    let (rows, cols) = r.dims();
+    let (ph, pw) = preview_dims(rows, cols, max_dim);
+    let mut flat: [Vec<f64>; 3] = Default::default();
+    let cfg = tone_cfg(config, &mut flat);
+    let s = [stats_to_sys(&stats[0]), stats_to_sys(&stats[1]), stats_to_sys(&stats[2])];
+    let mut planes = planes3(rows, cols);
+    let mut pp = [planes[0].ab_mut(), planes[1].ab_mut(), planes[2].ab_mut()];
+    let mut pixels = vec![0u8; ph * pw * 3];
+    let mut info: sys::ab_tone_info = unsafe { std::mem::zeroed() };
+    hip.check(unsafe {
+        sys::ab_apply_tone_composite(hip.ctx, &r.ab(), &g.ab(), &b.ab(), s.as_ptr(), &cfg, max_dim as i64, pp.as_mut_ptr(), pixels.as_mut_ptr(), 0, &mut info)
+    })?;
+    Ok((planes, TonePreview { pixels, info: tone_info(&info) }))
+}
+
 // ---- a13  core/imaging/star_mask.rs, masked_stretch.rs -------------------------------------------------------------------------------------------------
 /// drop-in for generate_star_mask (star_mask.rs:38-44)
 pub fn generate_star_mask(hip: &Hip, image: &impl PlaneSrc, config: &StarMaskConfig) -> Result<StarMaskResult, String> {

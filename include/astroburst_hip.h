@@ -1220,6 +1220,56 @@ AB_API int ab_drizzle_rgb(ab_ctx *ctx, const ab_plane *r_frames, size_t n_r, con
                           size_t n_b, const ab_drizzle_config *dcfg, const ab_drizzle_rgb_config *cfg, ab_plane_mut *out_wb, uint8_t *out_rgb8,
                           int32_t out_on_device, ab_drizzle_result res[3], ab_processed_drizzle_rgb_info *info);
 
+/* ---- the compose wizard's tone editor: cmd/processing/curves.rs (apply_tone_composite_cmd :57-191) up to the PNG encoder ------- */
+/* Every move of an STF, levels, curves or SCNR slider runs apply_stf_f32 x 3 (:113-119), apply_levels_rgb (:121-131), apply_curve_rgb
+ * (:133-146), apply_scnr_inplace (:148-154) and render_rgb_preview(.., MAX_PREVIEW_DIM) (:161, cmd/helpers.rs:204-262) over the whole
+ * composite and keeps only the preview's bytes.  Every stage is pointwise, so one kernel family (csrc/tone.hip) runs the chain in
+ * registers: 12 B read and 3 B written per pixel.  When the composite exceeds max_dim on a side and no plane is wanted, only the pixels
+ * the preview picks are toned at all.  Each stage is the arithmetic of the entry point it stands for (ab_apply_stf_f32, ab_apply_levels,
+ * ab_apply_curve, ab_apply_scnr_inplace, ab_render_rgb_preview with stf == NULL): planes and bytes are bit for bit that chain's. */
+typedef struct {                /* apply_tone_composite_cmd's arguments, cmd/processing/curves.rs:58-71 */
+    int32_t has_stf[3];         /* stf_r / stf_g / stf_b: Option<[f64; 3]> (:60-62) */
+    ab_stf_params stf[3];       /* {shadow, midtone, highlight} = a[0], a[1], a[2] (:103-111) */
+    int32_t linked_stf;         /* Option<bool>.unwrap_or(false) (:87) */
+    ab_levels_params levels[3]; /* levels_r / _g / _b (:64-66); absent = LevelsParams::default() = {0, 1, 1} (:121-123) */
+    const double *curve_xy[3];  /* curves_r / _g / _b: Option<ToneCurveInput> (:67-69): NULL = None; else n_curve[c] (x, y) pairs (n may be 0) */
+    size_t n_curve[3];
+    int32_t has_scnr;           /* Option<ScnrConfig> (:70) */
+    ab_scnr_config scnr;
+} ab_tone_config;
+typedef struct {
+    ab_stf_params stf[3];       /* what was applied (RES_STF, :171-187) */
+    ab_image_stats norm[3];     /* the statistics each channel was normalised with (:89-101; the combined ones x 3 when linked) */
+    int32_t levels_applied, curves_applied, scnr_applied; /* RES_LEVELS_APPLIED, RES_CURVES_APPLIED, RES_SCNR_APPLIED (:168-170) */
+    uint64_t rows, cols, preview_rows, preview_cols;      /* 0 from ab_tone_plan, which sees no plane */
+} ab_tone_info;
+AB_API void ab_tone_config_default(ab_tone_config *cfg); /* nothing explicit, unlinked, levels {0, 1, 1}, no curves, no SCNR */
+/* Host only: the command's decisions, and the three LUTs it would apply (lut3x4096 nullable; written only when curves_applied).
+ *   STF     unlinked: auto_stf(stats[c], AutoStfConfig::default()), normalised with stats[c] (:92-100).  linked: the combined statistics
+ *           and the one STF of compute_linked_stf_with_stats (:89-91, helpers.rs:185-202 = ab_compute_linked_stf) for all three.  An
+ *           explicit stf[c] replaces channel c's parameters, never the statistics it is normalised with (:103-111).
+ *   levels  applied when any channel is not LevelsParams::is_identity (:125; core/imaging/curves.rs:18-22: |black|, |gamma - 1| and
+ *           |white - 1| all below 1e-7).  apply_levels then runs per channel (:127): a channel that is itself identity is CLONED
+ *           (core/imaging/curves.rs:32-34) and keeps the NaN, infinity or negative value another channel sends to 0 (:46).
+ *   curves  a channel is identity when it is None or SplineLut::is_identity(points) (:133-135; core/imaging/curves.rs:94-103: more
+ *           than two points never; none always; one when |x - y| < 1e-6; two when they lie within 1e-6 of (0, 0) and (1, 1)).  All
+ *           three identity: no curve runs (:136-138).  Else EVERY channel is looked up (:139-142): Some(points) in
+ *           from_points(points) -- "identity" points included -- and None in from_points([(0, 0), (1, 1)]) (:53-55), which is no
+ *           identity map: it truncates to 4096 levels and sends non-finite and negative values to 0 (core/imaging/curves.rs:105-109, :192).
+ *   SCNR    has_scnr && amount > 1e-7 (:149). */
+AB_API int ab_tone_plan(const ab_image_stats stats[3], const ab_tone_config *cfg, ab_tone_info *info, float *lut3x4096);
+/* The command from its loaded channels (:76-84: r, g, b and their ImageStats) to the encoder's input.  r, g, b: one size, host or
+ * device, any float-aligned address.  out_planes (nullable): three planes of that size, host or device -- the r_img, g_img, b_img the
+ * command drops.  out_rgb8 (nullable): preview_rows x preview_cols x 3 bytes with the dims of ab_preview_dims(rows, cols, max_dim), host
+ * or device (out_on_device) at ANY byte address: the pick ((d as f64) * ratio).min((n - 1) as f64) as usize (helpers.rs:306-309) and
+ * the byte (v.clamp(0, 1) * 255f32) as u8 (helpers.rs:243-245; NaN -> 0) of ab_render_rgb_preview with stf == NULL.  An output may
+ * not overlap an input.  A mismatch of the planes' dims, rows * cols >= 2^31, max_dim < 1 or both outputs NULL -> AB_ERR_INVALID
+ * before anything touches the device.  One launch; two (full-size planes, then the pick) when out_planes is given and the image
+ * exceeds max_dim.  Asynchronous when inputs and outputs are on the device (the LUTs travel through a pinned buffer of the context). */
+AB_API int ab_apply_tone_composite(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, const ab_image_stats stats[3],
+                                   const ab_tone_config *cfg, int64_t max_dim, ab_plane_mut *out_planes, uint8_t *out_rgb8,
+                                   int32_t out_on_device, ab_tone_info *info);
+
 /* ---- bench support: a plain float4 device copy, the measured HBM ceiling ---- */
 AB_API int ab_bench_copy(ab_ctx *ctx, const float *src_dev, float *dst_dev, size_t n_floats);
 
