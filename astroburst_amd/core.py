@@ -1889,13 +1889,13 @@ class Context:
                                     luminance_ceiling)
 
     def generate_star_mask(self, image, growth_factor=2.5, softness=4.0, detection_sigma=5.0, min_fwhm=1.5, max_fwhm=30.0,
-                           luminance_protect=False, luminance_ceiling=0.85, stars=None) -> StarMaskResult:
+                           luminance_protect=False, luminance_ceiling=0.85, stars=None, out=None) -> StarMaskResult:
         """generate_star_mask (star_mask.rs:38-44); with stars=[DetectedStar | (x, y, fwhm)] it is
-        generate_star_mask_from_detection (:46-138) on that detection."""
+        generate_star_mask_from_detection (:46-138) on that detection.  out: the mask's plane (allocated like the image when None)."""
         keep = []
         pi = self._plane(image, keep)
-        mask = self._new_like(image, pi.rows, pi.cols)
-        pm = self._out_plane(mask, keep, pi.rows, pi.cols)
+        mask = self._new_like(image, pi.rows, pi.cols) if out is None else out
+        pm = self._out_plane(mask, keep, mask.shape[0], mask.shape[1])
         cfg = self._mask_cfg(growth_factor, softness, detection_sigma, min_fwhm, max_fwhm, luminance_protect, luminance_ceiling)
         info = _lib.StarMaskInfoC()
         if stars is None:
@@ -1921,12 +1921,14 @@ class Context:
 
     def masked_stretch(self, image, iterations=10, target_background=0.25, mask_growth=2.5, mask_softness=4.0,
                        luminance_protect=True, luminance_ceiling=0.85, protection_amount=0.85, convergence_threshold=1e-5,
-                       mask: "StarMaskResult | None" = None) -> MaskedStretchResult:
-        """masked_stretch (masked_stretch.rs:44-58); with mask=StarMaskResult it is masked_stretch_with_mask (:60-118)."""
+                       mask: "StarMaskResult | None" = None, out=None) -> MaskedStretchResult:
+        """masked_stretch (masked_stretch.rs:44-58); with mask=StarMaskResult it is masked_stretch_with_mask (:60-118).  out: the
+        stretched plane (allocated like the image when None)."""
         keep = []
         pi = self._plane(image, keep)
-        out = self._new_like(image, pi.rows, pi.cols)
-        po = self._out_plane(out, keep, pi.rows, pi.cols)
+        if out is None:
+            out = self._new_like(image, pi.rows, pi.cols)
+        po = self._out_plane(out, keep, out.shape[0], out.shape[1])
         cfg = self._ms_cfg(iterations, target_background, mask_growth, mask_softness, luminance_protect, luminance_ceiling,
                            protection_amount, convergence_threshold)
         res = _lib.MaskedStretchResultC()
@@ -1941,12 +1943,14 @@ class Context:
 
     def masked_stretch_rgb_shared(self, r, g, b, iterations=10, target_background=0.25, mask_growth=2.5, mask_softness=4.0,
                                   luminance_protect=True, luminance_ceiling=0.85, protection_amount=0.85,
-                                  convergence_threshold=1e-5):
-        """masked_stretch_rgb_shared (masked_stretch.rs:155-193) -> (res_r, res_g, res_b, shared StarMask scalars)."""
+                                  convergence_threshold=1e-5, outs=None):
+        """masked_stretch_rgb_shared (masked_stretch.rs:155-193) -> (res_r, res_g, res_b, shared StarMask scalars).  outs: the three
+        stretched planes (allocated like their channels when None)."""
         keep = []
         ps = [self._plane(x, keep) for x in (r, g, b)]
-        outs = [self._new_like(x, p.rows, p.cols) for x, p in zip((r, g, b), ps)]
-        pos = [self._out_plane(o, keep, p.rows, p.cols) for o, p in zip(outs, ps)]
+        if outs is None:
+            outs = [self._new_like(x, p.rows, p.cols) for x, p in zip((r, g, b), ps)]
+        pos = [self._out_plane(o, keep, o.shape[0], o.shape[1]) for o in outs]
         cfg = self._ms_cfg(iterations, target_background, mask_growth, mask_softness, luminance_protect, luminance_ceiling,
                            protection_amount, convergence_threshold)
         res = (_lib.MaskedStretchResultC * 3)()

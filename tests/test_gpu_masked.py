@@ -151,6 +151,8 @@ def test_a_large_iteration_ceiling_costs_what_the_loop_runs(ctx, oracle):
     m_or = oracle.generate_star_mask(img, stars=stars, luminance_protect=True)
     m_gp = ctx.generate_star_mask(img, stars=stars, luminance_protect=True)
     want = oracle.masked_stretch(img, mask=m_or, iterations=200000)
+    # (the loop stops after 3 iterations on this field: the enqueue never reaches its second chunk here.  Loops that do -- running out
+    # or stopping by their own decision in the second and third chunk -- are tests/test_gpu_masked_adversarial.py's M-long family)
     assert want.iterations_run < 64
     t0 = time.perf_counter()
     got = ctx.masked_stretch(img, mask=m_gp, iterations=200000)
