@@ -10,6 +10,7 @@ from .core import ASINH_ROUTE_AVX2, ASINH_ROUTE_SCALAR, AsinhStats  # noqa: F401
 from .core import RGB_PACK_8, RGB_PACK_8_ROUND, RGB_PACK_16BE, DrizzleRgbResult, ProcessedDrizzleRgb, RgbExportInfo, rgb_packed_bytes  # noqa: F401
 from .core import ToneInfo, ToneResult  # noqa: F401
 from .core import CROP_AUTO_THRESHOLD, CropBox, CropPlan  # noqa: F401
+from .core import FitsView, RgbFitsView, downsample_histogram, histogram_bin_edges  # noqa: F401
 from .core import SynthFrames, synth_chacha_block, synth_config, synth_noise_params, synth_psf_type, synth_rng_f64, synth_star_field  # noqa: F401
 
 __version__ = "0.2.0"

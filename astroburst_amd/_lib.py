@@ -292,6 +292,19 @@ class ToneInfoC(C.Structure):  # ab_tone_info: what the command decided (curves.
                 ("preview_cols", C.c_uint64)]
 
 
+class FitsViewConfigC(C.Structure):  # ab_fits_view_config: AutoStfConfig + HISTOGRAM_BINS_DISPLAY (cmd/io/mod.rs:26, :144)
+    _fields_ = [("stf", AutoStfConfigC), ("hist_bins", C.c_size_t)]
+
+
+class FitsViewInfoC(C.Structure):  # ab_fits_view_info: what process_fits_full's JSON reports (cmd/io/mod.rs:151-170)
+    _fields_ = [("rows", C.c_uint64), ("cols", C.c_uint64), ("stats", ImageStatsC), ("stf", StfParamsC), ("hist_len", C.c_uint64)]
+
+
+class RgbFitsViewInfoC(C.Structure):  # ab_rgb_fits_view_info: process_rgb_fits' (cmd/io/mod.rs:71-99)
+    _fields_ = [("rows", C.c_uint64), ("cols", C.c_uint64), ("preview_rows", C.c_uint64), ("preview_cols", C.c_uint64),
+                ("stats", ImageStatsC * 3), ("stf", StfParamsC * 3), ("hist_len", C.c_uint64)]
+
+
 class DrizzleResultC(C.Structure):  # DrizzleResult's scalars (drizzle.rs:335-344)
     _fields_ = [("frame_count", C.c_size_t), ("output_scale", C.c_double), ("in_rows", C.c_int64), ("in_cols", C.c_int64),
                 ("out_rows", C.c_int64), ("out_cols", C.c_int64), ("rejected_pixels", C.c_uint64)]
@@ -585,6 +598,14 @@ def lib() -> C.CDLL:
     L.ab_tone_config_default.restype = None
     L.ab_tone_plan.argtypes = [isp, C.POINTER(ToneConfigC), C.POINTER(ToneInfoC), f32p]
     L.ab_apply_tone_composite.argtypes = [vp, pp, pp, pp, isp, C.POINTER(ToneConfigC), C.c_int64, pmp, vp, C.c_int32, C.POINTER(ToneInfoC)]
+    u32p, fvc = C.POINTER(C.c_uint32), C.POINTER(FitsViewConfigC)
+    L.ab_downsample_histogram.argtypes = [u32p, C.c_size_t, C.c_size_t, u32p, C.POINTER(C.c_size_t)]
+    L.ab_histogram_bin_edges.argtypes = [C.c_double, C.c_double, C.c_size_t, C.POINTER(C.c_double)]
+    L.ab_display_histogram.argtypes = [vp, pp, C.c_double, C.c_double, C.c_size_t, vp, C.c_int32, C.POINTER(C.c_size_t)]
+    L.ab_fits_view_config_default.argtypes = [fvc]
+    L.ab_fits_view_config_default.restype = None
+    L.ab_process_fits_view.argtypes = [vp, pp, fvc, vp, C.c_int32, vp, C.c_int32, C.POINTER(FitsViewInfoC)]
+    L.ab_process_rgb_fits_view.argtypes = [vp, pp, pp, pp, fvc, C.c_int64, vp, C.c_int32, vp, C.c_int32, C.POINTER(RgbFitsViewInfoC)]
     for name in declared_symbols():
         fn = getattr(L, name)  # AttributeError here = header / library drift
         if fn.restype is C.c_int and name not in ("ab_last_error", "ab_version", "ab_ctx_get_stream", "ab_comm_collectives_issued"):

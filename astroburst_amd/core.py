@@ -289,6 +289,53 @@ def tone_plan(stats, stf=None, linked_stf=False, levels=None, curves=None, scnr=
     return _tone_info(info), (luts if want_luts and info.curves_applied else None)
 
 
+@dataclass
+class FitsView:  # what process_fits / process_fits_full hand to the encoder and the JSON (cmd/io/mod.rs:105-172)
+    u8: object             # uint8 (rows, cols): apply_stf's bytes
+    bins: object           # uint32 (hist_len,): the display histogram, or None (hist_bins = 0)
+    rows: int
+    cols: int
+    stats: object          # ImageStats, or None (fetch=False)
+    stf: object            # StfParams, or None
+
+
+@dataclass
+class RgbFitsView:  # process_rgb_fits' (cmd/io/mod.rs:33-102)
+    rgb8: object           # uint8 (preview_rows, preview_cols, 3), or None
+    bins: object           # uint32 (hist_len,): the display histogram of R, or None
+    rows: int
+    cols: int
+    preview_rows: int
+    preview_cols: int
+    stats: object          # 3 x ImageStats, or None (fetch=False)
+    stf: object            # 3 x StfParams, or None
+
+
+HISTOGRAM_BINS = 65536     # stats.rs:8: what compute_histogram_with_stats builds before the fold
+
+
+def downsample_histogram(bins, target_bins: int) -> np.ndarray:
+    """downsample_histogram (core/imaging/stats.rs:423-444), host only: saturating u32 sums of the source ranges the reference's
+    f64 ratio picks -- the dropped last source bin of e.g. 65536 -> 49 included."""
+    src = np.ascontiguousarray(bins, dtype=np.uint32)
+    out = np.zeros(max(1, min(int(target_bins), src.size)), np.uint32)
+    n = C.c_size_t(0)
+    u32p = C.POINTER(C.c_uint32)
+    rc = _lib.lib().ab_downsample_histogram(src.ctypes.data_as(u32p), src.size, int(target_bins), out.ctypes.data_as(u32p), C.byref(n))
+    if rc != _lib.AB_OK:
+        raise AstroBurstError(rc, "ab_downsample_histogram: no source bins or target_bins == 0")
+    return out[:n.value]
+
+
+def histogram_bin_edges(dmin: float, dmax: float, bins: int) -> np.ndarray:
+    """Histogram.bin_edges of build_histogram (stats.rs:379-387, :412-413), host only: bins + 1 doubles."""
+    out = np.zeros(max(int(bins), 0) + 1, np.float64)
+    rc = _lib.lib().ab_histogram_bin_edges(float(dmin), float(dmax), int(bins), out.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc != _lib.AB_OK:
+        raise AstroBurstError(rc, "ab_histogram_bin_edges: bins == 0")
+    return out
+
+
 class CropBox(NamedTuple):  # detect_valid_region's tuple (cmd/compose/crop.rs:14-62): rows [top, bottom), columns [left, right)
     top: int
     bottom: int
@@ -2448,6 +2495,95 @@ class Context:
         self._check(self._L.ab_apply_tone_composite(self._h, C.byref(pr), C.byref(pg), C.byref(pb), st, C.byref(cfg), int(max_dim), pp, ptr, dev,
                                                     C.byref(info)))
         return ToneResult(planes, rgb8, _tone_info(info))
+
+    # ---- cmd/io/mod.rs: opening a file (process_fits, process_fits_full, process_rgb_fits) and the histogram panel ------------
+    downsample_histogram = staticmethod(downsample_histogram)
+    histogram_bin_edges = staticmethod(histogram_bin_edges)
+
+    def _bins_out(self, like, n, out=None):
+        """the display bins next to the input: an int32 CUDA tensor for device planes (torch has no arithmetic on uint32; a count is
+        below 2^31, so the words are the same), a uint32 numpy array for host planes -> (array, ptr, on_device); or the caller's"""
+        if out is not None:
+            if _is_torch(out):
+                ok = out.is_cuda and out.dtype in (torch.int32, torch.uint32) and out.is_contiguous() and out.numel() >= n
+                return self._bins_ok(ok, n), out, C.c_void_p(out.data_ptr()), 1
+            ok = isinstance(out, np.ndarray) and out.dtype == np.uint32 and out.flags.c_contiguous and out.size >= n
+            return self._bins_ok(ok, n), out, C.c_void_p(out.ctypes.data if ok else 0), 0
+        if _is_torch(like) and like.is_cuda:
+            out = torch.empty((n,), dtype=torch.int32, device=like.device)
+            return None, out, C.c_void_p(out.data_ptr()), 1
+        out = np.zeros(n, np.uint32)
+        return None, out, C.c_void_p(out.ctypes.data), 0
+
+    @staticmethod
+    def _bins_ok(ok, n):
+        if not ok:
+            raise AstroBurstError(_lib.AB_ERR_INVALID, f"the bin output must be contiguous, 32-bit and hold {n} words")
+
+    def display_histogram(self, image, dmin: float, dmax: float, target_bins: int = 512, out=None):
+        """downsample_histogram(compute_histogram_with_stats(image, {min, max}), target_bins) (stats.rs:373-376, :423-444) in one pass
+        -> min(target_bins, 65536) bins: uint32 numpy for a host plane, int32 CUDA (asynchronous) for a device plane, or `out`."""
+        keep = []
+        pi = self._plane(image, keep)
+        n = max(1, min(int(target_bins), HISTOGRAM_BINS))
+        _, bins, ptr, dev = self._bins_out(image, n, out)
+        got = C.c_size_t(0)
+        self._check(self._L.ab_display_histogram(self._h, C.byref(pi), float(dmin), float(dmax), int(target_bins), ptr, dev, C.byref(got)))
+        return bins[:got.value]
+
+    @staticmethod
+    def _view_config(hist_bins, target_bg, shadow_k):
+        cfg = _lib.FitsViewConfigC()
+        _lib.lib().ab_fits_view_config_default(C.byref(cfg))
+        cfg.hist_bins = int(hist_bins)
+        if target_bg is not None:
+            cfg.stf.target_bg = float(target_bg)
+        if shadow_k is not None:
+            cfg.stf.shadow_k = float(shadow_k)
+        return cfg
+
+    def process_fits_view(self, image, hist_bins: int = 512, target_bg=None, shadow_k=None, fetch=True, out=None, out_bins=None) -> FitsView:
+        """The mono branch of process_fits_full (cmd/io/mod.rs:138-144) as one chain: compute_image_stats -> auto_stf -> apply_stf and
+        the display histogram in the same pass.  hist_bins=0: process_fits, no histogram.  fetch=False with device outputs keeps the
+        call asynchronous (stats and stf are then None).  Outputs are of the image's kind unless `out` / `out_bins` are given."""
+        keep = []
+        pi = self._plane(image, keep)
+        rows, cols = int(pi.rows), int(pi.cols)
+        cfg = self._view_config(hist_bins, target_bg, shadow_k)
+        u8, ptr, dev = self._bytes_out(image, (rows, cols), out)
+        nb = min(int(hist_bins), HISTOGRAM_BINS)
+        _, bins, bptr, bdev = self._bins_out(image, nb, out_bins) if nb > 0 else (None, None, None, 0)
+        info = _lib.FitsViewInfoC()
+        self._check(self._L.ab_process_fits_view(self._h, C.byref(pi), C.byref(cfg), ptr, dev, bptr, bdev, C.byref(info) if fetch else None))
+        if bins is not None:
+            bins = bins[:nb]
+        if not fetch:
+            return FitsView(u8, bins, rows, cols, None, None)
+        return FitsView(u8, bins, int(info.rows), int(info.cols), self._stats_out(info.stats),
+                        StfParams(info.stf.shadow, info.stf.midtone, info.stf.highlight))
+
+    def process_rgb_fits_view(self, r, g, b, hist_bins: int = 512, max_dim: int = 4096, target_bg=None, shadow_k=None, fetch=True, want_rgb8=True,
+                              out=None, out_bins=None) -> RgbFitsView:
+        """process_rgb_fits from its three planes on (cmd/io/mod.rs:44-62) as one chain: statistics and auto_stf per channel (unlinked),
+        apply_stf_f32 and render_rgb_preview(.., max_dim) fused into one packer, the display histogram of R riding in it.  fetch=False
+        with device outputs keeps the call asynchronous."""
+        keep = []
+        pr, pg, pb = (self._plane(x, keep) for x in (r, g, b))
+        rows, cols = int(pr.rows), int(pr.cols)
+        cfg = self._view_config(hist_bins, target_bg, shadow_k)
+        ph, pw = self.preview_dims(rows, cols, max_dim) if max_dim > 0 else (1, 1)   # (max_dim < 1 is the library's AB_ERR_INVALID)
+        rgb8, ptr, dev = self._bytes_out(r, (ph, pw, 3), out) if (want_rgb8 or out is not None) else (None, None, 0)
+        nb = min(int(hist_bins), HISTOGRAM_BINS)
+        _, bins, bptr, bdev = self._bins_out(r, nb, out_bins) if nb > 0 else (None, None, None, 0)
+        info = _lib.RgbFitsViewInfoC()
+        self._check(self._L.ab_process_rgb_fits_view(self._h, C.byref(pr), C.byref(pg), C.byref(pb), C.byref(cfg), int(max_dim), ptr, dev, bptr, bdev,
+                                                     C.byref(info) if fetch else None))
+        if bins is not None:
+            bins = bins[:nb]
+        if not fetch:
+            return RgbFitsView(rgb8, bins, rows, cols, ph, pw, None, None)
+        return RgbFitsView(rgb8, bins, int(info.rows), int(info.cols), int(info.preview_rows), int(info.preview_cols),
+                           tuple(self._stats_out(s) for s in info.stats), tuple(StfParams(p.shadow, p.midtone, p.highlight) for p in info.stf))
 
     # ---- cmd/compose/crop.rs ---------------------------------------------------------------------------------
     @staticmethod

@@ -64,6 +64,7 @@ enum {
     AB_WS_PSF,                // PSF estimation: statistics partials, the candidate counter, the f64 / f32 kernel and its scalars (psf.hip)
     AB_WS_SYNTH,              // synthetic generator: star records, norms, tile lists, the frames' route flags (synth.hip)
     AB_WS_TONE,               // the tone editor's three curve LUTs, 3 x 4096 f32 (tone.hip)
+    AB_WS_VIEW,               // the open-file view: 65 536 source bins, display bins bound for the host, three channels' results (view.hip)
     AB_WS_SLOTS
 };
 

@@ -1601,6 +1601,92 @@ pub fn apply_tone_composite_planes(hip: &Hip, r: &impl PlaneSrc, g: &impl PlaneS
     Ok((planes, TonePreview { pixels, info: tone_info(&info) }))
 }
 
+// ---- opening a file: cmd/io/mod.rs (process_fits, process_fits_full, process_rgb_fits), cmd/analysis/mod.rs (compute_histogram) ------------------------
+/// drop-in for downsample_histogram (stats.rs:423-444) on the bins themselves; host-only
+pub fn downsample_histogram(bins: &[u32], target_bins: usize) -> Result<Vec<u32>> {
+    let mut out = vec![0u32; target_bins.min(bins.len())];
+    let mut len = 0usize;
+    if unsafe { sys::ab_downsample_histogram(bins.as_ptr(), bins.len(), target_bins, out.as_mut_ptr(), &mut len) } != 0 {
+        bail!("downsample_histogram: no source bins or target_bins == 0");
+    }
+    out.truncate(len);
+    Ok(out)
+}
+/// Histogram.bin_edges of build_histogram (stats.rs:379-387, :412-413); host-only
+pub fn histogram_bin_edges(dmin: f64, dmax: f64, bins: usize) -> Result<Vec<f64>> {
+    let mut out = vec![0.0f64; bins + 1];
+    if unsafe { sys::ab_histogram_bin_edges(dmin, dmax, bins, out.as_mut_ptr()) } != 0 {
+        bail!("histogram_bin_edges: bins == 0");
+    }
+    Ok(out)
+}
+/// downsample_histogram(&compute_histogram_with_stats(data, stats), target_bins) (stats.rs:373-376, :423-444) in one pass over the plane
+pub fn display_histogram(hip: &Hip, data: &impl PlaneSrc, dmin: f64, dmax: f64, target_bins: usize) -> Result<Vec<u32>> {
+    let mut out = vec![0u32; target_bins.clamp(1, 65536)];
+    let mut len = 0usize;
+    hip.check(unsafe { sys::ab_display_histogram(hip.ctx, &data.ab(), dmin, dmax, target_bins, out.as_mut_ptr(), 0, &mut len) })?;
+    out.truncate(len);
+    Ok(out)
+}
+/// what process_fits_full hands to the encoder and the JSON (cmd/io/mod.rs:138-170)
+pub struct FitsView {
+    pub pixels: Vec<u8>,
+    pub display_bins: Vec<u32>,
+    pub dims: (usize, usize),
+    pub stats: ImageStats,
+    pub stf: StfParams,
+}
+/// what process_rgb_fits hands over (cmd/io/mod.rs:44-99): preview_dims.0 x preview_dims.1 x 3 interleaved bytes, R's display bins
+pub struct RgbFitsView {
+    pub pixels: Vec<u8>,
+    pub display_bins: Vec<u32>,
+    pub dims: (usize, usize),
+    pub preview_dims: (usize, usize),
+    pub stats: [ImageStats; 3],
+    pub stf: [StfParams; 3],
+}
+fn fits_view_cfg(config: &AutoStfConfig, hist_bins: usize) -> sys::ab_fits_view_config {
+    let mut cfg: sys::ab_fits_view_config = unsafe { std::mem::zeroed() };
+    unsafe { sys::ab_fits_view_config_default(&mut cfg) };
+    cfg.stf = sys::ab_auto_stf_config { target_bg: config.target_bg, shadow_k: config.shadow_k };
+    cfg.hist_bins = hist_bins;
+    cfg
+}
+/// the mono branch of process_fits_full (hist_bins = 0: of process_fits) from the loaded plane to the encoder's input: statistics, auto_stf,
+/// apply_stf and the display histogram as one device chain with one synchronisation
+pub fn process_fits_view(hip: &Hip, arr: &impl PlaneSrc, config: &AutoStfConfig, hist_bins: usize) -> Result<FitsView> {
+    let (rows, cols) = arr.dims();
+    let cfg = fits_view_cfg(config, hist_bins);
+    let mut pixels = vec![0u8; rows * cols];
+    let mut bins = vec![0u32; hist_bins.min(65536)];
+    let mut info: sys::ab_fits_view_info = unsafe { std::mem::zeroed() };
+    let bins_ptr = if bins.is_empty() { std::ptr::null_mut() } else { bins.as_mut_ptr() };
+    hip.check(unsafe { sys::ab_process_fits_view(hip.ctx, &arr.ab(), &cfg, pixels.as_mut_ptr(), 0, bins_ptr, 0, &mut info) })?;
+    Ok(FitsView { pixels, display_bins: bins, dims: (info.rows as usize, info.cols as usize), stats: stats_from_sys(&info.stats), stf: stf_from_sys(&info.stf) })
+}
+/// process_rgb_fits from its three planes on (cmd/io/mod.rs:44-62): per-channel statistics and auto_stf, apply_stf_f32, render_rgb_preview and
+/// R's display histogram as one device chain with one synchronisation
+pub fn process_rgb_fits_view(hip: &Hip, r: &impl PlaneSrc, g: &impl PlaneSrc, b: &impl PlaneSrc, config: &AutoStfConfig, hist_bins: usize, max_dim: usize) -> Result<RgbFitsView> {
+    let (rows, cols) = r.dims();
+    let (ph, pw) = preview_dims(rows, cols, max_dim);
+    let cfg = fits_view_cfg(config, hist_bins);
+    let mut pixels = vec![0u8; ph * pw * 3];
+    let mut bins = vec![0u32; hist_bins.min(65536)];
+    let mut info: sys::ab_rgb_fits_view_info = unsafe { std::mem::zeroed() };
+    let bins_ptr = if bins.is_empty() { std::ptr::null_mut() } else { bins.as_mut_ptr() };
+    hip.check(unsafe {
+        sys::ab_process_rgb_fits_view(hip.ctx, &r.ab(), &g.ab(), &b.ab(), &cfg, max_dim as i64, pixels.as_mut_ptr(), 0, bins_ptr, 0, &mut info)
+    })?;
+    Ok(RgbFitsView {
+        pixels,
+        display_bins: bins,
+        dims: (info.rows as usize, info.cols as usize),
+        preview_dims: (info.preview_rows as usize, info.preview_cols as usize),
+        stats: [stats_from_sys(&info.stats[0]), stats_from_sys(&info.stats[1]), stats_from_sys(&info.stats[2])],
+        stf: [stf_from_sys(&info.stf[0]), stf_from_sys(&info.stf[1]), stf_from_sys(&info.stf[2])],
+    })
+}
+
 // ---- a13  core/imaging/star_mask.rs, masked_stretch.rs -------------------------------------------------------------------------------------------------
 /// drop-in for generate_star_mask (star_mask.rs:38-44)
 pub fn generate_star_mask(hip: &Hip, image: &impl PlaneSrc, config: &StarMaskConfig) -> Result<StarMaskResult, String> {

@@ -1270,6 +1270,67 @@ AB_API int ab_apply_tone_composite(ab_ctx *ctx, const ab_plane *r, const ab_plan
                                    const ab_tone_config *cfg, int64_t max_dim, ab_plane_mut *out_planes, uint8_t *out_rgb8,
                                    int32_t out_on_device, ab_tone_info *info);
 
+/* ---- opening a file: cmd/io/mod.rs (process_fits :105-126, process_fits_full :129-172, process_rgb_fits :33-102) and the histogram
+ * panel's compute_histogram (cmd/analysis/mod.rs:22-53), up to the PNG encoder and the JSON --------------------------------------- */
+/* Host only.  downsample_histogram (core/imaging/stats.rs:423-444): target_bins >= n_bins copies (*out_len = n_bins); else
+ * ratio = n_bins as f64 / target_bins as f64 and out[i] = the SATURATING u32 sum of bins[(i as f64 * ratio) as usize ..
+ * min(((i + 1) as f64 * ratio) as usize, n_bins)), *out_len = target_bins.  out holds min(target_bins, n_bins) words.  The rule is
+ * no clean partition: for 9841 of the targets below 65 536 (49, 98, 103, 107, 161, ...) (target as f64 * ratio) as usize is 65 535
+ * and the LAST source bin -- the one that holds the image's maximum -- is dropped.  Reproduced.  n_bins == 0, target_bins == 0 or a
+ * NULL pointer -> AB_ERR_INVALID. */
+AB_API int ab_downsample_histogram(const uint32_t *bins, size_t n_bins, size_t target_bins, uint32_t *out, size_t *out_len);
+/* Host only.  Histogram.bin_edges of build_histogram (stats.rs:379-387, :412-413): bins + 1 doubles, every one dmin when
+ * dmax - dmin < 1e-10, else dmin + i as f64 * (range / bins as f64).  bins == 0 or NULL -> AB_ERR_INVALID. */
+AB_API int ab_histogram_bin_edges(double dmin, double dmax, size_t bins, double *edges);
+/* downsample_histogram(compute_histogram_with_stats(img, {min: dmin, max: dmax}), target_bins) (stats.rs:373-376, :423-444) in one
+ * pass: bin for bin ab_downsample_histogram(ab_build_histogram(img, 65536, dmin, dmax), 65536, target_bins), for every pair of
+ * doubles, target_bins >= 1, a host or device plane at any float-aligned address.  *out_len (nullable) = min(target_bins, 65536) =
+ * the words written to out_bins (host, or device with out_on_device).  A target that divides 65 536 (up to 16 384; the product's
+ * 512) accumulates the display bins in LDS: no 65 536-bin intermediate, the plane is read once.  Other targets count the 65 536
+ * bins on the device and fold them there.  rows * cols >= 2^31 -> AB_ERR_INVALID (no count can wrap).  Device plane and device
+ * output: asynchronous. */
+AB_API int ab_display_histogram(ab_ctx *ctx, const ab_plane *img, double dmin, double dmax, size_t target_bins, uint32_t *out_bins,
+                                int32_t out_on_device, size_t *out_len);
+typedef struct {
+    ab_auto_stf_config stf; /* AutoStfConfig::default() = {0.25, -2.8} (cmd/io/mod.rs:26, :48-50) */
+    size_t hist_bins;       /* HISTOGRAM_BINS_DISPLAY = 512 (types/constants.rs:9); 0: no histogram (process_fits) */
+} ab_fits_view_config;
+typedef struct {
+    uint64_t rows, cols;    /* RES_DIMENSIONS = [cols, rows] */
+    ab_image_stats stats;   /* RES_STATS */
+    ab_stf_params stf;      /* RES_STF */
+    uint64_t hist_len;      /* RES_BIN_COUNT: min(hist_bins, 65536) */
+} ab_fits_view_info;
+typedef struct {
+    uint64_t rows, cols, preview_rows, preview_cols;
+    ab_image_stats stats[3]; /* stats_r, stats_g, stats_b (cmd/io/mod.rs:44-46) */
+    ab_stf_params stf[3];    /* stf_r, stf_g, stf_b (:48-50) */
+    uint64_t hist_len;
+} ab_rgb_fits_view_info;
+AB_API void ab_fits_view_config_default(ab_fits_view_config *cfg);
+/* The mono branch of process_fits_full (cmd/io/mod.rs:138-144; hist_bins = 0: of process_fits, :114-116): compute_image_stats ->
+ * auto_stf(cfg->stf) -> apply_stf, and downsample_histogram(compute_histogram_with_stats(img, stats), hist_bins), as ONE chain: the
+ * statistics, then one kernel that reads the transform and the statistics' min / max from HBM, writes every pixel's byte and counts
+ * the same pixel into the display histogram, then at most one synchronisation, which fetches info and the host outputs (info NULL
+ * and device outputs: none).  img: host or device, any float-aligned address.  out_u8: rows x cols bytes at any address, host or
+ * device.  out_bins: min(hist_bins, 65536) words, host or device (bins_on_device); may be NULL when hist_bins == 0.  The bytes are
+ * ab_auto_stretch_preview's, the statistics and stf what it returns, the bins ab_display_histogram(img, stats.min, stats.max,
+ * hist_bins)'s: max - min < 1e-10 (decided on the device; so also when no pixel is valid) -> zero bins. */
+AB_API int ab_process_fits_view(ab_ctx *ctx, const ab_plane *img, const ab_fits_view_config *cfg, uint8_t *out_u8, int32_t out_on_device,
+                                uint32_t *out_bins, int32_t bins_on_device, ab_fits_view_info *info);
+/* process_rgb_fits from its three planes on (cmd/io/mod.rs:44-62): compute_image_stats x 3, auto_stf(cfg->stf) x 3 (unlinked),
+ * apply_stf_f32 per channel, render_rgb_preview(.., max_dim) (cmd/helpers.rs:204-262) and, with hist_bins > 0, the display histogram
+ * of R with R's statistics (:61-62).  One chain: three statistics chains, each followed by a small device-to-device copy of its
+ * result, then one kernel that reads the three transforms from HBM and packs the preview (an image above max_dim tones only the
+ * pixels the preview picks); R's histogram rides in it when every pixel is visited and is one more pass over R otherwise; one
+ * synchronisation at the end, none with info NULL and device outputs.  out_rgb8 (nullable when hist_bins > 0): preview_rows x
+ * preview_cols x 3 bytes with the dims of ab_preview_dims, any address.  With the default cfg->stf the bytes are
+ * ab_apply_tone_composite's with ab_tone_config_default and the same statistics.  Mismatched dims, rows * cols >= 2^31, max_dim < 1,
+ * out_rgb8 NULL with hist_bins == 0 or out_bins NULL with hist_bins > 0 -> AB_ERR_INVALID before anything touches the device. */
+AB_API int ab_process_rgb_fits_view(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, const ab_fits_view_config *cfg,
+                                    int64_t max_dim, uint8_t *out_rgb8, int32_t out_on_device, uint32_t *out_bins, int32_t bins_on_device,
+                                    ab_rgb_fits_view_info *info);
+
 /* ---- bench support: a plain float4 device copy, the measured HBM ceiling ---- */
 AB_API int ab_bench_copy(ab_ctx *ctx, const float *src_dev, float *dst_dev, size_t n_floats);
 

@@ -20,7 +20,7 @@ API = set(re.findall(r"AB_API[^;(]*?\b(ab_[a-z0-9_]+)\s*\(", HEADER))
 SKIP = {"ab_ctx_destroy", "ab_comm_destroy", "ab_last_error", "ab_version", "ab_ctx_get_stream", "ab_comm_rank", "ab_comm_size",
         "ab_comm_collectives_issued", "ab_subframe_weight_config_default", "ab_batch_stack_config_default",
         "ab_normalize_subframe_weights", "ab_psf_estimation_config_default", "ab_synth_config_default",
-        "ab_crop_config_default", "ab_tone_config_default"}   # void / pointer / trivially non-throwing getters
+        "ab_crop_config_default", "ab_tone_config_default", "ab_fits_view_config_default"}   # void / pointer / trivially non-throwing getters
 
 
 def match_brace(s, i):
