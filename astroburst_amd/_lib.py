@@ -305,6 +305,29 @@ class RgbFitsViewInfoC(C.Structure):  # ab_rgb_fits_view_info: process_rgb_fits'
                 ("stats", ImageStatsC * 3), ("stf", StfParamsC * 3), ("hist_len", C.c_uint64)]
 
 
+AB_COLOR_STATS_EXACT_OR_FULL, AB_COLOR_STATS_KNOWN_RANGE = range(2)
+
+
+class ColorPlanC(C.Structure):  # ab_color_plan: calibrate_and_scnr_cmd's decisions (cmd/compose/color.rs:115-117, :138-159)
+    _fields_ = [("factors", C.c_float * 3), ("scnr_applied", C.c_int32), ("route", C.c_int32 * 3), ("known_min", C.c_double * 3),
+                ("known_max", C.c_double * 3)]
+
+
+class ColorStepInfoC(C.Structure):  # ab_color_step_info: what the command caches and reports (color.rs:169-183)
+    _fields_ = [("rows", C.c_uint64), ("cols", C.c_uint64), ("preview_rows", C.c_uint64), ("preview_cols", C.c_uint64),
+                ("factors", C.c_float * 3), ("scnr_applied", C.c_int32), ("route", C.c_int32 * 3), ("stats", ImageStatsC * 3),
+                ("stf", StfParamsC)]
+
+
+class BlendCompositeInfoC(C.Structure):  # ab_blend_composite_info: blend_channels_cmd's (cmd/compose/blend.rs:211-221)
+    _fields_ = [("rows", C.c_uint64), ("cols", C.c_uint64), ("preview_rows", C.c_uint64), ("preview_cols", C.c_uint64),
+                ("resampled", C.c_int32), ("stats", ImageStatsC * 3), ("stf", StfParamsC)]
+
+
+class AutoWbC(C.Structure):  # ab_auto_wb: compute_auto_wb_cmd's JSON (color.rs:214-222)
+    _fields_ = [("factors", C.c_double * 3), ("stability", C.c_double * 3), ("ref_channel", C.c_int32)]
+
+
 class DrizzleResultC(C.Structure):  # DrizzleResult's scalars (drizzle.rs:335-344)
     _fields_ = [("frame_count", C.c_size_t), ("output_scale", C.c_double), ("in_rows", C.c_int64), ("in_cols", C.c_int64),
                 ("out_rows", C.c_int64), ("out_cols", C.c_int64), ("rejected_pixels", C.c_uint64)]
@@ -606,6 +629,12 @@ def lib() -> C.CDLL:
     L.ab_fits_view_config_default.restype = None
     L.ab_process_fits_view.argtypes = [vp, pp, fvc, vp, C.c_int32, vp, C.c_int32, C.POINTER(FitsViewInfoC)]
     L.ab_process_rgb_fits_view.argtypes = [vp, pp, pp, pp, fvc, C.c_int64, vp, C.c_int32, vp, C.c_int32, C.POINTER(RgbFitsViewInfoC)]
+    f64p, scp_ = C.POINTER(C.c_double), C.POINTER(ScnrConfigC)
+    L.ab_color_step_plan.argtypes = [C.c_uint64, isp, f64p, C.c_int32, scp_, C.POINTER(ColorPlanC)]
+    L.ab_calibrate_and_scnr.argtypes = [vp, pp, pp, pp, isp, f64p, C.c_int32, scp_, C.c_int64, pmp, vp, C.c_int32, C.POINTER(ColorStepInfoC)]
+    L.ab_blend_composite.argtypes = [vp, pp, C.c_size_t, C.POINTER(BlendWeightC), C.c_size_t, C.c_int64, pmp, vp, C.c_int32,
+                                     C.POINTER(BlendCompositeInfoC)]
+    L.ab_compute_auto_wb.argtypes = [isp, isp, isp, C.POINTER(AutoWbC)]
     for name in declared_symbols():
         fn = getattr(L, name)  # AttributeError here = header / library drift
         if fn.restype is C.c_int and name not in ("ab_last_error", "ab_version", "ab_ctx_get_stream", "ab_comm_collectives_issued"):

@@ -311,6 +311,88 @@ class RgbFitsView:  # process_rgb_fits' (cmd/io/mod.rs:33-102)
     stf: object            # 3 x StfParams, or None
 
 
+COLOR_STATS_EXACT_OR_FULL, COLOR_STATS_KNOWN_RANGE = _lib.AB_COLOR_STATS_EXACT_OR_FULL, _lib.AB_COLOR_STATS_KNOWN_RANGE
+
+
+@dataclass
+class ColorPlan:  # what calibrate_and_scnr_cmd decides (cmd/compose/color.rs:115-117, :138-159 with calibrate_channel, :21-49)
+    factors: tuple         # 3 x the f32 factor applied, as Python floats
+    scnr_applied: bool
+    route: tuple           # 3 x COLOR_STATS_EXACT_OR_FULL | COLOR_STATS_KNOWN_RANGE
+    known_min: tuple       # 3 x float (0.0 off the known-range route)
+    known_max: tuple
+
+
+@dataclass
+class ColorStepResult:  # calibrate_and_scnr_cmd: what it caches, encodes and reports (color.rs:161-183)
+    planes: tuple          # (r, g, b): __composite_r / _g / _b
+    rgb8: object           # uint8 (preview_rows, preview_cols, 3), or None
+    rows: int
+    cols: int
+    preview_rows: int
+    preview_cols: int
+    factors: object        # 3 x float, or None (fetch=False)
+    scnr_applied: object   # bool, or None
+    route: object          # 3 x route, or None
+    stats: object          # 3 x ImageStats, or None
+    stf: object            # the linked StfParams, or None
+
+
+@dataclass
+class BlendCompositeResult:  # blend_channels_cmd's (cmd/compose/blend.rs:185-221)
+    planes: tuple          # (r, g, b)
+    rgb8: object           # uint8 (preview_rows, preview_cols, 3), or None
+    rows: int
+    cols: int
+    preview_rows: int
+    preview_cols: int
+    resampled: object      # bool, or None (fetch=False)
+    stats: object          # 3 x ImageStats, or None
+    stf: object            # the linked StfParams, or None
+
+
+@dataclass
+class AutoWb:  # compute_auto_wb_cmd's JSON (color.rs:214-222)
+    factors: tuple         # (r, g, b)
+    stability: tuple       # (stab_r, stab_g, stab_b)
+    ref_channel: str       # "R" | "G" | "B"
+
+
+def _stats3(stats):
+    return (_lib.ImageStatsC * 3)(*[ImageStatsC(s.min, s.max, s.median, s.mad, s.sigma, s.mean, s.valid_count) for s in stats])
+
+
+def _scnr_config(scnr):
+    """(has_scnr, ab_scnr_config | None) of None or dict(method=, amount=, preserve_luminance=)"""
+    if scnr is None:
+        return 0, None
+    m = scnr.get("method", "average")
+    return 1, _lib.ScnrConfigC(0 if m in ("average", "AverageNeutral", 0) else 1, scnr.get("amount", 1.0), int(bool(scnr.get("preserve_luminance", False))))
+
+
+def color_step_plan(n_pixels: int, orig_stats, factors, scnr=None) -> ColorPlan:
+    """The decisions of calibrate_and_scnr_cmd (cmd/compose/color.rs:97-184) without its pixels: the f32 factors, whether SCNR runs and
+    the statistics route of each channel's final plane.  Host-only."""
+    has, cfg = _scnr_config(scnr)
+    plan = _lib.ColorPlanC()
+    f = (C.c_double * 3)(*[float(v) for v in factors])
+    rc = _lib.lib().ab_color_step_plan(int(n_pixels), _stats3(orig_stats), f, has, C.byref(cfg) if cfg is not None else None, C.byref(plan))
+    if rc != _lib.AB_OK:
+        raise AstroBurstError(rc, "ab_color_step_plan: bad arguments")
+    return ColorPlan(tuple(float(v) for v in plan.factors), bool(plan.scnr_applied), tuple(int(v) for v in plan.route),
+                     tuple(float(v) for v in plan.known_min), tuple(float(v) for v in plan.known_max))
+
+
+def compute_auto_wb(sr, sg, sb) -> AutoWb:
+    """compute_auto_wb_cmd (cmd/compose/color.rs:187-224) of the three channels' ImageStats.  Host-only."""
+    st = _stats3((sr, sg, sb))
+    out = _lib.AutoWbC()
+    rc = _lib.lib().ab_compute_auto_wb(C.byref(st[0]), C.byref(st[1]), C.byref(st[2]), C.byref(out))
+    if rc != _lib.AB_OK:
+        raise AstroBurstError(rc, "ab_compute_auto_wb: bad arguments")
+    return AutoWb(tuple(float(v) for v in out.factors), tuple(float(v) for v in out.stability), "RGB"[out.ref_channel])
+
+
 HISTOGRAM_BINS = 65536     # stats.rs:8: what compute_histogram_with_stats builds before the fold
 
 
@@ -2584,6 +2666,69 @@ class Context:
             return RgbFitsView(rgb8, bins, rows, cols, ph, pw, None, None)
         return RgbFitsView(rgb8, bins, int(info.rows), int(info.cols), int(info.preview_rows), int(info.preview_cols),
                            tuple(self._stats_out(s) for s in info.stats), tuple(StfParams(p.shadow, p.midtone, p.highlight) for p in info.stf))
+
+    # ---- cmd/compose/blend.rs and cmd/compose/color.rs: the wizard's blend and colour steps ---------------------------------
+    color_step_plan = staticmethod(color_step_plan)
+    compute_auto_wb = staticmethod(compute_auto_wb)
+
+    def _composite_outputs(self, like, rows, cols, max_dim, want_rgb8, out, out_planes, keep):
+        """the three f32 planes and the preview's bytes of a wizard step: the caller's (out_planes: three arrays or CUDA tensors of
+        rows x cols; out: contiguous uint8 of preview_rows * preview_cols * 3, any address) or new ones of `like`'s kind"""
+        if out_planes is None:
+            planes, pp = self._plane3(like, rows, cols, keep)
+        else:
+            planes = tuple(out_planes)
+            ok = len(planes) == 3 and all(tuple(p.shape) == (rows, cols) and (_is_torch(p) or (isinstance(p, np.ndarray) and p.dtype == np.float32
+                                                                                              and p.flags.c_contiguous)) for p in planes)
+            if not ok:
+                raise AstroBurstError(_lib.AB_ERR_INVALID, f"out_planes must be three contiguous float32 planes of {rows} x {cols}")
+            pp = (Plane * 3)(*[self._out_plane(a, keep, rows, cols) for a in planes])
+        ph, pw = self.preview_dims(rows, cols, max_dim) if max_dim > 0 else (1, 1)   # (max_dim < 1 is the library's AB_ERR_INVALID)
+        rgb8, ptr, dev = self._bytes_out(like, (ph, pw, 3), out) if (want_rgb8 or out is not None) else (None, None, 0)
+        return planes, pp, rgb8, ptr, dev, ph, pw
+
+    def calibrate_and_scnr(self, r, g, b, orig_stats, factors, scnr=None, max_dim=4096, fetch=True, want_rgb8=True, out=None,
+                           out_planes=None) -> ColorStepResult:
+        """calibrate_and_scnr_cmd (cmd/compose/color.rs:97-184) from its loaded originals to the encoder's input as one chain: white
+        balance and SCNR in one kernel, three statistics chains by color_step_plan's routes, the linked STF on the device and the
+        preview, one synchronisation.  orig_stats: the originals' ImageStats; factors: (r, g, b) as the command receives them; scnr:
+        None or dict(method=, amount=, preserve_luminance=).  fetch=False with device outputs keeps the call asynchronous (the
+        scalars are then None).  Outputs are of r's kind unless out / out_planes are given."""
+        keep = []
+        pr, pg, pb = (self._plane(x, keep) for x in (r, g, b))
+        rows, cols = int(pr.rows), int(pr.cols)
+        planes, pp, rgb8, ptr, dev, ph, pw = self._composite_outputs(r, rows, cols, max_dim, want_rgb8, out, out_planes, keep)
+        has, cfg = _scnr_config(scnr)
+        f = (C.c_double * 3)(*[float(v) for v in factors])
+        info = _lib.ColorStepInfoC()
+        self._check(self._L.ab_calibrate_and_scnr(self._h, C.byref(pr), C.byref(pg), C.byref(pb), _stats3(orig_stats), f, has,
+                                                  C.byref(cfg) if cfg is not None else None, int(max_dim), pp, ptr, dev, C.byref(info) if fetch else None))
+        if not fetch:
+            return ColorStepResult(planes, rgb8, rows, cols, ph, pw, None, None, None, None, None)
+        return ColorStepResult(planes, rgb8, int(info.rows), int(info.cols), int(info.preview_rows), int(info.preview_cols),
+                               tuple(float(v) for v in info.factors), bool(info.scnr_applied), tuple(int(v) for v in info.route),
+                               tuple(self._stats_out(s) for s in info.stats), StfParams(info.stf.shadow, info.stf.midtone, info.stf.highlight))
+
+    def blend_composite(self, channels, weights, max_dim=4096, fetch=True, want_rgb8=True, out=None, out_planes=None) -> BlendCompositeResult:
+        """blend_channels_cmd (cmd/compose/blend.rs:128-223) from its loaded channels on as one chain: channels of differing dims are
+        resampled (bicubic) to the largest rows and the largest cols, blend_channels, three statistics chains, the linked STF on the
+        device and the preview, one synchronisation.  weights: iterable of (channel_idx, r_weight, g_weight, b_weight).  Outputs are
+        of the first channel's kind unless out / out_planes are given."""
+        if len(channels) == 0:   # (the library's own error: no plane is there to take the output's kind from)
+            self._check(self._L.ab_blend_composite(self._h, None, 0, None, 0, int(max_dim), None, None, 0, None))
+        keep = []
+        chans = (Plane * len(channels))(*[self._plane(c, keep) for c in channels])
+        rows, cols = max(int(p.rows) for p in chans), max(int(p.cols) for p in chans)
+        ws = (_lib.BlendWeightC * max(1, len(weights)))(*[_lib.BlendWeightC(int(w[0]), w[1], w[2], w[3]) for w in weights])
+        planes, pp, rgb8, ptr, dev, ph, pw = self._composite_outputs(channels[0], rows, cols, max_dim, want_rgb8, out, out_planes, keep)
+        info = _lib.BlendCompositeInfoC()
+        self._check(self._L.ab_blend_composite(self._h, chans, len(channels), ws, len(weights), int(max_dim), pp, ptr, dev,
+                                               C.byref(info) if fetch else None))
+        if not fetch:
+            return BlendCompositeResult(planes, rgb8, rows, cols, ph, pw, None, None, None)
+        return BlendCompositeResult(planes, rgb8, int(info.rows), int(info.cols), int(info.preview_rows), int(info.preview_cols),
+                                    bool(info.resampled), tuple(self._stats_out(s) for s in info.stats),
+                                    StfParams(info.stf.shadow, info.stf.midtone, info.stf.highlight))
 
     # ---- cmd/compose/crop.rs ---------------------------------------------------------------------------------
     @staticmethod

@@ -65,6 +65,7 @@ enum {
     AB_WS_SYNTH,              // synthetic generator: star records, norms, tile lists, the frames' route flags (synth.hip)
     AB_WS_TONE,               // the tone editor's three curve LUTs, 3 x 4096 f32 (tone.hip)
     AB_WS_VIEW,               // the open-file view: 65 536 source bins, display bins bound for the host, three channels' results (view.hip)
+    AB_WS_WIZARD,             // the blend / colour steps: three channels' statistics, the linked STF and transforms, resampled channels (wizard_color.hip)
     AB_WS_SLOTS
 };
 
@@ -432,6 +433,10 @@ int ab_warp_rows_device(ab_ctx *ctx, const float *src, int64_t src_rows, int64_t
                         int64_t out_cols, int64_t row0, int64_t nrows, float *out);
 int ab_resample_device(ab_ctx *ctx, const float *src, int64_t src_rows, int64_t src_cols, int64_t out_rows, int64_t out_cols,
                        float *out);
+// color.hip: blend_channels of device planes (ch: a HOST table of n_channels device pointers to n pixels each); at most 16 channels
+// and 32 weights whose channel_idx is in range
+int ab_blend_device(ab_ctx *ctx, const float *const *ch, size_t n_channels, const ab_blend_weight *weights, size_t n_weights, int64_t n, float *r,
+                    float *g, float *b);
 
 // comm.hip: wait for ctx->stream while a collective of `comm` may be in flight -- bounded (AB_COMM_TIMEOUT_MS) and watching
 // RCCL's asynchronous error state; on failure the communicator is aborted and AB_ERR_COMM returned.  NULL / host-staged

@@ -247,6 +247,32 @@ int unary_map(ab_ctx *ctx, const ab_plane *img, ab_plane_mut *out, F launch) {
 
 }  // namespace
 
+// blend_channels (channel_blend.rs:13-70) of device planes: ch is a HOST table of n_channels device pointers to n pixels each
+int ab_blend_device(ab_ctx *ctx, const float *const *ch, size_t n_channels, const ab_blend_weight *weights, size_t n_weights, int64_t n, float *r,
+                    float *g, float *b) {
+    AB_CHECK(ctx, n_channels >= 1 && n_channels <= (size_t)kMaxBlendChannels, "1..%d channels", kMaxBlendChannels);
+    BlendArgs a;
+    memset(&a, 0, sizeof a);
+    int nw = 0;
+    for (size_t w = 0; w < n_weights; ++w) {                       // channel_blend.rs:20-23
+        if (weights[w].channel_idx >= n_channels) continue;
+        AB_CHECK(ctx, nw < kMaxBlendWeights, "at most %d blend weights", kMaxBlendWeights);
+        a.idx[nw] = (int)weights[w].channel_idx;
+        a.rw[nw] = (float)weights[w].r_weight;
+        a.gw[nw] = (float)weights[w].g_weight;
+        a.bw[nw] = (float)weights[w].b_weight;
+        ++nw;
+    }
+    for (size_t i = 0; i < n_channels; ++i) a.ch[i] = ch[i];
+    a.n_weights = nw;
+    a.n = n;
+    a.r = r, a.g = g, a.b = b;
+    hipLaunchKernelGGL(blend_kernel, dim3(stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "blend: %s", hipGetErrorString(e));
+    return AB_OK;
+}
+
 extern "C" {
 
 int ab_apply_scnr_inplace(ab_ctx *ctx, ab_plane_mut *r, ab_plane_mut *g, ab_plane_mut *b, const ab_scnr_config *cfg) try {
@@ -299,41 +325,24 @@ int ab_blend_channels(ab_ctx *ctx, const ab_plane *channels, size_t n_channels, 
     for (size_t i = 0; i < n_channels; ++i)
         AB_CHECK(ctx, channels[i].rows * channels[i].cols >= n, "channel %zu is smaller than the output", i);
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    BlendArgs a;
-    memset(&a, 0, sizeof a);
-    int nw = 0;
-    for (size_t w = 0; w < n_weights; ++w) {                       // channel_blend.rs:20-23
-        if (weights[w].channel_idx >= n_channels) continue;
-        AB_CHECK(ctx, nw < kMaxBlendWeights, "at most %d blend weights", kMaxBlendWeights);
-        a.idx[nw] = (int)weights[w].channel_idx;
-        a.rw[nw] = (float)weights[w].r_weight;
-        a.gw[nw] = (float)weights[w].g_weight;
-        a.bw[nw] = (float)weights[w].b_weight;
-        ++nw;
-    }
-    a.n_weights = nw;
-    a.n = n;
+    size_t nw = 0;
+    for (size_t w = 0; w < n_weights; ++w) nw += weights[w].channel_idx < n_channels;
+    AB_CHECK(ctx, nw <= (size_t)kMaxBlendWeights, "at most %d blend weights", kMaxBlendWeights);
     std::vector<StagedPlane> st(n_channels);
+    const float *ch[kMaxBlendChannels];
     int rc = AB_OK;
     size_t staged = 0;
     for (; staged < n_channels; ++staged) {
         rc = ab_stage_in(ctx, &channels[staged], &st[staged]);
         if (rc != AB_OK) break;
-        a.ch[staged] = st[staged].dptr;
+        ch[staged] = st[staged].dptr;
     }
     StagedOut so[3];
     ab_plane_mut *outs[3] = {r, g, b};
     int opened = 0;
     for (; rc == AB_OK && opened < 3; ++opened) rc = ab_stage_out_begin(ctx, outs[opened], &so[opened]);
     if (rc != AB_OK && opened > 0) --opened;
-    if (rc == AB_OK) {
-        a.r = so[0].dptr;
-        a.g = so[1].dptr;
-        a.b = so[2].dptr;
-        hipLaunchKernelGGL(blend_kernel, dim3(stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "blend: %s", hipGetErrorString(e));
-    }
+    if (rc == AB_OK) rc = ab_blend_device(ctx, ch, n_channels, weights, n_weights, n, so[0].dptr, so[1].dptr, so[2].dptr);
     for (int i = 0; i < opened; ++i) {
         if (rc == AB_OK)
             rc = ab_stage_out_finish(ctx, &so[i]);

@@ -1687,6 +1687,153 @@ pub fn process_rgb_fits_view(hip: &Hip, r: &impl PlaneSrc, g: &impl PlaneSrc, b:
     })
 }
 
+// ---- the compose wizard's blend and colour steps: cmd/compose/blend.rs (blend_channels_cmd), cmd/compose/color.rs ----------------------------------------
+/// how a channel's kept statistics were computed (color.rs:21-49, :138-159)
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum ColorStatsRoute {
+    /// compute_image_stats of the final plane
+    ExactOrFull,
+    /// compute_image_stats_with_known_range of the final plane (a channel SCNR leaves alone, above 4 000 000 px)
+    KnownRange,
+}
+fn route_from_sys(r: i32) -> ColorStatsRoute {
+    if r == sys::AB_COLOR_STATS_KNOWN_RANGE as i32 { ColorStatsRoute::KnownRange } else { ColorStatsRoute::ExactOrFull }
+}
+/// calibrate_and_scnr_cmd's decisions (color.rs:115-117, :138-159)
+#[derive(Clone, Debug)]
+pub struct ColorPlan {
+    pub factors: [f32; 3],
+    pub scnr_applied: bool,
+    pub route: [ColorStatsRoute; 3],
+    pub known_range: [(f64, f64); 3],
+}
+/// what calibrate_and_scnr_cmd encodes and reports beside the planes it caches as __composite_r / _g / _b: pixels is RgbImage::from_raw's input
+pub struct ColorStep {
+    pub pixels: Vec<u8>,
+    pub dims: (usize, usize),
+    pub preview_dims: (usize, usize),
+    pub factors: [f32; 3],
+    pub scnr_applied: bool,
+    pub route: [ColorStatsRoute; 3],
+    pub stats: [ImageStats; 3],
+    pub stf: StfParams,
+}
+/// what blend_channels_cmd encodes and reports beside the planes it caches (blend.rs:185-221)
+pub struct BlendComposite {
+    pub pixels: Vec<u8>,
+    pub dims: (usize, usize),
+    pub preview_dims: (usize, usize),
+    pub resampled: bool,
+    pub stats: [ImageStats; 3],
+    pub stf: StfParams,
+}
+/// compute_auto_wb_cmd's JSON (color.rs:214-222)
+#[derive(Clone, Debug)]
+pub struct AutoWb {
+    pub factors: [f64; 3],
+    pub stability: [f64; 3],
+    pub ref_channel: char,
+}
+fn scnr_arg(scnr: Option<&ScnrConfig>) -> (i32, sys::ab_scnr_config) {
+    match scnr {
+        Some(s) => (1, scnr_to_sys(s)),
+        None => (0, unsafe { std::mem::zeroed() }),
+    }
+}
+/// the colour step's decisions without its pixels; host-only
+pub fn color_step_plan(n_pixels: usize, orig_stats: &[ImageStats; 3], factors: [f64; 3], scnr: Option<&ScnrConfig>) -> Result<ColorPlan> {
+    let s = [stats_to_sys(&orig_stats[0]), stats_to_sys(&orig_stats[1]), stats_to_sys(&orig_stats[2])];
+    let (has, cfg) = scnr_arg(scnr);
+    let mut plan: sys::ab_color_plan = unsafe { std::mem::zeroed() };
+    if unsafe { sys::ab_color_step_plan(n_pixels as u64, s.as_ptr(), factors.as_ptr(), has, &cfg, &mut plan) } != 0 {
+        bail!("the colour step's plan could not be computed");
+    }
+    Ok(ColorPlan {
+        factors: plan.factors,
+        scnr_applied: plan.scnr_applied != 0,
+        route: [route_from_sys(plan.route[0]), route_from_sys(plan.route[1]), route_from_sys(plan.route[2])],
+        known_range: [(plan.known_min[0], plan.known_max[0]), (plan.known_min[1], plan.known_max[1]), (plan.known_min[2], plan.known_max[2])],
+    })
+}
+/// calibrate_and_scnr_cmd (color.rs:97-184) from its loaded originals to the encoder's input as one device chain with one synchronisation:
+/// white balance and SCNR in one kernel, the three statistics the command keeps, the linked STF and the preview
+#[allow(clippy::too_many_arguments)]
+pub fn calibrate_and_scnr_into(hip: &Hip, r: &impl PlaneSrc, g: &impl PlaneSrc, b: &impl PlaneSrc, orig_stats: &[ImageStats; 3], factors: [f64; 3], scnr: Option<&ScnrConfig>, max_dim: usize,
+                               out_r: &mut impl PlaneDst, out_g: &mut impl PlaneDst, out_b: &mut impl PlaneDst) -> Result<ColorStep> {
+    let (rows, cols) = r.dims();
+    let (ph, pw) = preview_dims(rows, cols, max_dim);
+    let s = [stats_to_sys(&orig_stats[0]), stats_to_sys(&orig_stats[1]), stats_to_sys(&orig_stats[2])];
+    let (has, cfg) = scnr_arg(scnr);
+    let mut pp = [out_r.ab_mut(), out_g.ab_mut(), out_b.ab_mut()];
+    let mut pixels = vec![0u8; ph * pw * 3];
+    let mut info: sys::ab_color_step_info = unsafe { std::mem::zeroed() };
+    hip.check(unsafe {
+        sys::ab_calibrate_and_scnr(hip.ctx, &r.ab(), &g.ab(), &b.ab(), s.as_ptr(), factors.as_ptr(), has, &cfg, max_dim as i64, pp.as_mut_ptr(), pixels.as_mut_ptr(), 0, &mut info)
+    })?;
+    Ok(ColorStep {
+        pixels,
+        dims: (info.rows as usize, info.cols as usize),
+        preview_dims: (info.preview_rows as usize, info.preview_cols as usize),
+        factors: info.factors,
+        scnr_applied: info.scnr_applied != 0,
+        route: [route_from_sys(info.route[0]), route_from_sys(info.route[1]), route_from_sys(info.route[2])],
+        stats: [stats_from_sys(&info.stats[0]), stats_from_sys(&info.stats[1]), stats_from_sys(&info.stats[2])],
+        stf: stf_from_sys(&info.stf),
+    })
+}
+/// the same into three host planes it allocates
+pub fn calibrate_and_scnr(hip: &Hip, r: &impl PlaneSrc, g: &impl PlaneSrc, b: &impl PlaneSrc, orig_stats: &[ImageStats; 3], factors: [f64; 3], scnr: Option<&ScnrConfig>, max_dim: usize) -> Result<([Array2<f32>; 3], ColorStep)> {
+    let (rows, cols) = r.dims();
+    let [mut pr, mut pg, mut pb] = planes3(rows, cols);
+    let out = calibrate_and_scnr_into(hip, r, g, b, orig_stats, factors, scnr, max_dim, &mut pr, &mut pg, &mut pb)?;
+    Ok(([pr, pg, pb], out))
+}
+/// the dims blend_channels_cmd blends at: the largest rows and the largest cols (blend.rs:148-150); Err on no channel (:139-141)
+pub fn blend_composite_dims<P: PlaneSrc>(channels: &[P]) -> Result<(usize, usize)> {
+    if channels.is_empty() {
+        bail!("No channel paths provided");
+    }
+    Ok((channels.iter().map(|c| c.dims().0).max().unwrap(), channels.iter().map(|c| c.dims().1).max().unwrap()))
+}
+/// blend_channels_cmd (blend.rs:128-223) from its loaded channels on as one device chain with one synchronisation: the bicubic resample
+/// of channels that differ in size, blend_channels, three statistics, the linked STF and the preview
+pub fn blend_composite_into<P: PlaneSrc>(hip: &Hip, channels: &[P], weights: &[BlendWeight], max_dim: usize, out_r: &mut impl PlaneDst, out_g: &mut impl PlaneDst,
+                                         out_b: &mut impl PlaneDst) -> Result<BlendComposite> {
+    let (rows, cols) = blend_composite_dims(channels)?;
+    let (ph, pw) = preview_dims(rows, cols, max_dim);
+    let in_planes: Vec<_> = channels.iter().map(|c| c.ab()).collect();
+    let w = blend_weights(weights);
+    let mut pp = [out_r.ab_mut(), out_g.ab_mut(), out_b.ab_mut()];
+    let mut pixels = vec![0u8; ph * pw * 3];
+    let mut info: sys::ab_blend_composite_info = unsafe { std::mem::zeroed() };
+    hip.check(unsafe {
+        sys::ab_blend_composite(hip.ctx, in_planes.as_ptr(), in_planes.len(), w.as_ptr(), w.len(), max_dim as i64, pp.as_mut_ptr(), pixels.as_mut_ptr(), 0, &mut info)
+    })?;
+    Ok(BlendComposite {
+        pixels,
+        dims: (info.rows as usize, info.cols as usize),
+        preview_dims: (info.preview_rows as usize, info.preview_cols as usize),
+        resampled: info.resampled != 0,
+        stats: [stats_from_sys(&info.stats[0]), stats_from_sys(&info.stats[1]), stats_from_sys(&info.stats[2])],
+        stf: stf_from_sys(&info.stf),
+    })
+}
+/// the same into three host planes it allocates
+pub fn blend_composite<P: PlaneSrc>(hip: &Hip, channels: &[P], weights: &[BlendWeight], max_dim: usize) -> Result<([Array2<f32>; 3], BlendComposite)> {
+    let (rows, cols) = blend_composite_dims(channels)?;
+    let [mut r, mut g, mut b] = planes3(rows, cols);
+    let out = blend_composite_into(hip, channels, weights, max_dim, &mut r, &mut g, &mut b)?;
+    Ok(([r, g, b], out))
+}
+/// drop-in for the body of compute_auto_wb_cmd (color.rs:192-222); host-only
+pub fn compute_auto_wb(sr: &ImageStats, sg: &ImageStats, sb: &ImageStats) -> Result<AutoWb> {
+    let mut out: sys::ab_auto_wb = unsafe { std::mem::zeroed() };
+    if unsafe { sys::ab_compute_auto_wb(&stats_to_sys(sr), &stats_to_sys(sg), &stats_to_sys(sb), &mut out) } != 0 {
+        bail!("compute_auto_wb: null argument");
+    }
+    Ok(AutoWb { factors: out.factors, stability: out.stability, ref_channel: ['R', 'G', 'B'][out.ref_channel as usize] })
+}
+
 // ---- a13  core/imaging/star_mask.rs, masked_stretch.rs -------------------------------------------------------------------------------------------------
 /// drop-in for generate_star_mask (star_mask.rs:38-44)
 pub fn generate_star_mask(hip: &Hip, image: &impl PlaneSrc, config: &StarMaskConfig) -> Result<StarMaskResult, String> {

@@ -1331,6 +1331,79 @@ AB_API int ab_process_rgb_fits_view(ab_ctx *ctx, const ab_plane *r, const ab_pla
                                     int64_t max_dim, uint8_t *out_rgb8, int32_t out_on_device, uint32_t *out_bins, int32_t bins_on_device,
                                     ab_rgb_fits_view_info *info);
 
+/* ---- the compose wizard's blend and colour steps: cmd/compose/blend.rs (blend_channels_cmd :128-223) and cmd/compose/color.rs
+ * (calibrate_and_scnr_cmd :97-184, compute_auto_wb_cmd :187-224, reset_wb_cmd :51-95), up to the PNG encoder and the JSON ---------- */
+/* Both commands end alike: three ImageStats, compute_linked_stf (cmd/helpers.rs:185-202), three make_stf_u8_fn(linked, stats[c])
+ * (core/imaging/stf.rs:122-145) and render_rgb_preview_with_stf (cmd/helpers.rs:264-322).  csrc/wizard_color.hip runs each as ONE chain
+ * that stays in HBM: the planes' kernel, three statistics chains whose results are saved side by side on the device, one small
+ * workgroup that forms the linked STF and the three transforms there (linked_stf_kernel), the preview's packer reading them from HBM
+ * (preview_stf_kernel), and at most one synchronisation, which fetches info and the host outputs (info NULL and device outputs: none).
+ * reset_wb_cmd needs no entry point of its own: it is ab_compute_linked_stf of the originals' cached statistics followed by
+ * ab_render_rgb_preview with stf (the linked one three times) and stats given. */
+typedef enum {
+    AB_COLOR_STATS_EXACT_OR_FULL = 0, /* compute_image_stats of the final plane (color.rs:30, :144-154) */
+    AB_COLOR_STATS_KNOWN_RANGE = 1    /* compute_image_stats_with_known_range of the final plane (color.rs:41-47) */
+} ab_color_stats_route;
+typedef struct {
+    float factors[3];        /* (factor as f32).max(1e-6) (color.rs:115-117; f32::max: a NaN gives 1e-6) */
+    int32_t scnr_applied;    /* has_scnr && amount > 1e-7 (:139; a NaN amount is not applied) */
+    int32_t route[3];        /* ab_color_stats_route of R, G, B */
+    double known_min[3];     /* KNOWN_RANGE: orig.min * factor as f64 and orig.max * factor as f64 (swapped for a negative factor, */
+    double known_max[3];     /* :41-45); 0 on the other route */
+} ab_color_plan;
+typedef struct {
+    uint64_t rows, cols, preview_rows, preview_cols;
+    float factors[3];        /* the f32 factors applied */
+    int32_t scnr_applied;    /* "scnr_applied" (:180) */
+    int32_t route[3];        /* the statistics route each channel took */
+    ab_image_stats stats[3]; /* stats_r, stats_g, stats_b as insert_composite_rgb receives them (:169) */
+    ab_stf_params stf;       /* the linked STF: "auto_stf" (:171) */
+} ab_color_step_info;
+typedef struct {
+    uint64_t rows, cols, preview_rows, preview_cols; /* RES_DIMENSIONS = [cols, rows] (blend.rs:213) */
+    int32_t resampled;       /* needs_resample (:152) */
+    ab_image_stats stats[3]; /* RES_STATS_R / _G / _B (:216-218) */
+    ab_stf_params stf;       /* "auto_stf" (:219) */
+} ab_blend_composite_info;
+typedef struct {
+    double factors[3];       /* RES_R_FACTOR, RES_G_FACTOR, RES_B_FACTOR (color.rs:203-212) */
+    double stability[3];     /* stab_r, stab_g, stab_b: mad / median, f64::MAX when median <= 1e-10 (:196-201) */
+    int32_t ref_channel;     /* 0 R, 1 G, 2 B (:221) */
+} ab_auto_wb;
+/* Host only: what calibrate_and_scnr_cmd decides for a composite of n_pixels pixels.  A channel's statistics are taken ONCE, of its
+ * final plane, by the route that yields what the reference keeps: EXACT_OR_FULL when n_pixels <= 4 000 000 (PAR_THRESHOLD, :19), for
+ * G when SCNR is applied (:154) and for every channel when SCNR is applied with preserve_luminance (:142-152); KNOWN_RANGE otherwise
+ * (a channel SCNR does not change: its final plane is its scaled plane).  The statistics the reference computes and overwrites are
+ * never computed.  scnr may be NULL when has_scnr == 0.  A NULL orig_stats, factors or plan -> AB_ERR_INVALID. */
+AB_API int ab_color_step_plan(uint64_t n_pixels, const ab_image_stats orig_stats[3], const double factors[3], int32_t has_scnr,
+                              const ab_scnr_config *scnr, ab_color_plan *plan);
+/* calibrate_and_scnr_cmd from its loaded originals (:112: orig_r, orig_g, orig_b and their ImageStats) to the encoder's input.
+ * r, g, b: one size, host or device, any float-aligned address.  out_planes (required): three planes of that size, host or device,
+ * any float-aligned address -- what becomes __composite_r / _g / _b: bit for bit ab_calibrate_channel's planes followed by
+ * ab_apply_scnr_inplace, written by one kernel that multiplies and runs SCNR in registers (12 B read and 12 B written per pixel).
+ * out_rgb8 (nullable): preview_rows x preview_cols x 3 bytes with the dims of ab_preview_dims(rows, cols, max_dim), host or device
+ * (out_on_device) at ANY byte address: ab_render_rgb_preview's bytes with the linked stf x 3 and info->stats given (the ROUNDED byte
+ * of apply_stf, stf.rs:96-100).  Above max_dim only the picked pixels are loaded.  An output may not overlap an input or another
+ * output.  Mismatched dims, rows * cols >= 2^31, max_dim < 1 or a NULL out_planes -> AB_ERR_INVALID before anything touches the
+ * device. */
+AB_API int ab_calibrate_and_scnr(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, const ab_image_stats orig_stats[3],
+                                 const double factors[3], int32_t has_scnr, const ab_scnr_config *scnr, int64_t max_dim, ab_plane_mut *out_planes,
+                                 uint8_t *out_rgb8, int32_t out_on_device, ab_color_step_info *info);
+/* blend_channels_cmd from its loaded channels on (blend.rs:143-205).  n_channels == 0 -> AB_ERR_INVALID "No channel paths provided"
+ * (:139-141).  Channels of differing dims are resampled (bicubic, ab_resample_image) to the largest rows and the largest cols
+ * (:148-169) into a workspace of the context: the originals are untouched.  out_planes (required): three planes of those dims
+ * written by ab_blend_channels' kernel (:185; a weight whose channel_idx is out of range is skipped, a NaN reaches the planes), then
+ * three statistics chains without a known range (:187-193), the linked STF and the preview as above.  Planes, statistics, STF and
+ * bytes equal ab_blend_channels -> ab_compute_image_stats x 3 -> ab_compute_linked_stf -> ab_render_rgb_preview(stf x 3, stats).
+ * At most 16 channels and 32 weights in range, as ab_blend_channels. */
+AB_API int ab_blend_composite(ab_ctx *ctx, const ab_plane *channels, size_t n_channels, const ab_blend_weight *weights, size_t n_weights,
+                              int64_t max_dim, ab_plane_mut *out_planes, uint8_t *out_rgb8, int32_t out_on_device, ab_blend_composite_info *info);
+/* Host only: compute_auto_wb_cmd (color.rs:187-224) of the three channels' statistics.  The reference channel is R when stab_r <=
+ * stab_g && stab_r <= stab_b, else B when stab_b <= stab_g, else G; the others are scaled to its median.max(1e-10).  It
+ * restates the command, not rgb.rs: ab_select_wb_reference stays its own function (tests/test_color_step_cpu.py holds the factors of
+ * the two equal on every branch and tie, which is a property of today's reference, not a contract). */
+AB_API int ab_compute_auto_wb(const ab_image_stats *sr, const ab_image_stats *sg, const ab_image_stats *sb, ab_auto_wb *out);
+
 /* ---- bench support: a plain float4 device copy, the measured HBM ceiling ---- */
 AB_API int ab_bench_copy(ab_ctx *ctx, const float *src_dev, float *dst_dev, size_t n_floats);
 
