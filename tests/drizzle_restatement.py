@@ -79,7 +79,8 @@ def weight(kernel, cx, cy, half, ox, oy):
     if kernel == SQUARE:
         return overlap_area(cx - half, cy - half, cx + half, cy + half, float(ox), float(oy), ox + 1.0, oy + 1.0)
     if kernel == GAUSSIAN:
-        dist2 = (ox + 0.5 - cx) ** 2 + (oy + 0.5 - cy) ** 2
+        ex, ey = ox + 0.5 - cx, oy + 0.5 - cy
+        dist2 = ex * ex + ey * ey  # (:91-92 powi(2) is a multiplication: +inf for an offset of 1e300, where Python's ** raises)
         sigma = max(half, 0.5)
         return math.exp(-dist2 / (2.0 * sigma * sigma))
     return lanczos3(abs(ox + 0.5 - cx)) * lanczos3(abs(oy + 0.5 - cy))
@@ -222,7 +223,8 @@ def _frame_contributions(img, dx, dy, scale, half, kernel, out_rows, out_cols):
              * np.maximum(np.minimum(pcy + half, oyf + 1.0) - np.maximum(pcy - half, oyf), 0.0))
     elif kernel == GAUSSIAN:
         ex, ey = oxf + 0.5 - pcx, oyf + 0.5 - pcy
-        dist2 = ex * ex + ey * ey
+        with np.errstate(over="ignore"):  # (an offset of 1e300: +inf, as in the reference; the weight is exp(-inf) = 0)
+            dist2 = ex * ex + ey * ey
         sigma = max(half, 0.5)
         arg = -dist2 / (2.0 * sigma * sigma)
         w = np.zeros_like(arg)
