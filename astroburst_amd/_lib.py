@@ -438,6 +438,11 @@ def lib() -> C.CDLL:
     L.ab_align_channel_affine.argtypes = [vp, pp, pp, C.c_int, C.POINTER(AffineAlignResultC)]
     L.ab_affine_from_stars.argtypes = [C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_double), C.c_size_t, C.c_int64,
                                        C.c_int64, C.c_int, C.POINTER(AffineAlignResultC), C.POINTER(C.c_int)]
+    L.ab_triangle_votes_host.argtypes = [C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_uint32)]
+    L.ab_matches_from_votes.argtypes = [C.c_size_t, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                        C.c_size_t, C.POINTER(C.c_size_t)]
+    L.ab_triangle_votes_device.argtypes = [vp, C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_size_t), C.c_size_t,
+                                           C.c_int, C.POINTER(C.c_uint32)]
     L.ab_phase_correlate.argtypes = [vp, pp, pp, C.POINTER(PhaseCorrelationResultC)]
     L.ab_correlate_single.argtypes = [vp, pp, pp, C.POINTER(PhaseCorrelationResultC), vp]
     L.ab_apply_scnr_inplace.argtypes = [vp, pp, pp, pp, C.POINTER(ScnrConfigC)]

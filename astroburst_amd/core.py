@@ -591,6 +591,38 @@ def psf_select_stars(stars, max_val: float, rows: int, cols: int, **config):
     return [int(idx[i]) for i in range(sel.value)], int(flt.value)
 
 
+VOTE_DIM = 64  # a vote matrix is VOTE_DIM x VOTE_DIM uint32: row = reference star index, column = target star index
+
+
+def _star_xy(xy) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(xy, np.float64).reshape(-1, 2))
+
+
+def triangle_votes_host(ref_xy, tgt_xy) -> np.ndarray:
+    """The vote matrix of the library's HOST matcher (the vote half of match_triangles, affine.rs:320-350) for two star lists of
+    (x, y) -> uint32 [64, 64].  Host arithmetic in the library: no GPU."""
+    r, t = _star_xy(ref_xy), _star_xy(tgt_xy)
+    out = np.zeros((VOTE_DIM, VOTE_DIM), np.uint32)
+    dp = C.POINTER(C.c_double)
+    rc = _lib.lib().ab_triangle_votes_host(r.ctypes.data_as(dp), r.shape[0], t.ctypes.data_as(dp), t.shape[0],
+                                           out.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if rc != _lib.AB_OK:
+        raise AstroBurstError(rc, "ab_triangle_votes_host: bad arguments")
+    return out
+
+
+def matches_from_votes(votes, n_ref: int, n_tgt: int):
+    """The greedy half of match_triangles (affine.rs:351-384) on a given 64 x 64 vote matrix -> [(ref index, tgt index)] in
+    acceptance order (votes descending, ties by (ref, tgt) index).  Host arithmetic in the library: no GPU."""
+    v = np.ascontiguousarray(np.asarray(votes, np.uint32).reshape(VOTE_DIM, VOTE_DIM))
+    ri, ti = (C.c_size_t * VOTE_DIM)(), (C.c_size_t * VOTE_DIM)()
+    n = C.c_size_t(0)
+    rc = _lib.lib().ab_matches_from_votes(int(n_ref), int(n_tgt), v.ctypes.data_as(C.POINTER(C.c_uint32)), ri, ti, VOTE_DIM, C.byref(n))
+    if rc != _lib.AB_OK:
+        raise AstroBurstError(rc, "ab_matches_from_votes: bad arguments")
+    return [(int(ri[i]), int(ti[i])) for i in range(min(n.value, VOTE_DIM))]
+
+
 _SYNTH_FIELDS = {"uniform": _lib.AB_SYNTH_FIELD_UNIFORM, "king_cluster": _lib.AB_SYNTH_FIELD_KING_CLUSTER,
                  "exponential_disk": _lib.AB_SYNTH_FIELD_EXPONENTIAL_DISK}
 _SYNTH_PSFS = {"gaussian": _lib.AB_SYNTH_PSF_GAUSSIAN, "moffat": _lib.AB_SYNTH_PSF_MOFFAT, "airy": _lib.AB_SYNTH_PSF_AIRY}
@@ -1636,6 +1668,20 @@ class Context:
             return None
         return AffineAlignResult(tuple(res.transform), int(res.matched_stars), int(res.inliers), res.residual_px,
                                  AFFINE_METHODS[res.method])
+
+    def triangle_votes(self, ref_xy, targets, grouped: bool = False) -> np.ndarray:
+        """The vote matrices of the GPU matcher (the one register_frames / align_pairs_affine run after detection) for GIVEN star
+        lists: one reference list against every list of `targets` -> uint32 [len(targets), 64, 64].  grouped=False takes the targets
+        one after another, grouped=True in groups of up to eight in the given order, as a batch's two forms do."""
+        r = _star_xy(ref_xy)
+        ts = [_star_xy(t) for t in targets]
+        cat = np.ascontiguousarray(np.concatenate(ts + [np.zeros((0, 2))]) if ts else np.zeros((0, 2)))
+        counts = (C.c_size_t * max(len(ts), 1))(*[t.shape[0] for t in ts])
+        out = np.zeros((len(ts), VOTE_DIM, VOTE_DIM), np.uint32)
+        dp = C.POINTER(C.c_double)
+        self._check(self._L.ab_triangle_votes_device(self._h, r.ctypes.data_as(dp), r.shape[0], cat.ctypes.data_as(dp), counts, len(ts),
+                                                     1 if grouped else 0, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
 
     # ---- core/alignment/phase_correlation.rs ----------------------------------------------------------
     def phase_correlate(self, reference, target):

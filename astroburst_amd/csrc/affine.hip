@@ -95,8 +95,8 @@ std::array<size_t, 3> sort_triangle_vertices(const std::vector<Pt> &s, const siz
 
 // votes -> one-to-one matches (:351-384): pairs by votes descending (ties: ref index, then tgt index -- pinned,
 // see the file header), greedily keeping pairs whose two stars are both still free
-std::vector<Match> matches_from_votes(const std::vector<Pt> &rs, const std::vector<Pt> &ts, const uint32_t *votes, size_t stride) {
-    const size_t nr = rs.size(), nt = ts.size();
+// -> (ref index, tgt index) in acceptance order
+std::vector<std::pair<size_t, size_t>> match_pairs_from_votes(size_t nr, size_t nt, const uint32_t *votes, size_t stride) {
     // one u64 per pair, ordered like (votes descending, ref index, tgt index): ~votes in the high word, the indices below
     std::vector<uint64_t> pairs;
     pairs.reserve(stride * stride);
@@ -114,8 +114,8 @@ std::vector<Match> matches_from_votes(const std::vector<Pt> &rs, const std::vect
         std::nth_element(pairs.begin(), pairs.begin() + sorted_upto, pairs.end());
     }
     std::sort(pairs.begin(), pairs.begin() + sorted_upto);
-    std::vector<char> used_r(nr, 0), used_t(nt, 0);
-    std::vector<Match> out;
+    std::vector<char> used_r(std::min(nr, stride), 0), used_t(std::min(nt, stride), 0);
+    std::vector<std::pair<size_t, size_t>> out;
     const size_t full = std::min(std::min(nr, nt), kVotingStars);  // every voting star of the shorter list taken: nothing further can be accepted
     for (size_t i = 0; i < pairs.size() && out.size() < full; ++i) {
         if (i == sorted_upto) {  // the rest: only pairs whose two stars are both still free can ever be accepted -- usually a handful
@@ -129,13 +129,21 @@ std::vector<Match> matches_from_votes(const std::vector<Pt> &rs, const std::vect
         const size_t ri = (size_t)((p >> 16) & 0xffffu), ti = (size_t)(p & 0xffffu);
         if (used_r[ri] || used_t[ti]) continue;
         used_r[ri] = used_t[ti] = 1;
-        out.push_back({rs[ri][0], rs[ri][1], ts[ti][0], ts[ti][1]});
+        out.push_back({ri, ti});
     }
     return out;
 }
 
-std::vector<Match> match_triangles(const std::vector<Pt> &rs, const std::vector<Pt> &ts, const std::vector<Tri> &rt,
-                                   const std::vector<Tri> &tt) {  // :320-384
+std::vector<Match> matches_from_votes(const std::vector<Pt> &rs, const std::vector<Pt> &ts, const uint32_t *votes, size_t stride) {
+    std::vector<Match> out;
+    for (const auto &p : match_pairs_from_votes(rs.size(), ts.size(), votes, stride))
+        out.push_back({rs[p.first][0], rs[p.first][1], ts[p.second][0], ts[p.second][1]});
+    return out;
+}
+
+// the vote half of match_triangles (:320-350): votes[ref star][tgt star], kHostVoteDim x kHostVoteDim
+std::vector<uint32_t> triangle_votes(const std::vector<Pt> &rs, const std::vector<Pt> &ts, const std::vector<Tri> &rt,
+                                     const std::vector<Tri> &tt) {
     const size_t nr = rs.size(), nt = ts.size();
     std::vector<uint32_t> votes(nr * nt, 0);
     // The reference compares every ref triangle with every tgt triangle (up to 34 220^2 pairs).  Votes are
@@ -176,7 +184,12 @@ std::vector<Match> match_triangles(const std::vector<Pt> &rs, const std::vector<
     std::vector<uint32_t> sq(kHostVoteDim * kHostVoteDim, 0);
     for (size_t r = 0; r < nr && r < kHostVoteDim; ++r)
         for (size_t t = 0; t < nt && t < kHostVoteDim; ++t) sq[r * kHostVoteDim + t] = votes[r * nt + t];
-    return matches_from_votes(rs, ts, sq.data(), kHostVoteDim);
+    return sq;
+}
+
+std::vector<Match> match_triangles(const std::vector<Pt> &rs, const std::vector<Pt> &ts, const std::vector<Tri> &rt,
+                                   const std::vector<Tri> &tt) {  // :320-384
+    return matches_from_votes(rs, ts, triangle_votes(rs, ts, rt, tt).data(), kHostVoteDim);
 }
 
 bool solve_3x3(const double a[3][3], const double b[3], double x[3]) {  // :556-595
@@ -1470,5 +1483,99 @@ int ab_affine_from_stars(const double *ref_xy, size_t n_ref, const double *tgt_x
     *found = affine_from_stars(rs, ts, rows, cols, num_threads, out) ? 1 : 0;
     return AB_OK;
 } AB_CATCH_NOCTX
+
+}  // extern "C"
+
+// ---- the matcher's seam: the vote matrices and the greedy pass on GIVEN star lists ----------------------------------------------
+// Registration reaches the matcher only through images (detection first), so every star list it ever sees is a set of centroids of
+// some field.  These three entry points feed it lists directly: the host's votes, the device's votes through the very functions
+// register_one / register_group run, and the greedy pass on a given matrix.
+namespace {
+
+// x, y pairs -> points; false where a coordinate is not finite (the reference panics there -- partial_cmp().unwrap() -- and for a
+// NaN ratio the host's cells and the device's buckets visit different candidates: there is no common answer)
+bool finite_points(const double *xy, size_t n, std::vector<Pt> *out) {
+    out->resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (!std::isfinite(xy[2 * i]) || !std::isfinite(xy[2 * i + 1])) return false;
+        (*out)[i] = {xy[2 * i], xy[2 * i + 1]};
+    }
+    if (out->size() > kMaxStars) out->resize(kMaxStars);  // top_n_stars
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ab_triangle_votes_host(const double *ref_xy, size_t n_ref, const double *tgt_xy, size_t n_tgt, uint32_t *votes_out) try {
+    if ((!ref_xy && n_ref) || (!tgt_xy && n_tgt) || !votes_out) return AB_ERR_INVALID;
+    std::vector<Pt> rs, ts;
+    if (!finite_points(ref_xy, n_ref, &rs) || !finite_points(tgt_xy, n_tgt, &ts)) return AB_ERR_INVALID;
+    std::fill(votes_out, votes_out + kHostVoteDim * kHostVoteDim, 0u);
+    if (rs.size() < kMinMatchesRigid || ts.size() < kMinMatchesRigid) return AB_OK;  // (:162-168: such a pair is never matched)
+    const auto votes = triangle_votes(rs, ts, build_triangles(rs), build_triangles(ts));
+    std::copy(votes.begin(), votes.end(), votes_out);
+    return AB_OK;
+} AB_CATCH_NOCTX
+
+int ab_matches_from_votes(size_t n_ref, size_t n_tgt, const uint32_t *votes, size_t *out_ref_idx, size_t *out_tgt_idx, size_t cap,
+                          size_t *n_out) try {
+    if (!votes || !n_out || ((!out_ref_idx || !out_tgt_idx) && cap)) return AB_ERR_INVALID;
+    const auto pairs = match_pairs_from_votes(n_ref, n_tgt, votes, kHostVoteDim);
+    for (size_t i = 0; i < pairs.size() && i < cap; ++i) {
+        out_ref_idx[i] = pairs[i].first;
+        out_tgt_idx[i] = pairs[i].second;
+    }
+    *n_out = pairs.size();
+    return AB_OK;
+} AB_CATCH_NOCTX
+
+int ab_triangle_votes_device(ab_ctx *ctx, const double *ref_xy, size_t n_ref, const double *tgt_xy, const size_t *n_tgt, size_t n_targets,
+                             int grouped, uint32_t *votes_out) try {
+    if (!ctx) return AB_ERR_INVALID;
+    AB_CHECK(ctx, (ref_xy || !n_ref) && (n_tgt || !n_targets) && (votes_out || !n_targets), "null argument");
+    std::vector<Pt> rs;
+    AB_CHECK(ctx, finite_points(ref_xy, n_ref, &rs), "triangle_votes: a reference coordinate is not finite");
+    std::vector<std::vector<Pt>> ts(n_targets);
+    size_t first = 0;
+    for (size_t k = 0; k < n_targets; ++k) {
+        AB_CHECK(ctx, tgt_xy || !n_tgt[k], "null argument");
+        AB_CHECK(ctx, finite_points(n_tgt[k] ? tgt_xy + 2 * first : nullptr, n_tgt[k], &ts[k]), "triangle_votes: a coordinate of target %zu is not finite", k);
+        first += n_tgt[k];
+    }
+    const size_t words = (size_t)kVoteDim * kVoteDim;
+    std::fill(votes_out, votes_out + n_targets * words, 0u);
+    if (rs.size() < kMinMatchesRigid || n_targets == 0) return AB_OK;
+    AB_HIP(ctx, hipSetDevice(ctx->device));
+    MatchWs w;
+    AB_TRY(match_ws(ctx, &w));
+    AB_TRY(gpu_build_triangles(ctx, w, rs, 0));  // the reference table, once per call
+    std::vector<uint32_t> votes[kTriGroupMax];
+    if (!grouped) {  // register_one's matcher steps, target after target
+        for (size_t k = 0; k < n_targets; ++k) {
+            if (ts[k].size() < kMinMatchesRigid) continue;
+            AB_TRY(gpu_build_triangles(ctx, w, ts[k], 1));
+            AB_TRY(gpu_votes(ctx, w, w.counts, &votes[0]));
+            std::copy(votes[0].begin(), votes[0].end(), votes_out + k * words);
+        }
+        return AB_OK;
+    }
+    for (size_t k0 = 0; k0 < n_targets; k0 += (size_t)kTriGroupMax) {  // register_group's
+        const int G = (int)std::min<size_t>((size_t)kTriGroupMax, n_targets - k0);
+        std::vector<Pt> live[kTriGroupMax];  // a list with too few stars takes its slot as an empty one
+        bool any = false;
+        for (int k = 0; k < G; ++k)
+            if (ts[k0 + (size_t)k].size() >= kMinMatchesRigid) {
+                live[k] = ts[k0 + (size_t)k];
+                any = true;
+            }
+        if (!any) continue;
+        AB_TRY(gpu_match_group(ctx, w, live, G, votes));
+        for (int k = 0; k < G; ++k)
+            if (!live[k].empty()) std::copy(votes[k].begin(), votes[k].end(), votes_out + (k0 + (size_t)k) * words);
+    }
+    return AB_OK;
+} AB_CATCH(ctx)
 
 }  // extern "C"

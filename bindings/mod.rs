@@ -455,6 +455,39 @@ pub fn affine_from_stars(ref_xy: &[(f64, f64)], tgt_xy: &[(f64, f64)], rows: usi
     let rc = unsafe { sys::ab_affine_from_stars(r.as_ptr(), ref_xy.len(), t.as_ptr(), tgt_xy.len(), rows as i64, cols as i64, num_threads(), &mut out, &mut found) };
     (rc == sys::AB_OK && found != 0).then(|| align_from_sys(&out))
 }
+/// side of a vote matrix: row = reference star index, column = target star index
+pub const VOTE_DIM: usize = 64;
+fn flat_xy(xy: &[(f64, f64)]) -> Vec<f64> {
+    xy.iter().flat_map(|p| [p.0, p.1]).collect()
+}
+/// the vote half of match_triangles (affine.rs:320-350) of the library's host matcher: VOTE_DIM x VOTE_DIM counts, row-major
+pub fn triangle_votes_host(ref_xy: &[(f64, f64)], tgt_xy: &[(f64, f64)]) -> Option<Vec<u32>> {
+    let (r, t) = (flat_xy(ref_xy), flat_xy(tgt_xy));
+    let mut votes = vec![0u32; VOTE_DIM * VOTE_DIM];
+    let rc = unsafe { sys::ab_triangle_votes_host(r.as_ptr(), ref_xy.len(), t.as_ptr(), tgt_xy.len(), votes.as_mut_ptr()) };
+    (rc == sys::AB_OK).then_some(votes)
+}
+/// the greedy half of match_triangles (affine.rs:351-384) on a given vote matrix: (ref index, tgt index) in acceptance order
+pub fn matches_from_votes(votes: &[u32], n_ref: usize, n_tgt: usize) -> Option<Vec<(usize, usize)>> {
+    if votes.len() != VOTE_DIM * VOTE_DIM {
+        return None;
+    }
+    let (mut ri, mut ti, mut n) = (vec![0usize; VOTE_DIM], vec![0usize; VOTE_DIM], 0usize);
+    let rc = unsafe { sys::ab_matches_from_votes(n_ref, n_tgt, votes.as_ptr(), ri.as_mut_ptr(), ti.as_mut_ptr(), VOTE_DIM, &mut n) };
+    (rc == sys::AB_OK).then(|| ri.into_iter().zip(ti).take(n.min(VOTE_DIM)).collect())
+}
+/// the GPU matcher's vote matrices for given star lists (one reference list, many target lists): VOTE_DIM x VOTE_DIM counts per target;
+/// grouped = false takes the targets one after another, true in groups of up to eight, as a batch's two forms do
+pub fn triangle_votes(hip: &Hip, ref_xy: &[(f64, f64)], targets: &[Vec<(f64, f64)>], grouped: bool) -> Result<Vec<Vec<u32>>> {
+    let r = flat_xy(ref_xy);
+    let t: Vec<f64> = targets.iter().flat_map(|l| flat_xy(l)).collect();
+    let counts: Vec<usize> = targets.iter().map(|l| l.len()).collect();
+    let mut votes = vec![0u32; targets.len() * VOTE_DIM * VOTE_DIM];
+    hip.check(unsafe {
+        sys::ab_triangle_votes_device(hip.ctx, r.as_ptr(), ref_xy.len(), t.as_ptr(), counts.as_ptr(), counts.len(), grouped as i32, votes.as_mut_ptr())
+    })?;
+    Ok(votes.chunks(VOTE_DIM * VOTE_DIM).map(|m| m.to_vec()).collect())
+}
 /// drop-in for core::alignment::pair::align_pair (pair.rs:41-77)
 pub fn align_pair(hip: &Hip, reference: &impl PlaneSrc, target: &impl PlaneSrc, method: AlignMethod, rows: usize, cols: usize) -> Result<AlignPairResult> {
     match method {

@@ -288,6 +288,23 @@ AB_API int ab_align_pairs_affine(ab_ctx *ctx, const ab_plane *reference, const a
 /* the star-list half (triangles -> votes -> RANSAC -> sanity) on given centroids; host only */
 AB_API int ab_affine_from_stars(const double *ref_xy, size_t n_ref, const double *tgt_xy, size_t n_tgt, int64_t rows,
                                 int64_t cols, int num_threads, ab_affine_align_result *out, int *found);
+/* The matcher's seam (test hooks; nothing in the reference corresponds to them as functions).  Vote matrices are 64 x 64 uint32_t,
+ * row = reference star index, column = target star index; only the first 60 stars of a list form triangles and collect votes
+ * (build_triangles' limit, :285), a list is cut to its first 120 (top_n_stars), and a pair with a list of fewer than 4 stars
+ * has an all-zero matrix (:162-168).  A coordinate that is not finite is AB_ERR_INVALID (the reference panics on it).
+ *   ab_triangle_votes_host    the vote half of match_triangles (:320-350) on the host; no context
+ *   ab_matches_from_votes     the greedy half (:351-384) on a given matrix: the accepted (ref, tgt) index pairs in acceptance order,
+ *                             the first `cap` of them written, *n_out = how many there are; no context
+ *   ab_triangle_votes_device  the GPU matcher registration runs, on given lists: the targets' lists are concatenated in tgt_xy
+ *                             (n_tgt[k] stars each), votes_out holds n_targets matrices; the reference table is built once per call;
+ *                             grouped = 0 takes the targets one after another (a batch's frame-by-frame form), grouped = 1 in groups
+ *                             of up to 8 in the given order (its grouped form), a list of fewer than 4 stars holding its slot as an
+ *                             empty one */
+AB_API int ab_triangle_votes_host(const double *ref_xy, size_t n_ref, const double *tgt_xy, size_t n_tgt, uint32_t *votes_out);
+AB_API int ab_matches_from_votes(size_t n_ref, size_t n_tgt, const uint32_t *votes, size_t *out_ref_idx, size_t *out_tgt_idx, size_t cap,
+                                 size_t *n_out);
+AB_API int ab_triangle_votes_device(ab_ctx *ctx, const double *ref_xy, size_t n_ref, const double *tgt_xy, const size_t *n_tgt,
+                                    size_t n_targets, int grouped, uint32_t *votes_out);
 
 /* ---- a9  core/imaging/stats.rs ------------------------------------------------------------- */
 typedef struct { /* ImageStats, types/image.rs:2-10 */

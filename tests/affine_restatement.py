@@ -13,6 +13,9 @@ per operation, no fused multiply-add), written from the Rust and from nothing el
     core/alignment/affine.rs:589-640  fit_rigid
     core/alignment/affine.rs:642-660  compute_residual, dist
 
+triangle_votes and matches_from_votes are the two halves of match_triangles (:326-349 and :351-383) as functions of their own, for
+the tests that hold the library's vote matrices and greedy pass to them cell by cell (tests/triangle_cases.py).
+
 It shares no code with oracle/orc_affine.c nor with csrc/affine.hip (VERDICT r3 "weak" 3: those two are restatements by one
 author; this is the third, in another language, that both are held to).  Two things the Rust leaves open are taken as
 PARAMETERS of this file, because they are choices and not arithmetic:
@@ -35,6 +38,7 @@ RANSAC_ITERATIONS = 2000
 RANSAC_INLIER_PX = 3.0
 MIN_TRIANGLE_SIDE = 15.0
 MIN_VOTES = 1
+VOTING_STARS = 60                                                 # :285, build_triangles' `limit`
 MIN_INLIER_RATIO = 0.20
 MAX_RESIDUAL_PX = 5.0
 MAX_OFFSET_FRACTION = 0.40
@@ -58,7 +62,7 @@ def build_triangles(stars):                                       # :279-317
     n = len(stars)
     if n < 3:
         return []
-    limit = min(n, 60)
+    limit = min(n, VOTING_STARS)
     tris = []
     for i in range(limit):
         for j in range(i + 1, limit):
@@ -77,14 +81,20 @@ def sort_triangle_vertices(stars, idx):                           # :385-398: by
     return [v[0] for v in verts]
 
 
+def hit_indices(rt, t_mid, t_long):
+    """:335-339 for one reference triangle against EVERY target triangle: a pair is skipped when either ratio differs by more than
+    the tolerance (numpy f64 array operations: the same subtractions and compares; the second test runs on the survivors of the
+    first, as the Rust's second `if` does)"""
+    cand = np.flatnonzero(~(np.abs(rt[1] - t_mid) > TRIANGLE_TOLERANCE))
+    return cand[~(np.abs(rt[2] - t_long[cand]) > TRIANGLE_TOLERANCE)]
+
+
 def match_triangles(ref_stars, tgt_stars, ref_tris, tgt_tris, tie_break=lambda pair: pair):   # :319-383
     votes = {}
     tgt_sorted = [sort_triangle_vertices(tgt_stars, tt[0]) for tt in tgt_tris]
-    # (the two `> TRIANGLE_TOLERANCE` tests of every pair as numpy f64 array operations: the same subtractions and compares,
-    # 34 220^2 of them for 60 + 60 stars)
     t_mid, t_long = np.array([tt[1] for tt in tgt_tris]), np.array([tt[2] for tt in tgt_tris])
     for rt in ref_tris:
-        hits = np.nonzero(~(np.abs(rt[1] - t_mid) > TRIANGLE_TOLERANCE) & ~(np.abs(rt[2] - t_long) > TRIANGLE_TOLERANCE))[0]
+        hits = hit_indices(rt, t_mid, t_long)
         if hits.size == 0:
             continue
         ref_sorted = sort_triangle_vertices(ref_stars, rt[0])
@@ -104,6 +114,56 @@ def match_triangles(ref_stars, tgt_stars, ref_tris, tgt_tris, tie_break=lambda p
         used_tgt.add(ti)
         matches.append((ref_stars[ri][0], ref_stars[ri][1], tgt_stars[ti][0], tgt_stars[ti][1]))
     return matches
+
+
+VOTE_DIM = 64   # the C ABI's vote matrices: row = reference star index, column = target star index (only stars 0 .. 59 vote, :285)
+
+
+def _star_list(stars):
+    return [tuple(map(float, s)) for s in np.asarray(stars, np.float64).reshape(-1, 2)][:MAX_STARS]
+
+
+def triangle_votes(ref_stars, tgt_stars):
+    """The votes of match_triangles (:326-349) as a VOTE_DIM x VOTE_DIM integer matrix, behind the driver's gates (:162-168: a list
+    of fewer than MIN_MATCHES_RIGID stars is never matched -> zeros).  Same arithmetic as match_triangles above -- build_triangles,
+    sort_triangle_vertices, the two `> TRIANGLE_TOLERANCE` tests of EVERY pair, no bucketing -- with the hits of one reference
+    triangle counted by numpy (a 60-star lattice against itself has 1.1e7 matching pairs)."""
+    votes = np.zeros((VOTE_DIM, VOTE_DIM), np.int64)
+    ref_stars, tgt_stars = _star_list(ref_stars), _star_list(tgt_stars)
+    if len(ref_stars) < MIN_MATCHES_RIGID or len(tgt_stars) < MIN_MATCHES_RIGID:
+        return votes
+    ref_tris, tgt_tris = build_triangles(ref_stars), build_triangles(tgt_stars)
+    if not ref_tris or not tgt_tris:
+        return votes
+    tgt_sorted = np.array([sort_triangle_vertices(tgt_stars, tt[0]) for tt in tgt_tris], np.int64)   # [n, 3]
+    t_mid, t_long = np.array([tt[1] for tt in tgt_tris]), np.array([tt[2] for tt in tgt_tris])
+    for rt in ref_tris:
+        hits = hit_indices(rt, t_mid, t_long)
+        if hits.size == 0:
+            continue
+        ref_sorted = sort_triangle_vertices(ref_stars, rt[0])
+        hit_verts = tgt_sorted[hits]
+        for p in range(3):
+            votes[ref_sorted[p]] += np.bincount(hit_verts[:, p], minlength=VOTE_DIM)
+    return votes
+
+
+def matches_from_votes(votes, n_ref, n_tgt, tie_break=lambda pair: pair):
+    """The greedy half of match_triangles (:351-383) on a vote matrix -> [(ref index, tgt index)] in acceptance order.  The
+    HashMap holds the pairs that received a vote; every one of them is sorted (no partial sort), ties by `tie_break`."""
+    votes = np.asarray(votes)
+    pairs = [((r, t), int(votes[r, t])) for r in range(min(n_ref, VOTE_DIM)) for t in range(min(n_tgt, VOTE_DIM)) if votes[r, t] > 0]
+    pairs.sort(key=lambda kv: (-kv[1], tie_break(kv[0])))
+    used_ref, used_tgt, out = set(), set(), []
+    for (ri, ti), v in pairs:
+        if v < MIN_VOTES:
+            break
+        if ri in used_ref or ti in used_tgt:
+            continue
+        used_ref.add(ri)
+        used_tgt.add(ti)
+        out.append((ri, ti))
+    return out
 
 
 def solve_3x3(a, b):                                              # :552-587
@@ -257,7 +317,11 @@ def affine_from_stars(ref_stars, tgt_stars, rows, cols, num_threads=8, tie_break
     ref_tris, tgt_tris = build_triangles(ref_stars), build_triangles(tgt_stars)
     if not ref_tris or not tgt_tris:
         return None
-    matches = match_triangles(ref_stars, tgt_stars, ref_tris, tgt_tris, tie_break)
+    return affine_from_matches(match_triangles(ref_stars, tgt_stars, ref_tris, tgt_tris, tie_break), rows, cols, num_threads)
+
+
+def affine_from_matches(matches, rows, cols, num_threads=8):
+    """affine.rs:172-204: the driver from the matched pairs on"""
     if len(matches) < MIN_MATCHES_RIGID:
         return None
     if len(matches) >= MIN_MATCHES_AFFINE:
@@ -268,3 +332,11 @@ def affine_from_stars(ref_stars, tgt_stars, rows, cols, num_threads=8, tie_break
     if res is not None and check_transform_sanity(res, rows, cols):
         return res
     return None
+
+
+def affine_from_votes(ref_stars, tgt_stars, votes, rows, cols, num_threads=8, tie_break=lambda pair: pair):
+    """affine_from_stars for a caller that holds triangle_votes(ref_stars, tgt_stars) already (a 60-star lattice takes seconds):
+    the greedy pass on the matrix, then the same tail"""
+    ref_stars, tgt_stars = _star_list(ref_stars), _star_list(tgt_stars)
+    pairs = matches_from_votes(votes, len(ref_stars), len(tgt_stars), tie_break)
+    return affine_from_matches([ref_stars[ri] + tgt_stars[ti] for ri, ti in pairs], rows, cols, num_threads)
