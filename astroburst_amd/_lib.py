@@ -328,6 +328,24 @@ class AutoWbC(C.Structure):  # ab_auto_wb: compute_auto_wb_cmd's JSON (color.rs:
     _fields_ = [("factors", C.c_double * 3), ("stability", C.c_double * 3), ("ref_channel", C.c_int32)]
 
 
+AB_MASK_PER_CHANNEL, AB_MASK_SHARED_LUMINANCE = range(2)
+
+
+class ArcsinhCompositeInfoC(C.Structure):  # ab_arcsinh_composite_info: arcsinh_stretch_composite_cmd's (cmd/processing/stretch.rs:117-122)
+    _fields_ = [("rows", C.c_uint64), ("cols", C.c_uint64), ("preview_rows", C.c_uint64), ("preview_cols", C.c_uint64),
+                ("factor", C.c_float), ("global_min", C.c_float), ("global_max", C.c_float), ("degenerate", C.c_int32)]
+
+
+class ArcsinhViewInfoC(C.Structure):  # ab_arcsinh_view_info: apply_arcsinh_stretch_cmd's (stretch.rs:35-41) and its preview's statistics
+    _fields_ = [("rows", C.c_uint64), ("cols", C.c_uint64), ("factor", C.c_float), ("data_min", C.c_float), ("data_max", C.c_float),
+                ("degenerate", C.c_int32), ("stats", ImageStatsC), ("stf", StfParamsC)]
+
+
+class MaskedStretchCompositeInfoC(C.Structure):  # ab_masked_stretch_composite_info: masked_stretch_composite_cmd's (stretch.rs:211-219)
+    _fields_ = [("rows", C.c_uint64), ("cols", C.c_uint64), ("preview_rows", C.c_uint64), ("preview_cols", C.c_uint64),
+                ("channels", MaskedStretchResultC * 3), ("stars_masked", C.c_uint64), ("mask_coverage", C.c_double), ("mask_mode", C.c_int32)]
+
+
 class DrizzleResultC(C.Structure):  # DrizzleResult's scalars (drizzle.rs:335-344)
     _fields_ = [("frame_count", C.c_size_t), ("output_scale", C.c_double), ("in_rows", C.c_int64), ("in_cols", C.c_int64),
                 ("out_rows", C.c_int64), ("out_cols", C.c_int64), ("rejected_pixels", C.c_uint64)]
@@ -640,6 +658,12 @@ def lib() -> C.CDLL:
     L.ab_blend_composite.argtypes = [vp, pp, C.c_size_t, C.POINTER(BlendWeightC), C.c_size_t, C.c_int64, pmp, vp, C.c_int32,
                                      C.POINTER(BlendCompositeInfoC)]
     L.ab_compute_auto_wb.argtypes = [isp, isp, isp, C.POINTER(AutoWbC)]
+    f32p, msc = C.POINTER(C.c_float), C.POINTER(MaskedStretchConfigC)
+    L.ab_arcsinh_rgb_range.argtypes = [isp, f32p]
+    L.ab_arcsinh_stretch_rgb.argtypes = [vp, pp, pp, pp, f32p, f32p, C.c_float, C.c_float, pmp, f32p]
+    L.ab_arcsinh_stretch_composite.argtypes = [vp, pp, pp, pp, C.c_double, f32p, f32p, C.c_int64, pmp, vp, C.c_int32, C.POINTER(ArcsinhCompositeInfoC)]
+    L.ab_arcsinh_stretch_view.argtypes = [vp, pp, C.c_double, pmp, vp, C.c_int32, C.POINTER(ArcsinhViewInfoC)]
+    L.ab_masked_stretch_composite.argtypes = [vp, pp, pp, pp, msc, C.c_int32, C.c_int64, pmp, vp, C.c_int32, C.POINTER(MaskedStretchCompositeInfoC)]
     for name in declared_symbols():
         fn = getattr(L, name)  # AttributeError here = header / library drift
         if fn.restype is C.c_int and name not in ("ab_last_error", "ab_version", "ab_ctx_get_stream", "ab_comm_collectives_issued"):

@@ -393,6 +393,61 @@ def compute_auto_wb(sr, sg, sb) -> AutoWb:
     return AutoWb(tuple(float(v) for v in out.factors), tuple(float(v) for v in out.stability), "RGB"[out.ref_channel])
 
 
+MASK_PER_CHANNEL, MASK_SHARED_LUMINANCE = _lib.AB_MASK_PER_CHANNEL, _lib.AB_MASK_SHARED_LUMINANCE
+
+
+@dataclass
+class ArcsinhCompositeResult:  # arcsinh_stretch_composite_cmd's (cmd/processing/stretch.rs:94-124)
+    planes: object         # (r, g, b) stretched, or None (the command discards them)
+    rgb8: object           # uint8 (preview_rows, preview_cols, 3), or None
+    rows: int
+    cols: int
+    preview_rows: int
+    preview_cols: int
+    factor: object         # the clamped f32 factor, or None (fetch=False)
+    global_min: object     # float, or None
+    global_max: object
+    degenerate: object     # bool: the range is below 1e-10, planes and bytes are zeros; or None
+
+
+@dataclass
+class ArcsinhViewResult:  # apply_arcsinh_stretch_cmd's (stretch.rs:15-43) with render_and_save's preview (cmd/common.rs:209-240)
+    plane: object          # the stretched plane: write_fits_mono's input
+    u8: object             # uint8 (rows, cols), or None
+    rows: int
+    cols: int
+    factor: object         # the clamped f32 factor, or None (fetch=False)
+    data_min: object
+    data_max: object
+    degenerate: object
+    stats: object          # ImageStats of the stretched plane, or None
+    stf: object            # StfParams, or None
+
+
+@dataclass
+class MaskedStretchCompositeResult:  # masked_stretch_composite_cmd's (stretch.rs:135-221)
+    planes: object         # (r, g, b) stretched, or None
+    rgb8: object           # uint8 (preview_rows, preview_cols, 3), or None
+    rows: int
+    cols: int
+    preview_rows: int
+    preview_cols: int
+    channels: object       # 3 x MaskedStretchResult (image None), or None (fetch=False)
+    stars_masked: object   # the shared mask's, or the sum of the three channels'
+    mask_coverage: object  # the shared mask's, or the mean of the three
+    mask_mode: object      # "shared_luminance" | "per_channel"
+
+
+def arcsinh_rgb_range(sr, sg, sb) -> tuple:
+    """(global_min, global_max) of arcsinh_stretch_rgb_with_stats (core/imaging/stretch.rs:72-78): the f32 fold of three channels'
+    ImageStats.  Host-only."""
+    out = (C.c_float * 2)()
+    rc = _lib.lib().ab_arcsinh_rgb_range(_stats3((sr, sg, sb)), out)
+    if rc != _lib.AB_OK:
+        raise AstroBurstError(rc, "ab_arcsinh_rgb_range: bad arguments")
+    return float(out[0]), float(out[1])
+
+
 HISTOGRAM_BINS = 65536     # stats.rs:8: what compute_histogram_with_stats builds before the fold
 
 
@@ -2775,6 +2830,91 @@ class Context:
         return BlendCompositeResult(planes, rgb8, int(info.rows), int(info.cols), int(info.preview_rows), int(info.preview_cols),
                                     bool(info.resampled), tuple(self._stats_out(s) for s in info.stats),
                                     StfParams(info.stf.shadow, info.stf.midtone, info.stf.highlight))
+
+    # ---- cmd/processing/stretch.rs: the wizard's stretch step ------------------------------------------------------------------
+    arcsinh_rgb_range = staticmethod(arcsinh_rgb_range)
+
+    def _stretch_outputs(self, like, rows, cols, max_dim, want_planes, want_rgb8, out, out_planes, keep):
+        """_composite_outputs with optional planes: (None, None, ...) when neither want_planes nor out_planes asks for them"""
+        if want_planes or out_planes is not None:
+            return self._composite_outputs(like, rows, cols, max_dim, want_rgb8, out, out_planes, keep)
+        ph, pw = self.preview_dims(rows, cols, max_dim) if max_dim > 0 else (1, 1)
+        rgb8, ptr, dev = self._bytes_out(like, (ph, pw, 3), out) if (want_rgb8 or out is not None) else (None, None, 0)
+        return None, None, rgb8, ptr, dev, ph, pw
+
+    @staticmethod
+    def _range_args(global_range):
+        if global_range is None:
+            return None, None
+        return C.byref(C.c_float(global_range[0])), C.byref(C.c_float(global_range[1]))
+
+    def arcsinh_stretch_rgb(self, r, g, b, factor, gamma=1.0, global_range=None, fetch=True, out_planes=None):
+        """arcsinh_stretch_rgb_with_stats (core/imaging/stretch.rs:56-90): one streaming pass for the global range (skipped with
+        global_range=(min, max)), one kernel for the three planes.  -> ((r, g, b), (global_min, global_max) | None)."""
+        keep = []
+        pr, pg, pb = (self._plane(x, keep) for x in (r, g, b))
+        rows, cols = int(pr.rows), int(pr.cols)
+        planes, pp, _, _, _, _, _ = self._composite_outputs(r, rows, cols, 1, False, None, out_planes, keep)
+        mn, mx = self._range_args(global_range)
+        mm = (C.c_float * 2)()
+        self._check(self._L.ab_arcsinh_stretch_rgb(self._h, C.byref(pr), C.byref(pg), C.byref(pb), mn, mx, C.c_float(factor), C.c_float(gamma), pp,
+                                                   mm if fetch else None))
+        return planes, ((float(mm[0]), float(mm[1])) if fetch else None)
+
+    def arcsinh_stretch_composite(self, r, g, b, factor, max_dim=4096, global_range=None, fetch=True, want_planes=False, want_rgb8=True, out=None,
+                                  out_planes=None) -> ArcsinhCompositeResult:
+        """arcsinh_stretch_composite_cmd (cmd/processing/stretch.rs:94-124) from the loaded composite to the encoder's input: the range
+        pass, then the stretch and the truncating packer in registers; above max_dim without planes only the picked pixels are
+        stretched.  fetch=False with device outputs keeps the call asynchronous (the scalars are then None)."""
+        keep = []
+        pr, pg, pb = (self._plane(x, keep) for x in (r, g, b))
+        rows, cols = int(pr.rows), int(pr.cols)
+        planes, pp, rgb8, ptr, dev, ph, pw = self._stretch_outputs(r, rows, cols, max_dim, want_planes, want_rgb8, out, out_planes, keep)
+        mn, mx = self._range_args(global_range)
+        info = _lib.ArcsinhCompositeInfoC()
+        self._check(self._L.ab_arcsinh_stretch_composite(self._h, C.byref(pr), C.byref(pg), C.byref(pb), float(factor), mn, mx, int(max_dim), pp, ptr, dev,
+                                                         C.byref(info) if fetch else None))
+        if not fetch:
+            return ArcsinhCompositeResult(planes, rgb8, rows, cols, ph, pw, None, None, None, None)
+        return ArcsinhCompositeResult(planes, rgb8, int(info.rows), int(info.cols), int(info.preview_rows), int(info.preview_cols), float(info.factor),
+                                      float(info.global_min), float(info.global_max), bool(info.degenerate))
+
+    def arcsinh_stretch_view(self, image, factor, fetch=True, want_u8=True, out=None, out_plane=None) -> ArcsinhViewResult:
+        """apply_arcsinh_stretch_cmd (stretch.rs:15-43) with render_and_save's preview as one chain: the range pass, the stretch, the
+        statistics and the STF of the stretched plane, one synchronisation."""
+        keep = []
+        pi = self._plane(image, keep)
+        rows, cols = int(pi.rows), int(pi.cols)
+        if out_plane is None:
+            out_plane = self._new_like(image, rows, cols)
+        po = self._out_plane(out_plane, keep, out_plane.shape[0], out_plane.shape[1])   # (its own dims: the library refuses a mismatch)
+        u8, ptr, dev = self._bytes_out(image, (rows, cols), out) if (want_u8 or out is not None) else (None, None, 0)
+        info = _lib.ArcsinhViewInfoC()
+        self._check(self._L.ab_arcsinh_stretch_view(self._h, C.byref(pi), float(factor), C.byref(po), ptr, dev, C.byref(info) if fetch else None))
+        if not fetch:
+            return ArcsinhViewResult(out_plane, u8, rows, cols, None, None, None, None, None, None)
+        return ArcsinhViewResult(out_plane, u8, int(info.rows), int(info.cols), float(info.factor), float(info.data_min), float(info.data_max),
+                                 bool(info.degenerate), self._stats_out(info.stats), StfParams(info.stf.shadow, info.stf.midtone, info.stf.highlight))
+
+    def masked_stretch_composite(self, r, g, b, shared_mask=False, max_dim=4096, iterations=10, target_background=0.25, mask_growth=2.5,
+                                 mask_softness=4.0, luminance_protect=True, luminance_ceiling=0.85, protection_amount=0.85, convergence_threshold=1e-5,
+                                 fetch=True, want_planes=False, want_rgb8=True, out=None, out_planes=None) -> MaskedStretchCompositeResult:
+        """masked_stretch_composite_cmd (stretch.rs:135-221): masked_stretch_rgb_shared (shared_mask) or masked_stretch x 3, then the
+        truncating packer; without planes the stretched channels stay in a workspace of the context."""
+        keep = []
+        pr, pg, pb = (self._plane(x, keep) for x in (r, g, b))
+        rows, cols = int(pr.rows), int(pr.cols)
+        planes, pp, rgb8, ptr, dev, ph, pw = self._stretch_outputs(r, rows, cols, max_dim, want_planes, want_rgb8, out, out_planes, keep)
+        cfg = self._ms_cfg(iterations, target_background, mask_growth, mask_softness, luminance_protect, luminance_ceiling, protection_amount,
+                           convergence_threshold)
+        info = _lib.MaskedStretchCompositeInfoC()
+        self._check(self._L.ab_masked_stretch_composite(self._h, C.byref(pr), C.byref(pg), C.byref(pb), C.byref(cfg), int(bool(shared_mask)), int(max_dim),
+                                                        pp, ptr, dev, C.byref(info) if fetch else None))
+        if not fetch:
+            return MaskedStretchCompositeResult(planes, rgb8, rows, cols, ph, pw, None, None, None, None)
+        return MaskedStretchCompositeResult(planes, rgb8, int(info.rows), int(info.cols), int(info.preview_rows), int(info.preview_cols),
+                                            tuple(self._ms_result(None, x) for x in info.channels), int(info.stars_masked), float(info.mask_coverage),
+                                            "shared_luminance" if info.mask_mode == MASK_SHARED_LUMINANCE else "per_channel")
 
     # ---- cmd/compose/crop.rs ---------------------------------------------------------------------------------
     @staticmethod

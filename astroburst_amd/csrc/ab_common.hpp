@@ -66,6 +66,7 @@ enum {
     AB_WS_TONE,               // the tone editor's three curve LUTs, 3 x 4096 f32 (tone.hip)
     AB_WS_VIEW,               // the open-file view: 65 536 source bins, display bins bound for the host, three channels' results (view.hip)
     AB_WS_WIZARD,             // the blend / colour steps: three channels' statistics, the linked STF and transforms, resampled channels (wizard_color.hip)
+    AB_WS_STRETCH,            // the stretch steps: the range words and what info reports, host-bound bytes, planes nobody asked for (wizard_stretch.hip)
     AB_WS_SLOTS
 };
 

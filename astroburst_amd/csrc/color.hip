@@ -13,6 +13,7 @@
 // separate f32 operations in weight order (no FMA contraction) so the result is bit-identical to
 // the reference's `rv += v * rw`.  The curve LUT (4096 f32 = 16 KiB) is staged in LDS.
 #include "ab_common.hpp"
+#include "arcsinh_device.hpp"
 #include "scnr_device.hpp"
 
 #include <algorithm>
@@ -119,15 +120,7 @@ __global__ __launch_bounds__(kBlock) void arcsinh_kernel(const float *in, int64_
                                                          float inv_denom, int apply_gamma, float gamma, float *out) {
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-        const float val = in[i];
-        float r = 0.0f;
-        if (__builtin_isfinite(val)) {                             // stretch.rs:36-43
-            float norm = (val - dmin) * inv_range;
-            norm = norm < 0.0f ? 0.0f : (norm > 1.0f ? 1.0f : norm);
-            const float stretched = asinhf(norm * factor) * inv_denom;
-            r = apply_gamma ? powf(stretched, gamma) : stretched;
-        }
-        out[i] = r;
+        out[i] = arcsinh_px(in[i], dmin, inv_range, factor, inv_denom, apply_gamma, gamma);  // stretch.rs:34-42
     }
 }
 

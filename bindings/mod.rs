@@ -1925,6 +1925,132 @@ pub fn masked_stretch_rgb_shared_into(
     Ok((res3, shared))
 }
 
+// ---- the compose wizard's stretch step: cmd/processing/stretch.rs, core/imaging/stretch.rs:47-90 -----------------------------------------------------------
+/// what arcsinh_stretch_composite_cmd encodes and reports (stretch.rs:94-124): pixels is RgbImage::from_raw's input
+pub struct ArcsinhComposite {
+    pub pixels: Vec<u8>,
+    pub dims: (usize, usize),
+    pub preview_dims: (usize, usize),
+    pub factor: f32,
+    pub global_range: (f32, f32),
+    pub degenerate: bool,
+}
+/// what apply_arcsinh_stretch_cmd saves and reports (stretch.rs:15-43 with render_and_save, cmd/common.rs:209-240)
+pub struct ArcsinhView {
+    pub stretched: Array2<f32>,
+    pub pixels: Vec<u8>,
+    pub dims: (usize, usize),
+    pub factor: f32,
+    pub data_range: (f32, f32),
+    pub degenerate: bool,
+    pub stats: ImageStats,
+    pub stf: StfParams,
+}
+/// one channel of masked_stretch_composite_cmd's "channels" (stretch.rs:126-132)
+#[derive(Clone, Copy, Debug)]
+pub struct MaskedChannelStats {
+    pub iterations_run: usize,
+    pub final_background: f64,
+    pub converged: bool,
+}
+/// what masked_stretch_composite_cmd encodes and reports (stretch.rs:135-221)
+pub struct MaskedStretchComposite {
+    pub pixels: Vec<u8>,
+    pub dims: (usize, usize),
+    pub preview_dims: (usize, usize),
+    pub channels: [MaskedChannelStats; 3],
+    pub stars_masked: usize,
+    pub mask_coverage: f64,
+    pub mask_mode: &'static str,
+}
+fn opt_ptr(v: &Option<f32>) -> *const f32 {
+    match v {
+        Some(x) => x as *const f32,
+        None => std::ptr::null(),
+    }
+}
+/// the fold of stretch.rs:72-78 over three channels' cached statistics: (global_min, global_max); host-only
+pub fn arcsinh_rgb_range(sr: &ImageStats, sg: &ImageStats, sb: &ImageStats) -> (f32, f32) {
+    let s = [stats_to_sys(sr), stats_to_sys(sg), stats_to_sys(sb)];
+    let mut mm = [0f32; 2];
+    unsafe { sys::ab_arcsinh_rgb_range(s.as_ptr(), mm.as_mut_ptr()) };
+    (mm[0], mm[1])
+}
+/// drop-in for arcsinh_stretch_rgb_with_stats (core/imaging/stretch.rs:56-90): one range pass unless both values are given, one kernel
+pub fn arcsinh_stretch_rgb_with_stats(hip: &Hip, r: &impl PlaneSrc, g: &impl PlaneSrc, b: &impl PlaneSrc, global_min: Option<f32>, global_max: Option<f32>, factor: f32,
+                                      gamma: f32) -> Result<(Array2<f32>, Array2<f32>, Array2<f32>)> {
+    let (rows, cols) = r.dims();
+    let [mut or, mut og, mut ob] = planes3(rows, cols);
+    // (Some, None) and (None, Some) compute the range like (None, None): stretch.rs:69-71
+    let (mn, mx) = if global_min.is_some() && global_max.is_some() { (global_min, global_max) } else { (None, None) };
+    let mut pp = [or.ab_mut(), og.ab_mut(), ob.ab_mut()];
+    hip.check(unsafe { sys::ab_arcsinh_stretch_rgb(hip.ctx, &r.ab(), &g.ab(), &b.ab(), opt_ptr(&mn), opt_ptr(&mx), factor, gamma, pp.as_mut_ptr(), std::ptr::null_mut()) })?;
+    Ok((or, og, ob))
+}
+/// drop-in for arcsinh_stretch_rgb (core/imaging/stretch.rs:47-54)
+pub fn arcsinh_stretch_rgb(hip: &Hip, r: &impl PlaneSrc, g: &impl PlaneSrc, b: &impl PlaneSrc, factor: f32) -> Result<(Array2<f32>, Array2<f32>, Array2<f32>)> {
+    arcsinh_stretch_rgb_with_stats(hip, r, g, b, None, None, factor, 1.0)
+}
+/// arcsinh_stretch_composite_cmd (stretch.rs:94-124) from the loaded composite to the encoder's input; the command discards the planes, so none are written.
+/// global_range: the cached statistics' fold (arcsinh_rgb_range), which skips the range pass
+pub fn arcsinh_stretch_composite(hip: &Hip, r: &impl PlaneSrc, g: &impl PlaneSrc, b: &impl PlaneSrc, factor: f64, global_range: Option<(f32, f32)>, max_dim: usize) -> Result<ArcsinhComposite> {
+    let (rows, cols) = r.dims();
+    let (ph, pw) = preview_dims(rows, cols, max_dim);
+    let (mn, mx) = (global_range.map(|v| v.0), global_range.map(|v| v.1));
+    let mut pixels = vec![0u8; ph * pw * 3];
+    let mut info: sys::ab_arcsinh_composite_info = unsafe { std::mem::zeroed() };
+    hip.check(unsafe {
+        sys::ab_arcsinh_stretch_composite(hip.ctx, &r.ab(), &g.ab(), &b.ab(), factor, opt_ptr(&mn), opt_ptr(&mx), max_dim as i64, std::ptr::null_mut(), pixels.as_mut_ptr(), 0, &mut info)
+    })?;
+    Ok(ArcsinhComposite {
+        pixels,
+        dims: (info.rows as usize, info.cols as usize),
+        preview_dims: (info.preview_rows as usize, info.preview_cols as usize),
+        factor: info.factor,
+        global_range: (info.global_min, info.global_max),
+        degenerate: info.degenerate != 0,
+    })
+}
+/// apply_arcsinh_stretch_cmd (stretch.rs:15-43) with render_and_save's preview as one device chain with one synchronisation
+pub fn arcsinh_stretch_view(hip: &Hip, image: &impl PlaneSrc, factor: f64) -> Result<ArcsinhView> {
+    let (rows, cols) = image.dims();
+    let mut stretched = Array2::<f32>::zeros((rows, cols));
+    let mut pixels = vec![0u8; rows * cols];
+    let mut info: sys::ab_arcsinh_view_info = unsafe { std::mem::zeroed() };
+    hip.check(unsafe { sys::ab_arcsinh_stretch_view(hip.ctx, &image.ab(), factor, &mut stretched.ab_mut(), pixels.as_mut_ptr(), 0, &mut info) })?;
+    Ok(ArcsinhView {
+        stretched,
+        pixels,
+        dims: (info.rows as usize, info.cols as usize),
+        factor: info.factor,
+        data_range: (info.data_min, info.data_max),
+        degenerate: info.degenerate != 0,
+        stats: stats_from_sys(&info.stats),
+        stf: stf_from_sys(&info.stf),
+    })
+}
+/// masked_stretch_composite_cmd (stretch.rs:135-221): masked_stretch_rgb_shared (shared_mask) or masked_stretch x 3, then the preview; the stretched
+/// channels stay in a workspace of the context
+pub fn masked_stretch_composite(hip: &Hip, r: &impl PlaneSrc, g: &impl PlaneSrc, b: &impl PlaneSrc, config: &MaskedStretchConfig, shared_mask: bool, max_dim: usize) -> Result<MaskedStretchComposite> {
+    let (rows, cols) = r.dims();
+    let (ph, pw) = preview_dims(rows, cols, max_dim);
+    let mut pixels = vec![0u8; ph * pw * 3];
+    let mut info: sys::ab_masked_stretch_composite_info = unsafe { std::mem::zeroed() };
+    hip.check(unsafe {
+        sys::ab_masked_stretch_composite(hip.ctx, &r.ab(), &g.ab(), &b.ab(), &masked_cfg(config), shared_mask as i32, max_dim as i64, std::ptr::null_mut(), pixels.as_mut_ptr(), 0, &mut info)
+    })?;
+    let ch = |c: &sys::ab_masked_stretch_result| MaskedChannelStats { iterations_run: c.iterations_run, final_background: c.final_background, converged: c.converged != 0 };
+    Ok(MaskedStretchComposite {
+        pixels,
+        dims: (info.rows as usize, info.cols as usize),
+        preview_dims: (info.preview_rows as usize, info.preview_cols as usize),
+        channels: [ch(&info.channels[0]), ch(&info.channels[1]), ch(&info.channels[2])],
+        stars_masked: info.stars_masked as usize,
+        mask_coverage: info.mask_coverage,
+        mask_mode: if info.mask_mode == sys::AB_MASK_SHARED_LUMINANCE as i32 { "shared_luminance" } else { "per_channel" },
+    })
+}
+
 // ---- a17  core/compose/rgb.rs, white_balance.rs, lrgb.rs, core/imaging/resample.rs ---------------------------------------------------------------------
 /// drop-in for resample_image (resample.rs:25-61)
 pub fn resample_image(hip: &Hip, image: &impl PlaneSrc, target_rows: usize, target_cols: usize) -> Result<Array2<f32>> {

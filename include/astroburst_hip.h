@@ -1421,6 +1421,86 @@ AB_API int ab_blend_composite(ab_ctx *ctx, const ab_plane *channels, size_t n_ch
  * the two equal on every branch and tie, which is a property of today's reference, not a contract). */
 AB_API int ab_compute_auto_wb(const ab_image_stats *sr, const ab_image_stats *sg, const ab_image_stats *sb, ab_auto_wb *out);
 
+/* ---- the compose wizard's stretch step: cmd/processing/stretch.rs (apply_arcsinh_stretch_cmd :15-43, arcsinh_stretch_composite_cmd
+ * :94-124, masked_stretch_composite_cmd :135-221) and core/imaging/stretch.rs (arcsinh_stretch_rgb_with_stats :56-90) ------------------ */
+/* arcsinh_stretch_rgb keeps two numbers of its three compute_image_stats calls: the smallest minimum and the largest maximum
+ * (stretch.rs:72-78).  csrc/wizard_stretch.hip finds them in ONE streaming pass over the three planes (12 B per pixel: per channel the
+ * extremes of the valid pixels, finite and > 1e-7, stats.rs:11-13; a channel without one contributes 0 to both, :46-48) and forms range,
+ * the range < 1e-10 -> zeros decision and the correctly rounded 1 / range on the device, so no host round trip stands between the pass
+ * and the stretch.  The per-pixel arithmetic is ab_arcsinh_stretch_with_stats' own (csrc/arcsinh_device.hpp).
+ * masked_stretch_cmd (:46-91) needs no entry point of its own: it is ab_masked_stretch followed by ab_auto_stretch_preview of the
+ * result.
+ * The factor of the two commands is (factor as f32).clamp(1.0, 500.0) (:26, :102).  f32::clamp keeps a NaN; with a NaN factor
+ * arcsinh_stretch_with_stats (core/imaging/stretch.rs:17-42) passes its early return (NaN.abs() < 1e-10 is false), forms
+ * inv_denom = 1 / asinh(NaN) = NaN, and every FINITE pixel becomes NaN while a non-finite pixel becomes 0 (:35-36); a degenerate range
+ * still yields zeros (:22-24).  The preview's bytes are then all 0 (NaN as u8) and the mono view's statistics are
+ * ImageStats::default(). */
+typedef struct {
+    uint64_t rows, cols, preview_rows, preview_cols; /* RES_DIMENSIONS = [cols, rows] (stretch.rs:121) */
+    float factor;                                    /* clamped_factor: RES_STRETCH_FACTOR (:119) */
+    float global_min, global_max;                    /* what the three channels were normalised with */
+    int32_t degenerate;                              /* global_max - global_min < 1e-10: planes and bytes are zeros */
+} ab_arcsinh_composite_info;
+typedef struct {
+    uint64_t rows, cols;     /* RES_DIMENSIONS = [cols, rows] (stretch.rs:40) */
+    float factor;            /* clamped_factor: RES_STRETCH_FACTOR (:38) */
+    float data_min, data_max; /* stats.min as f32, stats.max as f32 of the input (core/imaging/stretch.rs:6-7) */
+    int32_t degenerate;
+    ab_image_stats stats;    /* of the STRETCHED plane: what render_and_save's auto_stretch_preview computes (cmd/common.rs:18-22) */
+    ab_stf_params stf;       /* auto_stf(stats, default) */
+} ab_arcsinh_view_info;
+typedef enum {
+    AB_MASK_PER_CHANNEL = 0,     /* "per_channel" (stretch.rs:197) */
+    AB_MASK_SHARED_LUMINANCE = 1 /* "shared_luminance" (:174) */
+} ab_mask_mode;
+typedef struct {
+    uint64_t rows, cols, preview_rows, preview_cols; /* RES_DIMENSIONS = [cols, rows] (stretch.rs:218) */
+    ab_masked_stretch_result channels[3];            /* "channels": r, g, b (:166-170, :187-191) */
+    uint64_t stars_masked;                           /* RES_STARS_MASKED: the shared mask's, or the sum of the three (:192) */
+    double mask_coverage;                            /* RES_MASK_COVERAGE: the shared mask's, or (cr + cg + cb) / 3.0 (:193) */
+    int32_t mask_mode;                               /* ab_mask_mode */
+} ab_masked_stretch_composite_info;
+/* Host only: the fold of stretch.rs:72-78 over three channels' statistics -- out_min_max[0] = (sr.min as f32).min(sg.min as f32)
+ * .min(sb.min as f32), [1] likewise with max.  A caller that holds cached statistics passes the two values to the calls below and
+ * skips their range pass.  A NULL argument -> AB_ERR_INVALID. */
+AB_API int ab_arcsinh_rgb_range(const ab_image_stats st[3], float out_min_max[2]);
+/* arcsinh_stretch_rgb_with_stats (core/imaging/stretch.rs:56-90).  r, g, b: one size, host or device, any float-aligned address.
+ * global_min / global_max: both given (Some, Some) or both NULL (the range pass computes them: they equal
+ * (float)ab_compute_image_stats(c).min / .max folded by ab_arcsinh_rgb_range).  |factor| < 1e-10: the outputs are copies of the inputs
+ * (:65-67).  out_planes (required): three planes of that size, written by ONE kernel, bit for bit ab_arcsinh_stretch_with_stats x 3
+ * with the global range.  out_min_max (nullable): the range used (0, 0 for the copies); fetching it is the call's one synchronisation
+ * (device outputs and out_min_max NULL: none).  An output may not overlap an input or another output.  Mismatched dims,
+ * rows * cols >= 2^31, a NULL out_planes or exactly one of global_min / global_max -> AB_ERR_INVALID before anything touches the
+ * device. */
+AB_API int ab_arcsinh_stretch_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, const float *global_min, const float *global_max,
+                                  float factor, float gamma, ab_plane_mut *out_planes, float out_min_max[2]);
+/* arcsinh_stretch_composite_cmd (stretch.rs:94-124) from the loaded composite to the PNG encoder's input.  factor is clamped as the
+ * command clamps it (a NaN: see above); gamma is 1.  out_planes (nullable: the command discards them): three planes as above.
+ * out_rgb8 (nullable): preview_rows x preview_cols x 3 bytes with the dims of ab_preview_dims(rows, cols, max_dim), host or device
+ * (out_on_device) at ANY byte address: ab_render_rgb_preview's bytes with stf NULL of the stretched planes, (v.clamp(0, 1) * 255f32)
+ * as u8 (cmd/helpers.rs:243-245), stretched and packed in registers.  Above max_dim without out_planes only the picked pixels are
+ * loaded and stretched after the range pass; with out_planes one kernel writes the planes and the bytes.  At most one
+ * synchronisation, at the end; none with info NULL and device outputs.  Mismatched dims, rows * cols >= 2^31, max_dim < 1, both
+ * outputs NULL, exactly one of global_min / global_max, or an output that overlaps an input or another output -> AB_ERR_INVALID
+ * before anything touches the device. */
+AB_API int ab_arcsinh_stretch_composite(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, double factor, const float *global_min,
+                                        const float *global_max, int64_t max_dim, ab_plane_mut *out_planes, uint8_t *out_rgb8, int32_t out_on_device,
+                                        ab_arcsinh_composite_info *info);
+/* apply_arcsinh_stretch_cmd (stretch.rs:15-43) with render_and_save (cmd/common.rs:209-240) up to the encoders, as one chain with one
+ * synchronisation: the range pass on the plane, the stretch, then ab_auto_stretch_preview's device chain on the stretched plane.
+ * out_plane (required): what write_fits_mono receives (ab_fits_encode_pixels encodes it).  out_u8 (nullable): rows x cols bytes, host
+ * or device (out_on_device), any address -- render_and_save has no max_dim.  info (nullable). */
+AB_API int ab_arcsinh_stretch_view(ab_ctx *ctx, const ab_plane *img, double factor, ab_plane_mut *out_plane, uint8_t *out_u8, int32_t out_on_device,
+                                   ab_arcsinh_view_info *info);
+/* masked_stretch_composite_cmd (stretch.rs:135-221) from the loaded composite to the PNG encoder's input: a composition.
+ * shared_mask != 0 takes ab_masked_stretch_rgb_shared's route, otherwise ab_masked_stretch's three times; the stretched planes go to
+ * out_planes (nullable) or into a workspace of the context, and the packer above turns them into out_rgb8 (nullable; not both).
+ * Planes, results and bytes are bit for bit those calls followed by ab_render_rgb_preview with stf NULL.  The AB_ERR_INVALID cases
+ * of ab_arcsinh_stretch_composite, and a NULL cfg. */
+AB_API int ab_masked_stretch_composite(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, const ab_masked_stretch_config *cfg,
+                                       int32_t shared_mask, int64_t max_dim, ab_plane_mut *out_planes, uint8_t *out_rgb8, int32_t out_on_device,
+                                       ab_masked_stretch_composite_info *info);
+
 /* ---- bench support: a plain float4 device copy, the measured HBM ceiling ---- */
 AB_API int ab_bench_copy(ab_ctx *ctx, const float *src_dev, float *dst_dev, size_t n_floats);
 
