@@ -15,6 +15,7 @@ from .core import COLOR_STATS_EXACT_OR_FULL, COLOR_STATS_KNOWN_RANGE, AutoWb, Bl
 from .core import color_step_plan, compute_auto_wb  # noqa: F401
 from .core import MASK_PER_CHANNEL, MASK_SHARED_LUMINANCE, ArcsinhCompositeResult, ArcsinhViewResult, MaskedStretchCompositeResult  # noqa: F401
 from .core import arcsinh_rgb_range  # noqa: F401
+from .core import BackgroundStepResult  # noqa: F401
 from .core import matches_from_votes, triangle_votes_host  # noqa: F401
 from .core import SynthFrames, synth_chacha_block, synth_config, synth_noise_params, synth_psf_type, synth_rng_f64, synth_star_field  # noqa: F401
 

@@ -346,6 +346,11 @@ class MaskedStretchCompositeInfoC(C.Structure):  # ab_masked_stretch_composite_i
                 ("channels", MaskedStretchResultC * 3), ("stars_masked", C.c_uint64), ("mask_coverage", C.c_double), ("mask_mode", C.c_int32)]
 
 
+class BackgroundStepInfoC(C.Structure):  # ab_background_step_info: extract_background_cmd's JSON and cache entry (cmd/processing/background.rs:73-92)
+    _fields_ = [("bg", BackgroundInfoC), ("rows", C.c_uint64), ("cols", C.c_uint64), ("preview_rows", C.c_uint64), ("preview_cols", C.c_uint64),
+                ("corrected_stats", ImageStatsC), ("model_stats", ImageStatsC), ("corrected_stf", StfParamsC), ("model_stf", StfParamsC)]
+
+
 class DrizzleResultC(C.Structure):  # DrizzleResult's scalars (drizzle.rs:335-344)
     _fields_ = [("frame_count", C.c_size_t), ("output_scale", C.c_double), ("in_rows", C.c_int64), ("in_cols", C.c_int64),
                 ("out_rows", C.c_int64), ("out_cols", C.c_int64), ("rejected_pixels", C.c_uint64)]
@@ -664,6 +669,8 @@ def lib() -> C.CDLL:
     L.ab_arcsinh_stretch_composite.argtypes = [vp, pp, pp, pp, C.c_double, f32p, f32p, C.c_int64, pmp, vp, C.c_int32, C.POINTER(ArcsinhCompositeInfoC)]
     L.ab_arcsinh_stretch_view.argtypes = [vp, pp, C.c_double, pmp, vp, C.c_int32, C.POINTER(ArcsinhViewInfoC)]
     L.ab_masked_stretch_composite.argtypes = [vp, pp, pp, pp, msc, C.c_int32, C.c_int64, pmp, vp, C.c_int32, C.POINTER(MaskedStretchCompositeInfoC)]
+    L.ab_auto_stretch_preview_sampled.argtypes = [vp, pp, C.POINTER(AutoStfConfigC), C.c_int64, vp, C.c_int32, isp, C.POINTER(StfParamsC)]
+    L.ab_background_step.argtypes = [vp, pp, C.POINTER(BackgroundConfigC), C.c_int64, pmp, pmp, vp, vp, C.c_int32, C.POINTER(BackgroundStepInfoC)]
     for name in declared_symbols():
         fn = getattr(L, name)  # AttributeError here = header / library drift
         if fn.restype is C.c_int and name not in ("ab_last_error", "ab_version", "ab_ctx_get_stream", "ab_comm_collectives_issued"):

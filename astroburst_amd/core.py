@@ -438,6 +438,25 @@ class MaskedStretchCompositeResult:  # masked_stretch_composite_cmd's (stretch.r
     mask_mode: object      # "shared_luminance" | "per_channel"
 
 
+@dataclass
+class BackgroundStepResult:  # extract_background_cmd's (cmd/processing/background.rs:17-94) outputs up to the PNG encoders
+    corrected: object        # the corrected plane: what the command caches under wizard_bg_key
+    model: object            # the model, or None (want_model=False)
+    corrected_u8: object     # uint8 (preview_rows, preview_cols), or None
+    model_u8: object
+    rows: int
+    cols: int
+    preview_rows: int
+    preview_cols: int
+    sample_count: object     # int, or None (fetch=False)
+    rms_residual: object
+    coeffs: object           # the fitted coefficients (21 f64)
+    corrected_stats: object  # ImageStats the command caches with the plane, or None
+    model_stats: object
+    corrected_stf: object    # StfParams, or None
+    model_stf: object
+
+
 def arcsinh_rgb_range(sr, sg, sb) -> tuple:
     """(global_min, global_max) of arcsinh_stretch_rgb_with_stats (core/imaging/stretch.rs:72-78): the f32 fold of three channels'
     ImageStats.  Host-only."""
@@ -1884,6 +1903,66 @@ class Context:
         self._check(self._L.ab_extract_background(self._h, C.byref(pi), C.byref(cfg), pm, C.byref(pc), C.byref(info)))
         return BackgroundResult(model, corrected, int(info.sample_count), float(info.rms_residual),
                                 np.array(info.coeffs[:], dtype=np.float64))
+
+    # ---- the compose wizard's background step: cmd/processing/background.rs, cmd/common.rs:18-22, :152-193 ----------
+    def auto_stretch_preview_sampled(self, image, max_dim=4096, target_bg=0.25, shadow_k=-2.8, fetch=True, out=None):
+        """auto_stretch_preview (cmd/common.rs:18-22) followed by save_preview_png's pick (:152-193) as one chain: only the picked
+        pixels are stretched.  -> (uint8 (preview_rows, preview_cols), ImageStats | None, StfParams | None); numpy in, numpy out,
+        CUDA tensor in, CUDA tensor out (or `out`, contiguous uint8 of that size).  fetch=False with a device output leaves the
+        call asynchronous."""
+        keep = []
+        pi = self._plane(image, keep)
+        ph, pw = self.preview_dims(int(pi.rows), int(pi.cols), int(max_dim)) if max_dim >= 1 else (1, 1)
+        u8, ptr, dev = self._bytes_out(image, (ph, pw), out)
+        cfg = AutoStfConfigC(target_bg, shadow_k)
+        s, p = ImageStatsC(), StfParamsC()
+        self._check(self._L.ab_auto_stretch_preview_sampled(self._h, C.byref(pi), C.byref(cfg), int(max_dim), ptr, dev, C.byref(s) if fetch else None,
+                                                            C.byref(p) if fetch else None))
+        if not fetch:
+            return u8, None, None
+        return u8, self._stats_out(s), StfParams(p.shadow, p.midtone, p.highlight)
+
+    @staticmethod
+    def background_step_clamp_config(grid_size: int, poly_degree: int, iterations: int):
+        """the clamps extract_background_cmd applies before it builds its BackgroundConfig (background.rs:44-47, types/constants.rs:11-16):
+        grid_size 3 ..= 32, poly_degree 1 ..= 5, iterations 1 ..= 10.  background_step takes its arguments as extract_background does."""
+        return min(max(int(grid_size), 3), 32), min(max(int(poly_degree), 1), 5), min(max(int(iterations), 1), 10)
+
+    def background_step(self, image, grid_size=8, poly_degree=3, sigma_clip=2.5, iterations=3, mode="subtract", max_dim=4096, want_model=True,
+                        want_corrected_u8=True, want_model_u8=True, fetch=True, out_corrected=None, out_model=None, out_corrected_u8=None,
+                        out_model_u8=None) -> BackgroundStepResult:
+        """extract_background_cmd (cmd/processing/background.rs:17-94) from its loaded plane to the two PNG encoders' inputs and the
+        JSON, as one chain: extract_background, each plane's statistics once (the model's with the range its own kernel reduced),
+        both previews' picked pixels in one launch, one final synchronisation.  Numpy means host planes and host bytes, CUDA tensors
+        device planes and device bytes.  Raises AstroBurstError with the reference's message like extract_background."""
+        keep = []
+        pi = self._plane(image, keep)
+        rows, cols = int(pi.rows), int(pi.cols)
+        if out_corrected is None:
+            out_corrected = self._new_like(image, rows, cols)
+        pc = self._out_plane(out_corrected, keep, out_corrected.shape[0], out_corrected.shape[1])   # (its own dims: the library refuses a mismatch)
+        pm = None
+        if want_model or out_model is not None:
+            if out_model is None:
+                out_model = self._new_like(image, rows, cols)
+            pm = C.byref(self._out_plane(out_model, keep, out_model.shape[0], out_model.shape[1]))
+        ph, pw = self.preview_dims(rows, cols, int(max_dim)) if max_dim >= 1 else (1, 1)
+        cu8, cptr, dev = self._bytes_out(image, (ph, pw), out_corrected_u8) if (want_corrected_u8 or out_corrected_u8 is not None) else (None, None, None)
+        mu8, mptr, mdev = self._bytes_out(image, (ph, pw), out_model_u8) if (want_model_u8 or out_model_u8 is not None) else (None, None, None)
+        if dev is not None and mdev is not None and dev != mdev:
+            raise AstroBurstError(_lib.AB_ERR_INVALID, "the two previews' outputs are both host or both device")
+        dev = dev if dev is not None else (mdev if mdev is not None else int(_is_torch(image) and image.is_cuda))
+        cfg = _lib.BackgroundConfigC(grid_size, poly_degree, sigma_clip, iterations,
+                                     {"subtract": 0, "divide": 1}[mode] if isinstance(mode, str) else int(mode))
+        info = _lib.BackgroundStepInfoC()
+        self._check(self._L.ab_background_step(self._h, C.byref(pi), C.byref(cfg), int(max_dim), C.byref(pc), pm, cptr, mptr, dev,
+                                               C.byref(info) if fetch else None))
+        if not fetch:
+            return BackgroundStepResult(out_corrected, out_model, cu8, mu8, rows, cols, ph, pw, None, None, None, None, None, None, None)
+        stf = lambda p: StfParams(p.shadow, p.midtone, p.highlight)  # noqa: E731
+        return BackgroundStepResult(out_corrected, out_model, cu8, mu8, int(info.rows), int(info.cols), int(info.preview_rows), int(info.preview_cols),
+                                    int(info.bg.sample_count), float(info.bg.rms_residual), np.array(info.bg.coeffs[:], dtype=np.float64),
+                                    self._stats_out(info.corrected_stats), self._stats_out(info.model_stats), stf(info.corrected_stf), stf(info.model_stf))
 
     # ---- a17 RGB composition -------------------------------------------------------------------------
     def resample_image(self, image, target_rows: int, target_cols: int, out=None):

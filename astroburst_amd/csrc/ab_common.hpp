@@ -67,6 +67,7 @@ enum {
     AB_WS_VIEW,               // the open-file view: 65 536 source bins, display bins bound for the host, three channels' results (view.hip)
     AB_WS_WIZARD,             // the blend / colour steps: three channels' statistics, the linked STF and transforms, resampled channels (wizard_color.hip)
     AB_WS_STRETCH,            // the stretch steps: the range words and what info reports, host-bound bytes, planes nobody asked for (wizard_stretch.hip)
+    AB_WS_BACKGROUND,         // the background step: the model's range words, the corrected plane's statistics, host-bound bytes, a model nobody asked for (wizard_background.hip)
     AB_WS_SLOTS
 };
 
@@ -352,6 +353,19 @@ int ab_stats_device(ab_ctx *ctx, const float *data, int64_t n, int use_known, do
 int ab_stats_enqueue(ab_ctx *ctx, ab_comm *comm, const float *data, int64_t n, int64_t n_total, int use_known, double known_min,
                      double known_max, const ab_auto_stf_config *stf_cfg, const ab_image_stats **result_dev, const void **tx_dev,
                      const ab_stf_params **stf_dev);
+// background.hip: what extract_background (background.rs:55-116) does before it evaluates the surface, shared with wizard_background.hip.
+// ab_background_check: the configuration and size checks, host only (nothing touches the device).  ab_background_sample_fit: ticks
+// "sampling background" (1 / 4), the global median / MAD, the grid-cell medians, auto_sample_grid's rejection rounds, ticks "fitting
+// polynomial surface" (2 / 4), the least-squares fit and compute_rms_residual.  fit->sample_count is set even when the samples do not
+// suffice (the reference's error).  The caller owns the staged plane and whatever the stream still holds on an error.
+struct ab_background_fit {
+    double coeffs[21] = {};
+    int degree = 0;
+    size_t sample_count = 0;
+    double rms_residual = 0.0;
+};
+int ab_background_check(ab_ctx *ctx, int64_t rows, int64_t cols, const ab_background_config *cfg);
+int ab_background_sample_fit(ab_ctx *ctx, const float *img_dev, int64_t rows, int64_t cols, const ab_background_config *cfg, ab_background_fit *fit);
 // apply_stf -> u8 with the transform (StfTx) read from device memory
 int ab_stf_u8_device_tx(ab_ctx *ctx, const float *in, int64_t n, const void *tx_dev, uint8_t *out);
 // detect_stars of G frames of one size in lockstep (one launch per step for all of them); bg[f] = {median, sigma} of frame f's background

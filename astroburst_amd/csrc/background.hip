@@ -15,6 +15,7 @@
 // Host work: the <= 32 x 32 samples' kappa-sigma rejection and the <= 21-term least-squares fit
 // (Gaussian elimination with partial pivoting, f64) -- scalar maths the reference also runs serially.
 #include "ab_common.hpp"
+#include "background_device.hpp"
 #include "block_select.hpp"
 
 #include <algorithm>
@@ -22,8 +23,7 @@
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kMaxPolyTerms = 21;
+constexpr int kBlock = kPolyBlock;
 constexpr float kMadToSigmaF32 = (float)1.4826;
 
 // ---- grid-cell medians (background.rs:151-190) ---------------------------------------------------------
@@ -58,76 +58,25 @@ __global__ __launch_bounds__(absel::kBlock) void cell_median_kernel(const float 
     }
 }
 
-// ---- surface evaluation + correction (background.rs:307-383) ----------------------------------------------
-struct PolyArgs {
-    double coeffs[kMaxPolyTerms];
-    int degree;
-    int rows, cols;
-    double row_scale, col_scale;
-};
-
-// evaluate_polynomial_surface (:307-341), one row per blockIdx.y, kPolyPx pixels of it per thread.  The reference's term is
-// (coeffs[idx] * y_pows[yp]) * x_pows[xp]: the first product is the same for every pixel of a row, so a thread forms the row's
-// DEG-dependent table once and spends one multiply and one add per term and pixel -- the same operations in the same order, bit
-// for bit.  DEG is a template parameter: with a run-time degree the power tables were indexed dynamically and lived in scratch
-// memory (459 us for 8192^2, 0.58 TB/s of model written; round 4).  `x / col_scale` stays an IEEE division unless col_scale is a
-// power of two, where multiplying by its reciprocal is the same exact scaling.
-constexpr int kPolyPx = 4;
+// ---- surface evaluation + correction (background.rs:307-383): the per-pixel bodies are background_device.hpp's ---------------------
+// evaluate_polynomial_surface (:307-341), one row per blockIdx.y, kPolyPx pixels of it per thread
 template <int DEG>
 __global__ __launch_bounds__(kBlock) void poly_model_kernel(const PolyArgs p, float *__restrict__ model, int pow2_cols, double inv_cols) {
-    constexpr int T = (DEG + 1) * (DEG + 2) / 2;
     const int y = blockIdx.y;
-    const double ny = (double)y / p.row_scale - 0.5;
-    double y_pows[DEG + 1];
-    y_pows[0] = 1.0;
-#pragma unroll
-    for (int i = 1; i <= DEG; ++i) y_pows[i] = y_pows[i - 1] * ny;
-    double cy[T];  // coeffs[idx] * y_pows[yp] in eval_poly_inline's term order (:230-249)
-    {
-        int idx = 0;
-#pragma unroll
-        for (int total = 0; total <= DEG; ++total)
-#pragma unroll
-            for (int yp = total; yp >= 0; --yp) {
-                cy[idx] = p.coeffs[idx] * y_pows[yp];
-                ++idx;
-            }
-    }
+    double cy[(DEG + 1) * (DEG + 2) / 2];
+    poly_row_table<DEG>(p, y, cy);
 #pragma unroll
     for (int u = 0; u < kPolyPx; ++u) {
         const int x = (blockIdx.x * kPolyPx + u) * kBlock + threadIdx.x;
         if (x >= p.cols) continue;
-        const double nx = (pow2_cols ? (double)x * inv_cols : (double)x / p.col_scale) - 0.5;
-        double x_pows[DEG + 1];
-        x_pows[0] = 1.0;
-#pragma unroll
-        for (int i = 1; i <= DEG; ++i) x_pows[i] = x_pows[i - 1] * nx;
-        double val = 0.0;
-        int idx = 0;
-#pragma unroll
-        for (int total = 0; total <= DEG; ++total)
-#pragma unroll
-            for (int yp = total; yp >= 0; --yp) {
-                val += cy[idx] * x_pows[total - yp];
-                ++idx;
-            }
-        model[(size_t)y * p.cols + x] = (float)val;
+        model[(size_t)y * p.cols + x] = poly_px<DEG>(p, cy, x, pow2_cols, inv_cols);
     }
 }
 
 __global__ __launch_bounds__(kBlock) void bg_apply_kernel(const float *__restrict__ img, const float *__restrict__ model, int64_t n,
                                                           int mode, float model_median, float *__restrict__ out) {
     const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-        const float v = img[i], bg = model[i];
-        float r;
-        if (mode == 0) {
-            r = v - bg + model_median;                                    // :367-369
-        } else {
-            r = fabsf(bg) > 1e-10f ? (v / bg) * model_median : v;        // :370-376
-        }
-        out[i] = r;
-    }
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) out[i] = bg_apply_px(img[i], model[i], mode, model_median);
 }
 
 // ---- host scalar maths ----------------------------------------------------------------------------------------
@@ -199,51 +148,32 @@ struct Sample {
 
 }  // namespace
 
-extern "C" int ab_extract_background(ab_ctx *ctx, const ab_plane *img, const ab_background_config *cfg, ab_plane_mut *out_model,
-                                     ab_plane_mut *out_corrected, ab_background_info *info) try {
-    if (!ctx) return AB_ERR_INVALID;
-    AB_CHECK(ctx, img && cfg && out_corrected, "null argument");
-    const int64_t rows = img->rows, cols = img->cols, npix = rows * cols;
-    AB_CHECK(ctx, out_corrected->rows == rows && out_corrected->cols == cols && (!out_model || (out_model->rows == rows && out_model->cols == cols)),
-             "model / corrected planes must have the image's dims");
+// the configuration and size checks of extract_background, before anything touches the device (ab_common.hpp)
+int ab_background_check(ab_ctx *ctx, int64_t rows, int64_t cols, const ab_background_config *cfg) {
+    const int64_t npix = rows * cols;
     const int grid = (int)cfg->grid_size, degree = (int)cfg->poly_degree;
     AB_CHECK(ctx, grid >= 1 && grid <= 64 && degree >= 0 && degree <= 5, "grid_size must be 1..64 and poly_degree 0..5 (<= 21 terms)");
     AB_CHECK(ctx, rows <= 65535 && npix < (int64_t(1) << 31), "image too large for this build");
     const int cell_h = (int)(rows / grid), cell_w = (int)(cols / grid);
     if (cell_h < 4 || cell_w < 4) return ab_set_error(ctx, AB_ERR_INVALID, "Image too small for grid_size=%d", grid);  // :127-129
     AB_CHECK(ctx, (int64_t)cell_h * cell_w <= ((int64_t)1 << 26), "grid cells larger than 2^26 px are not supported");  // u32 ranks, one block per cell
-    const int margin_h = cell_h / 4, margin_w = cell_w / 4, inner_h = cell_h - 2 * margin_h, inner_w = cell_w - 2 * margin_w;
-    AB_HIP(ctx, hipSetDevice(ctx->device));
+    return AB_OK;
+}
 
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    float *model = nullptr;
+// auto_sample_grid (:118-210), fit_polynomial_surface (:251-290) and compute_rms_residual (:385-415) of a device plane that passed
+// ab_background_check (ab_common.hpp)
+int ab_background_sample_fit(ab_ctx *ctx, const float *img_dev, int64_t rows, int64_t cols, const ab_background_config *cfg, ab_background_fit *fit) {
+    const int64_t npix = rows * cols;
+    const int grid = (int)cfg->grid_size, degree = (int)cfg->poly_degree;
+    const int cell_h = (int)(rows / grid), cell_w = (int)(cols / grid);
+    const int margin_h = cell_h / 4, margin_w = cell_w / 4, inner_h = cell_h - 2 * margin_h, inner_w = cell_w - 2 * margin_w;
     CellOut *dcells = nullptr;
-    StagedOut so_corr, so_model;
-    bool corr_open = false, model_open = false;
-    int rc = AB_OK;
-    auto cleanup = [&]() {
-        if (corr_open) ab_stage_out_abort(ctx, &so_corr);
-        if (model_open) ab_stage_out_abort(ctx, &so_model);
-        (void)hipStreamSynchronize(ctx->stream);
-        ab_stage_release(ctx, &in);
-    };
-#define BG_TRY(expr)          \
-    do {                      \
-        rc = (expr);          \
-        if (rc != AB_OK) {    \
-            cleanup();        \
-            return rc;        \
-        }                     \
-    } while (0)
-#define BG_HIP(call)                                                                               \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            rc = ab_set_error(ctx, AB_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_));     \
-            cleanup();                                                                             \
-            return rc;                                                                             \
-        }                                                                                          \
+    fit->degree = degree;
+#define BG_TRY(expr) AB_TRY(expr)
+#define BG_HIP(call)                                                                                         \
+    do {                                                                                                     \
+        hipError_t e_ = (call);                                                                              \
+        if (e_ != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
     } while (0)
 
     BG_TRY(ab_workspace(ctx, AB_WS_SCOPE1, (size_t)grid * grid * sizeof(CellOut), (void **)&dcells));  // (kept between calls: ab_common.hpp)
@@ -252,7 +182,7 @@ extern "C" int ab_extract_background(ab_ctx *ctx, const ab_plane *img, const ab_
     // global median / MAD over finite, > 0 pixels (:135-146)
     float global_median, global_mad;
     ab_plane_sel sel;
-    sel.data = in.dptr;
+    sel.data = img_dev;
     sel.n = npix;
     BG_TRY(ab_plane_median_f32(ctx, sel, &global_median, nullptr));
     sel.use_dev = 1;
@@ -261,7 +191,7 @@ extern "C" int ab_extract_background(ab_ctx *ctx, const ab_plane *img, const ab_
     const float sigma = global_mad * kMadToSigmaF32;
 
     // grid-cell medians (:150-190)
-    hipLaunchKernelGGL(cell_median_kernel, dim3(grid * grid), dim3(absel::kBlock), 0, ctx->stream, in.dptr, in.cols, grid, cell_h,
+    hipLaunchKernelGGL(cell_median_kernel, dim3(grid * grid), dim3(absel::kBlock), 0, ctx->stream, img_dev, cols, grid, cell_h,
                        cell_w, margin_h, margin_w, inner_h, inner_w, dcells);
     BG_HIP(hipGetLastError());
     std::vector<CellOut> cells((size_t)grid * grid);
@@ -293,26 +223,17 @@ extern "C" int ab_extract_background(ab_ctx *ctx, const ab_plane *img, const ab_
         samples.erase(std::remove_if(samples.begin(), samples.end(), [&](const Sample &s) { return !(s.value >= lo && s.value <= hi); }),
                       samples.end());
     }
-    if (info) info->sample_count = samples.size();
-    if (samples.size() < min_samples) {  // :71-77
-        rc = ab_set_error(ctx, AB_ERR_INVALID, "Not enough background samples (%zu) for polynomial degree %d", samples.size(), degree);
-        cleanup();
-        return rc;
-    }
+    fit->sample_count = samples.size();
+    if (samples.size() < min_samples)  // :71-77
+        return ab_set_error(ctx, AB_ERR_INVALID, "Not enough background samples (%zu) for polynomial degree %d", samples.size(), degree);
 
     BG_TRY(ab_progress(ctx, "fitting polynomial surface", 2, 4));  // background.rs:79-84 (cancel checked, then tick)
     // fit_polynomial_surface (:251-290)
-    PolyArgs pa;
-    memset(&pa, 0, sizeof pa);
-    pa.degree = degree;
-    pa.rows = (int)rows;
-    pa.cols = (int)cols;
-    pa.row_scale = (double)rows;
-    pa.col_scale = (double)cols;
+    const double row_scale = (double)rows, col_scale = (double)cols;
     std::vector<double> ata(n_terms * n_terms, 0.0), atb(n_terms, 0.0);
     double basis[kMaxPolyTerms];
     for (const Sample &s : samples) {
-        const double ny = (double)s.y / pa.row_scale - 0.5, nx = (double)s.x / pa.col_scale - 0.5, val = (double)s.value;
+        const double ny = (double)s.y / row_scale - 0.5, nx = (double)s.x / col_scale - 0.5, val = (double)s.value;
         const int cnt = poly_basis_into(ny, nx, degree, basis);
         for (int i = 0; i < cnt; ++i) {
             atb[i] += basis[i] * val;
@@ -320,12 +241,88 @@ extern "C" int ab_extract_background(ab_ctx *ctx, const ab_plane *img, const ab_
         }
     }
     for (size_t i = 0; i < n_terms; ++i) ata[i * n_terms + i] += 1e-8;
-    if (!solve_linear_system(ata, atb, (int)n_terms)) {
-        rc = ab_set_error(ctx, AB_ERR_INVALID, "Failed to solve polynomial fit: Singular matrix in polynomial fit");
-        cleanup();
-        return rc;
+    if (!solve_linear_system(ata, atb, (int)n_terms))
+        return ab_set_error(ctx, AB_ERR_INVALID, "Failed to solve polynomial fit: Singular matrix in polynomial fit");
+    for (size_t i = 0; i < n_terms; ++i) fit->coeffs[i] = atb[i];
+
+    // compute_rms_residual (:385-415)
+    double sum_sq = 0.0;
+    for (const Sample &s : samples) {
+        double yp[7] = {1.0, 0, 0, 0, 0, 0, 0}, xp[7] = {1.0, 0, 0, 0, 0, 0, 0};
+        const double ny = (double)s.y / row_scale - 0.5, nx = (double)s.x / col_scale - 0.5;
+        for (int i = 1; i <= std::min(degree, 6); ++i) {
+            yp[i] = yp[i - 1] * ny;
+            xp[i] = xp[i - 1] * nx;
+        }
+        double val = 0.0;
+        int idx = 0;
+        for (int total = 0; total <= degree; ++total)
+            for (int ypow = total; ypow >= 0; --ypow) {
+                val += fit->coeffs[idx] * yp[ypow] * xp[total - ypow];
+                ++idx;
+            }
+        const double diff = (double)s.value - val;
+        sum_sq += diff * diff;
     }
-    for (size_t i = 0; i < n_terms; ++i) pa.coeffs[i] = atb[i];
+    fit->rms_residual = std::sqrt(sum_sq / (double)samples.size());
+    return AB_OK;
+#undef BG_TRY
+#undef BG_HIP
+}
+
+extern "C" int ab_extract_background(ab_ctx *ctx, const ab_plane *img, const ab_background_config *cfg, ab_plane_mut *out_model,
+                                     ab_plane_mut *out_corrected, ab_background_info *info) try {
+    if (!ctx) return AB_ERR_INVALID;
+    AB_CHECK(ctx, img && cfg && out_corrected, "null argument");
+    const int64_t rows = img->rows, cols = img->cols, npix = rows * cols;
+    AB_CHECK(ctx, out_corrected->rows == rows && out_corrected->cols == cols && (!out_model || (out_model->rows == rows && out_model->cols == cols)),
+             "model / corrected planes must have the image's dims");
+    AB_TRY(ab_background_check(ctx, rows, cols, cfg));
+    const int degree = (int)cfg->poly_degree;
+    AB_HIP(ctx, hipSetDevice(ctx->device));
+
+    StagedPlane in;
+    AB_TRY(ab_stage_in(ctx, img, &in));
+    float *model = nullptr;
+    StagedOut so_corr, so_model;
+    bool corr_open = false, model_open = false;
+    int rc = AB_OK;
+    auto cleanup = [&]() {
+        if (corr_open) ab_stage_out_abort(ctx, &so_corr);
+        if (model_open) ab_stage_out_abort(ctx, &so_model);
+        (void)hipStreamSynchronize(ctx->stream);
+        ab_stage_release(ctx, &in);
+    };
+#define BG_TRY(expr)          \
+    do {                      \
+        rc = (expr);          \
+        if (rc != AB_OK) {    \
+            cleanup();        \
+            return rc;        \
+        }                     \
+    } while (0)
+#define BG_HIP(call)                                                                               \
+    do {                                                                                           \
+        hipError_t e_ = (call);                                                                    \
+        if (e_ != hipSuccess) {                                                                    \
+            rc = ab_set_error(ctx, AB_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_));     \
+            cleanup();                                                                             \
+            return rc;                                                                             \
+        }                                                                                          \
+    } while (0)
+
+    ab_background_fit fit;
+    rc = ab_background_sample_fit(ctx, in.dptr, rows, cols, cfg, &fit);
+    if (info) info->sample_count = fit.sample_count;
+    BG_TRY(rc);
+    PolyArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.degree = degree;
+    pa.rows = (int)rows;
+    pa.cols = (int)cols;
+    pa.row_scale = (double)rows;
+    pa.col_scale = (double)cols;
+    memcpy(pa.coeffs, fit.coeffs, sizeof pa.coeffs);
     if (info) memcpy(info->coeffs, pa.coeffs, sizeof pa.coeffs);
 
     BG_TRY(ab_progress(ctx, "generating model", 3, 4));  // background.rs:88-93
@@ -369,28 +366,7 @@ extern "C" int ab_extract_background(ab_ctx *ctx, const ab_plane *img, const ab_
         rc = ab_stage_out_finish(ctx, &so_model);
         model_open = false;
     }
-    // compute_rms_residual (:385-415)
-    if (rc == AB_OK && info) {
-        double sum_sq = 0.0;
-        for (const Sample &s : samples) {
-            double yp[7] = {1.0, 0, 0, 0, 0, 0, 0}, xp[7] = {1.0, 0, 0, 0, 0, 0, 0};
-            const double ny = (double)s.y / pa.row_scale - 0.5, nx = (double)s.x / pa.col_scale - 0.5;
-            for (int i = 1; i <= std::min(degree, 6); ++i) {
-                yp[i] = yp[i - 1] * ny;
-                xp[i] = xp[i - 1] * nx;
-            }
-            double val = 0.0;
-            int idx = 0;
-            for (int total = 0; total <= degree; ++total)
-                for (int ypow = total; ypow >= 0; --ypow) {
-                    val += pa.coeffs[idx] * yp[ypow] * xp[total - ypow];
-                    ++idx;
-                }
-            const double diff = (double)s.value - val;
-            sum_sq += diff * diff;
-        }
-        info->rms_residual = std::sqrt(sum_sq / (double)samples.size());
-    }
+    if (rc == AB_OK && info) info->rms_residual = fit.rms_residual;
     cleanup();
     return rc;
 #undef BG_TRY

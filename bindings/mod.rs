@@ -2051,6 +2051,80 @@ pub fn masked_stretch_composite(hip: &Hip, r: &impl PlaneSrc, g: &impl PlaneSrc,
     })
 }
 
+// ---- the compose wizard's background step: cmd/processing/background.rs:17-94, cmd/common.rs:18-22, :152-193 ------------------------------------------------
+/// what auto_stretch_preview + save_preview_png hand to save_stf_png (cmd/common.rs:190-193), with the statistics behind the stretch
+pub struct MonoPreview {
+    pub pixels: Vec<u8>,
+    pub preview_dims: (usize, usize),
+    pub stats: ImageStats,
+    pub stf: StfParams,
+}
+/// what extract_background_cmd encodes, caches and reports (background.rs:51-92)
+pub struct BackgroundStep {
+    pub corrected_pixels: Vec<u8>,
+    pub model_pixels: Vec<u8>,
+    pub dims: (usize, usize),
+    pub preview_dims: (usize, usize),
+    pub sample_count: usize,
+    pub rms_residual: f64,
+    pub corrected_stats: ImageStats,
+    pub model_stats: ImageStats,
+    pub elapsed_ms: u64,
+}
+/// auto_stretch_preview (cmd/common.rs:18-22) followed by save_preview_png's pick (:190-193): only the picked pixels are stretched
+pub fn auto_stretch_preview_sampled(hip: &Hip, image: &impl PlaneSrc, max_dim: usize) -> Result<MonoPreview> {
+    let (rows, cols) = image.dims();
+    let (ph, pw) = preview_dims(rows, cols, max_dim);
+    let mut pixels = vec![0u8; ph * pw];
+    let mut stats: sys::ab_image_stats = unsafe { std::mem::zeroed() };
+    let mut stf: sys::ab_stf_params = unsafe { std::mem::zeroed() };
+    hip.check(unsafe { sys::ab_auto_stretch_preview_sampled(hip.ctx, &image.ab(), std::ptr::null(), max_dim as i64, pixels.as_mut_ptr(), 0, &mut stats, &mut stf) })?;
+    Ok(MonoPreview { pixels, preview_dims: (ph, pw), stats: stats_from_sys(&stats), stf: stf_from_sys(&stf) })
+}
+/// the clamps extract_background_cmd applies before it builds its BackgroundConfig (background.rs:44-47, types/constants.rs:11-16)
+pub fn background_step_clamp_config(grid_size: usize, poly_degree: usize, iterations: usize) -> (usize, usize, usize) {
+    (grid_size.clamp(3, 32), poly_degree.clamp(1, 5), iterations.clamp(1, 10))
+}
+/// extract_background_cmd (background.rs:17-94) from the loaded plane to the two encoders' inputs: extract_background, each plane's statistics once, both
+/// previews in one launch; the model stays in a workspace of the context.  `corrected` (host array or DevicePlane of the image's dims) receives the plane the
+/// command caches with corrected_stats.  config is taken as extract_background takes it (background_step_clamp_config)
+pub fn background_step_into(hip: &Hip, image: &impl PlaneSrc, config: &BackgroundConfig, max_dim: usize, corrected: &mut impl PlaneDst,
+                            progress: Option<&ProgressHandle>) -> Result<BackgroundStep> {
+    let start = std::time::Instant::now();
+    let (rows, cols) = image.dims();
+    let (ph, pw) = preview_dims(rows, cols, max_dim);
+    let (mut corrected_pixels, mut model_pixels) = (vec![0u8; ph * pw], vec![0u8; ph * pw]);
+    let cfg = sys::ab_background_config { grid_size: config.grid_size, poly_degree: config.poly_degree, sigma_clip: config.sigma_clip, iterations: config.iterations, mode: config.mode as i32 };
+    let mut info: sys::ab_background_step_info = unsafe { std::mem::zeroed() };
+    let mut pc = corrected.ab_mut();
+    hip.with_progress(progress, || {
+        hip.check(unsafe {
+            sys::ab_background_step(hip.ctx, &image.ab(), &cfg, max_dim as i64, &mut pc, std::ptr::null_mut(), corrected_pixels.as_mut_ptr(), model_pixels.as_mut_ptr(), 0, &mut info)
+        })
+    })?;
+    if let Some(p) = progress {
+        p.emit_complete(); // background.rs:105-107
+    }
+    Ok(BackgroundStep {
+        corrected_pixels,
+        model_pixels,
+        dims: (info.rows as usize, info.cols as usize),
+        preview_dims: (info.preview_rows as usize, info.preview_cols as usize),
+        sample_count: info.bg.sample_count,
+        rms_residual: info.bg.rms_residual,
+        corrected_stats: stats_from_sys(&info.corrected_stats),
+        model_stats: stats_from_sys(&info.model_stats),
+        elapsed_ms: start.elapsed().as_millis() as u64,
+    })
+}
+/// the same with the corrected plane on the host
+pub fn background_step(hip: &Hip, image: &impl PlaneSrc, config: &BackgroundConfig, max_dim: usize, progress: Option<&ProgressHandle>) -> Result<(Array2<f32>, BackgroundStep)> {
+    let (rows, cols) = image.dims();
+    let mut corrected = Array2::<f32>::zeros((rows, cols));
+    let step = background_step_into(hip, image, config, max_dim, &mut corrected, progress)?;
+    Ok((corrected, step))
+}
+
 // ---- a17  core/compose/rgb.rs, white_balance.rs, lrgb.rs, core/imaging/resample.rs ---------------------------------------------------------------------
 /// drop-in for resample_image (resample.rs:25-61)
 pub fn resample_image(hip: &Hip, image: &impl PlaneSrc, target_rows: usize, target_cols: usize) -> Result<Array2<f32>> {

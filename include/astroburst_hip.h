@@ -1501,6 +1501,53 @@ AB_API int ab_masked_stretch_composite(ab_ctx *ctx, const ab_plane *r, const ab_
                                        int32_t shared_mask, int64_t max_dim, ab_plane_mut *out_planes, uint8_t *out_rgb8, int32_t out_on_device,
                                        ab_masked_stretch_composite_info *info);
 
+/* ---- the compose wizard's background step: cmd/processing/background.rs (extract_background_cmd :17-94) and the mono preview of
+ * cmd/common.rs (auto_stretch_preview :18-22 followed by save_preview_png :190-193) ------------------------------------------------------ */
+/* save_preview_png picks downsample_nn::<1>'s pixels from auto_stretch_preview's bytes (cmd/common.rs:152-184): above max_dim every
+ * pixel of the plane is stretched to a byte and all but the picked ones are dropped.  csrc/wizard_background.hip stretches only the
+ * picked pixels.  downsample_nn's dims (dst = ((n as f64) * scale).round().max(1.0), scale = max_dim / max(width, height), :162-164;
+ * both dims kept when both fit, :158-160) are cmd/helpers.rs:285-287's rule, so the preview's dims are ab_preview_dims' for a mono plane
+ * as for a composite; its pick ((d as f64) * ratio).min((n - 1) as f64) as usize with ratio = n as f64 / dst as f64 (:166-176) is
+ * helpers.rs:297-300's too. */
+/* auto_stretch_preview (cmd/common.rs:18-22) followed by save_preview_png's pick (:190-193), as one chain: the statistics chain of
+ * ab_auto_stretch_preview, then ONE kernel that reads the transform from HBM, loads only the picked pixels and writes their apply_stf
+ * bytes (stf.rs:89-102).  img: host or device, any float-aligned address.  cfg NULL = AutoStfConfig::default().  out_u8 (required):
+ * preview_rows x preview_cols bytes with the dims of ab_preview_dims(rows, cols, max_dim), host or device (out_on_device), ANY byte
+ * address: byte for byte ab_auto_stretch_preview's output at the picked pixels.  out_stats / out_stf (nullable): what
+ * ab_auto_stretch_preview returns.  At most one synchronisation, at the end; none with both NULL and a device output.  A NULL img or
+ * out_u8, rows * cols >= 2^31, max_dim < 1 or an output that overlaps the input -> AB_ERR_INVALID before anything touches the device. */
+AB_API int ab_auto_stretch_preview_sampled(ab_ctx *ctx, const ab_plane *img, const ab_auto_stf_config *cfg, int64_t max_dim, uint8_t *out_u8,
+                                           int32_t out_on_device, ab_image_stats *out_stats, ab_stf_params *out_stf);
+typedef struct {
+    ab_background_info bg;                            /* RES_SAMPLE_COUNT, RES_RMS_RESIDUAL (background.rs:88-89) and the fitted coefficients */
+    uint64_t rows, cols, preview_rows, preview_cols;  /* RES_DIMENSIONS = [cols, rows] (:91) */
+    ab_image_stats corrected_stats; /* what the command caches with the plane (:73), which is what the preview computed (:53) */
+    ab_image_stats model_stats;     /* of the model (:54) */
+    ab_stf_params corrected_stf, model_stf; /* auto_stf(stats, default) of each */
+} ab_background_step_info;
+/* extract_background_cmd (background.rs:17-94) from its loaded plane to the two PNG encoders' inputs and the JSON, as one chain.
+ * The command clamps grid_size to 3 ..= 32, poly_degree to 1 ..= 5 and iterations to 1 ..= 10 (:44-47, types/constants.rs:11-16) and
+ * casts sigma_clip to f32; that stays on the caller's side, like ab_crop_config_default's defaults: cfg is taken as
+ * ab_extract_background takes it (grid_size 1 .. 64, poly_degree 0 .. 5).
+ * Sampling and fit are ab_extract_background's.  The surface kernel also reduces the minimum and maximum of the model's valid pixels
+ * (finite, > 1e-7) and counts them; the copy that fetches the model's median carries them, and the model's statistics receive them as
+ * compute_image_stats_with_known_range does (stats.rs:36-38), so above 4 000 000 pixels that chain has no range pass.  A degenerate
+ * range (a constant model, no valid pixel) falls back to the scan inside the statistics; either way the result is bit for bit the
+ * unknown-range chain's.  The corrected plane's statistics are computed ONCE (the command computes them at :53 and again at :73).
+ * One launch writes both previews' bytes, only the picked pixels above max_dim.
+ * out_corrected (required) and out_model (nullable: the model then lives in a workspace of the context): planes of the image's dims,
+ * host or device.  out_corrected_u8 / out_model_u8 (each nullable): preview_rows x preview_cols bytes with the dims of
+ * ab_preview_dims(rows, cols, max_dim), both host or both device (out_on_device), any byte address.  Planes, bytes, sample_count,
+ * coeffs, statistics and STF parameters are bit for bit ab_extract_background followed by ab_auto_stretch_preview of each plane and
+ * the pick.  Synchronisations: the cell medians, the global median and MAD, the model's median, and one at the end for info and the
+ * host outputs; with a device image and device outputs nothing is staged through the host.
+ * Progress ticks, cancel points and error strings are ab_extract_background's.  A NULL img, cfg or out_corrected, mismatched dims,
+ * rows * cols >= 2^31, max_dim < 1 or an output that overlaps the input or another output -> AB_ERR_INVALID before anything touches
+ * the device. */
+AB_API int ab_background_step(ab_ctx *ctx, const ab_plane *img, const ab_background_config *cfg, int64_t max_dim, ab_plane_mut *out_corrected,
+                              ab_plane_mut *out_model, uint8_t *out_corrected_u8, uint8_t *out_model_u8, int32_t out_on_device,
+                              ab_background_step_info *info);
+
 /* ---- bench support: a plain float4 device copy, the measured HBM ceiling ---- */
 AB_API int ab_bench_copy(ab_ctx *ctx, const float *src_dev, float *dst_dev, size_t n_floats);
 
