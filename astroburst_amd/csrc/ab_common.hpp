@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <functional>
@@ -491,6 +492,12 @@ int ab_stack_lists_setup(ab_ctx *ctx, int ws_slot, int64_t waves, int64_t px_wav
 int ab_stack_lists_trace(ab_ctx *ctx, const ab_stack_lists &lists, int64_t total);
 
 static inline int ab_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// the workgroups a persistent launch may have at per_cu per compute unit (a 2-D grid shapes them itself: wizard_background.hip)
+static inline int64_t ab_stream_cap(const ab_ctx *ctx, int per_cu = 8) { return (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * per_cu; }
+// workgroups of a persistent, grid-strided streaming launch: enough for `lanes` lanes, at most per_cu per compute unit, at least one
+static inline int ab_stream_grid(const ab_ctx *ctx, int64_t lanes, int block = 256, int per_cu = 8) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>((lanes + block - 1) / block, ab_stream_cap(ctx, per_cu)));
+}
 
 // AB_TRACE=1: wall-clock stamps of the host-visible stages on stderr (developer aid)
 struct ab_trace {

@@ -25,12 +25,6 @@ constexpr int kBlock = 256;
 constexpr int kMaxBlendChannels = 16;
 constexpr int kMaxBlendWeights = 32;
 
-int stream_grid(ab_ctx *ctx, int64_t n4) {
-    const int64_t want = (n4 + kBlock - 1) / kBlock;
-    const int64_t cap = (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8;
-    return (int)std::max<int64_t>(1, std::min(want, cap));
-}
-
 // ---- SCNR (scnr.rs:36-52): the per-pixel closure is scnr_device.hpp's scnr_px, shared with rgb_export.hip ----
 __global__ __launch_bounds__(kBlock) void scnr_kernel(float *r, float *g, float *b, int64_t n, int method, float amount,
                                                       int preserve, int vec) {
@@ -260,7 +254,7 @@ int ab_blend_device(ab_ctx *ctx, const float *const *ch, size_t n_channels, cons
     a.n_weights = nw;
     a.n = n;
     a.r = r, a.g = g, a.b = b;
-    hipLaunchKernelGGL(blend_kernel, dim3(stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, a);
+    hipLaunchKernelGGL(blend_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "blend: %s", hipGetErrorString(e));
     return AB_OK;
@@ -294,7 +288,7 @@ int ab_apply_scnr_inplace(ab_ctx *ctx, ab_plane_mut *r, ab_plane_mut *g, ab_plan
         }
     }
     const int vec = (((uintptr_t)dr | (uintptr_t)dg | (uintptr_t)db) & 15) == 0;
-    hipLaunchKernelGGL(scnr_kernel, dim3(stream_grid(ctx, vec ? (n >> 2) : n)), dim3(kBlock), 0, ctx->stream, dr, dg, db, n,
+    hipLaunchKernelGGL(scnr_kernel, dim3(ab_stream_grid(ctx, vec ? (n >> 2) : n)), dim3(kBlock), 0, ctx->stream, dr, dg, db, n,
                        (int)cfg->method, amount, (int)cfg->preserve_luminance, vec);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && tmp) {
@@ -375,7 +369,7 @@ int ab_apply_curve(ab_ctx *ctx, const ab_plane *img, const float *lut4096_host, 
     AB_HIP(ctx, hipMemcpyAsync(dlut, lut4096_host, 4096 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     AB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host LUT may be a temporary
     return unary_map(ctx, img, out, [&](const float *in, int64_t n, float *o) {
-        hipLaunchKernelGGL(curve_kernel, dim3(stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in, n, (const float *)dlut, o);
+        hipLaunchKernelGGL(curve_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in, n, (const float *)dlut, o);
     });
 } AB_CATCH(ctx)
 
@@ -390,7 +384,7 @@ int ab_apply_levels(ab_ctx *ctx, const ab_plane *img, const ab_levels_params *p,
     const double range = std::fmax(p->white - p->black, 1e-15);
     const double inv_range = 1.0 / range, inv_gamma = 1.0 / clampd(p->gamma, 0.01, 10.0);
     return unary_map(ctx, img, out, [&](const float *in, int64_t n, float *o) {
-        hipLaunchKernelGGL(levels_kernel, dim3(stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in, n, p->black, inv_range,
+        hipLaunchKernelGGL(levels_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in, n, p->black, inv_range,
                            inv_gamma, o);
     });
 } AB_CATCH(ctx)
@@ -410,7 +404,7 @@ int ab_arcsinh_stretch_with_stats(ab_ctx *ctx, const ab_plane *img, float dmin, 
     const float inv_range = 1.0f / range, inv_denom = 1.0f / asinhf(factor);
     const int apply_gamma = std::fabs(gamma - 1.0f) > 1e-6f;
     return unary_map(ctx, img, out, [&](const float *in, int64_t n, float *o) {
-        hipLaunchKernelGGL(arcsinh_kernel, dim3(stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in, n, dmin, inv_range, factor,
+        hipLaunchKernelGGL(arcsinh_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in, n, dmin, inv_range, factor,
                            inv_denom, apply_gamma, gamma, o);
     });
 } AB_CATCH(ctx)
@@ -419,7 +413,7 @@ int ab_scale(ab_ctx *ctx, const ab_plane *img, float factor, ab_plane_mut *out) 
     if (!ctx) return AB_ERR_INVALID;
     return unary_map(ctx, img, out, [&](const float *in, int64_t n, float *o) {
         const int vec = (((uintptr_t)in | (uintptr_t)o) & 15) == 0;
-        hipLaunchKernelGGL(scale_kernel, dim3(stream_grid(ctx, vec ? (n >> 2) : n)), dim3(kBlock), 0, ctx->stream, in, n, factor, o,
+        hipLaunchKernelGGL(scale_kernel, dim3(ab_stream_grid(ctx, vec ? (n >> 2) : n)), dim3(kBlock), 0, ctx->stream, in, n, factor, o,
                            vec);
     });
 } AB_CATCH(ctx)
@@ -441,7 +435,7 @@ int ab_luminance(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_pla
             rc = ab_stage_out_begin(ctx, out, &so);
             if (rc == AB_OK) {
                 const int64_t n = r->rows * r->cols;
-                hipLaunchKernelGGL(luminance_kernel, dim3(stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, sr.dptr, sg.dptr,
+                hipLaunchKernelGGL(luminance_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, sr.dptr, sg.dptr,
                                    sb.dptr, n, so.dptr);
                 hipError_t e = hipGetLastError();
                 if (e != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "luminance: %s", hipGetErrorString(e));
@@ -477,7 +471,7 @@ int ab_calibrate_image(ab_ctx *ctx, const ab_plane *raw, const ab_plane *bias, c
     }
     if (rc == AB_OK)
         rc = unary_map(ctx, raw, out, [&](const float *in, int64_t n, float *o) {
-            hipLaunchKernelGGL(calibrate_kernel, dim3(stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in, d[0], d[1], d[2],
+            hipLaunchKernelGGL(calibrate_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in, d[0], d[1], d[2],
                                dark_exposure_ratio, n, o);
         });
     for (int i = 0; i < staged; ++i)

@@ -11,18 +11,13 @@
 // the registration scalars visit the host.  Every per-pixel map is a streaming f32 kernel at
 // 4 B read + 4 B written per pixel.
 #include "ab_common.hpp"
+#include "entry_host.hpp"
 
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
 
 namespace {
-
-constexpr int kBlock = 256;
-
-int stream_grid(ab_ctx *ctx, int64_t n) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8));
-}
 
 #define AB_GRID_LOOP(i, n) \
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride_ = (int64_t)gridDim.x * kBlock; i < (n); i += stride_)
@@ -65,27 +60,6 @@ __global__ __launch_bounds__(kBlock) void compose_stf_kernel(float *__restrict__
     }
 }
 
-struct Scope {  // frees / aborts everything registered with it when the entry point returns
-    ab_ctx *ctx;
-    std::vector<StagedPlane *> ins;
-    std::vector<StagedOut *> outs;
-    std::vector<void *> dev;
-    int next_slot = 0;
-    explicit Scope(ab_ctx *c) : ctx(c) {}
-    ~Scope() {
-        for (StagedOut *o : outs) ab_stage_out_abort(ctx, o);
-        if (!dev.empty()) (void)hipStreamSynchronize(ctx->stream);
-        for (void *p : dev) (void)hipFree(p);
-        for (StagedPlane *p : ins) ab_stage_release(ctx, p);
-    }
-    int alloc(float **p, int64_t n) {  // out of the context's scope slots (kept between calls); a ninth plane is allocated and freed
-        if (next_slot < 8) return ab_workspace(ctx, AB_WS_SCOPE0 + next_slot++, std::max<size_t>((size_t)n, 1) * sizeof(float), (void **)p);
-        AB_HIP(ctx, hipMalloc((void **)p, std::max<size_t>((size_t)n, 1) * sizeof(float)));
-        dev.push_back(*p);
-        return AB_OK;
-    }
-};
-
 int copy_plane(ab_ctx *ctx, float *dst, const float *src, int64_t n) {
     if (n > 0 && dst != src) AB_HIP(ctx, hipMemcpyAsync(dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     return AB_OK;
@@ -96,7 +70,7 @@ int channel_or_synth(ab_ctx *ctx, const float *primary, const float *alt1, const
     if (primary) return copy_plane(ctx, dst, primary, n);
     if (alt1 && alt2) {
         if (n > 0) {
-            hipLaunchKernelGGL(avg2_kernel, dim3(stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, alt1, alt2, n, dst);
+            hipLaunchKernelGGL(avg2_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, alt1, alt2, n, dst);
             AB_HIP(ctx, hipGetLastError());
         }
         return AB_OK;
@@ -169,28 +143,20 @@ int ab_process_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_p
     info->cols = (uint64_t)cols;
     info->resampled = resample ? 1 : 0;
 
-    StagedPlane in[3];
-    StagedOut so[3], sp[3];
     Scope sc(ctx);
     const float *eff[3] = {nullptr, nullptr, nullptr};
     for (int c = 0; c < 3; ++c) {
         if (!ch[c]) continue;
-        AB_TRY(ab_stage_in(ctx, ch[c], &in[c]));
-        sc.ins.push_back(&in[c]);
-        eff[c] = in[c].dptr;
+        AB_TRY(sc.stage_in(ch[c], &eff[c]));
         if (resample && !(ch[c]->rows == rows && ch[c]->cols == cols)) {  // :106-119
             float *h = nullptr;
-            AB_TRY(sc.alloc(&h, n));
-            AB_TRY(ab_resample_device(ctx, in[c].dptr, ch[c]->rows, ch[c]->cols, rows, cols, h));
+            AB_TRY(sc.alloc((void **)&h, (size_t)n * sizeof(float)));
+            AB_TRY(ab_resample_device(ctx, eff[c], ch[c]->rows, ch[c]->cols, rows, cols, h));
             eff[c] = h;
         }
     }
     float *img[3];
-    for (int c = 0; c < 3; ++c) {
-        AB_TRY(ab_stage_out_begin(ctx, outs[c], &so[c]));
-        sc.outs.push_back(&so[c]);
-        img[c] = so[c].dptr;
-    }
+    for (int c = 0; c < 3; ++c) AB_TRY(sc.stage_out(outs[c], &img[c]));
     const int alt[3][2] = {{1, 2}, {0, 2}, {0, 1}};
     const bool do_align = cfg->align != 0;  // && count >= 2 (always true here)
     for (int c = 0; c < 3; ++c) {
@@ -231,7 +197,7 @@ int ab_process_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_p
     for (int c = 0; c < 3; ++c) {  // apply_multiplier_inplace (:127-130)
         const float mult = (float)wb[c];
         if (std::fabs(mult - 1.0f) < 1e-7f || n == 0) continue;
-        hipLaunchKernelGGL(scale_inplace_kernel, dim3(stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, img[c], n, mult);
+        hipLaunchKernelGGL(scale_inplace_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, img[c], n, mult);
         AB_HIP(ctx, hipGetLastError());
         scaled[c] = true;
     }
@@ -247,11 +213,11 @@ int ab_process_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_p
     };
     if (cfg->auto_stretch && cfg->linked_stf) {  // :265-273
         float *comb = nullptr;
-        AB_TRY(sc.alloc(&comb, n));
+        AB_TRY(sc.alloc((void **)&comb, (size_t)n * sizeof(float)));
         ab_image_stats st;
         memset(&st, 0, sizeof st);
         if (n > 0) {
-            hipLaunchKernelGGL(merge3_kernel, dim3(stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, img[0], img[1], img[2], n, comb);
+            hipLaunchKernelGGL(merge3_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, img[0], img[1], img[2], n, comb);
             AB_HIP(ctx, hipGetLastError());
             AB_TRY(ab_stats_device(ctx, comb, n, 0, 0.0, 0.0, &st));
         }
@@ -278,9 +244,9 @@ int ab_process_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_p
     for (int c = 0; c < 3; ++c) {
         info->stats_wb[c] = wbst[c];
         if (pres[c]) {  // pre_stretch_* (:296-298)
-            AB_TRY(ab_stage_out_begin(ctx, pres[c], &sp[c]));
-            sc.outs.push_back(&sp[c]);
-            AB_TRY(copy_plane(ctx, sp[c].dptr, img[c], n));
+            float *pre = nullptr;
+            AB_TRY(sc.stage_out(pres[c], &pre));
+            AB_TRY(copy_plane(ctx, pre, img[c], n));
         }
         if (n > 0) {  // apply_stf_inplace (:191-207)
             ComposeStf t;
@@ -289,7 +255,7 @@ int ab_process_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_p
             t.shadow = info->stf[c].shadow;
             t.clip_range = std::fmax(info->stf[c].highlight - info->stf[c].shadow, 1e-15);
             t.m = info->stf[c].midtone;
-            hipLaunchKernelGGL(compose_stf_kernel, dim3(stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, img[c], n, t);
+            hipLaunchKernelGGL(compose_stf_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, img[c], n, t);
             AB_HIP(ctx, hipGetLastError());
         }
     }
@@ -299,11 +265,7 @@ int ab_process_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_p
         AB_TRY(ab_apply_scnr_inplace(ctx, &pm[0], &pm[1], &pm[2], &cfg->scnr));
         info->scnr_applied = 1;
     }
-    for (int c = 0; c < 3; ++c) {
-        AB_TRY(ab_stage_out_finish(ctx, &so[c]));
-        if (pres[c]) AB_TRY(ab_stage_out_finish(ctx, &sp[c]));
-    }
-    return AB_OK;
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 }  // extern "C"

@@ -23,6 +23,7 @@
 // Both take up to kBatch planes of any dims in ONE launch: the kernel argument holds a table of (pointer, dims, first workgroup) and
 // a workgroup finds its plane by its index.  More than kBatch planes are served kBatch at a time.
 #include "ab_common.hpp"
+#include "entry_host.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -30,7 +31,7 @@
 
 namespace {
 
-constexpr int kBlock = 256;                 // the copy's workgroup, at most 8 per CU
+// (the copy's workgroup is entry_host.hpp's kBlock, at most 8 per CU)
 // The detection's workgroups each end in four atomics on one 16-byte slot, which the L2 serialises (about 5.5 ns each): with 2048
 // workgroups of 256 lanes a 4096^2 plane took 55 us, 45 of them that queue.  Sixteen waves per workgroup and two workgroups per CU keep
 // the same waves in flight with a quarter of the atomics: 22 us; one per CU loses bandwidth on large planes, four gain nothing there
@@ -224,8 +225,6 @@ __global__ __launch_bounds__(kBlock) void crop_kernel(const CropArgs a) {
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
-bool fits31(int64_t rows, int64_t cols) { return rows <= ((int64_t(1) << 31) - 1) / cols; }  // rows * cols < 2^31 (cols >= 1)
-
 int plane_check(ab_ctx *ctx, const ab_plane *p, size_t i) {
     AB_CHECK(ctx, p && p->data, "null plane %zu", i);
     AB_CHECK(ctx, p->rows >= 1 && p->cols >= 1, "plane %zu has a zero dimension (%lld x %lld)", i, (long long)p->rows, (long long)p->cols);
@@ -253,31 +252,15 @@ int64_t wg_cap(const ab_ctx *ctx, size_t planes, int per_cu) {
     return std::max<int64_t>(1, cap / (int64_t)std::max<size_t>(planes, 1));
 }
 
-struct StagedIns {  // releases the staged inputs when the entry point returns
-    ab_ctx *ctx;
-    std::vector<StagedPlane> in;
-    StagedIns(ab_ctx *c, size_t n) : ctx(c), in(n) {}
-    ~StagedIns() {
-        for (StagedPlane &p : in) ab_stage_release(ctx, &p);
-    }
-};
-struct StagedOuts {
-    ab_ctx *ctx;
-    std::vector<StagedOut> out;
-    StagedOuts(ab_ctx *c, size_t n) : ctx(c), out(n) {}
-    ~StagedOuts() {
-        for (StagedOut &o : out) ab_stage_out_abort(ctx, &o);  // (a finished output owns nothing any more)
-    }
-};
-
 // the boxes of n checked planes: boxes[4 i ..] = (top, bottom, left, right) of plane i
 int detect_boxes(ab_ctx *ctx, const ab_plane *imgs, size_t n, float threshold, std::vector<uint32_t> *boxes) {
     boxes->assign(4 * n, 0u);
     if (n == 0) return AB_OK;
     AB_HIP(ctx, hipSetDevice(ctx->device));
     AB_TRY(ab_cancel_point(ctx));
-    StagedIns st(ctx, n);
-    for (size_t i = 0; i < n; ++i) AB_TRY(ab_stage_in(ctx, &imgs[i], &st.in[i]));
+    Scope sc(ctx);
+    std::vector<const float *> src(n, nullptr);
+    for (size_t i = 0; i < n; ++i) AB_TRY(sc.stage_in(&imgs[i], &src[i]));
     uint32_t *slots = nullptr;
     AB_TRY(ab_scratch(ctx, 4 * n * sizeof(uint32_t), (void **)&slots));
     for (size_t first = 0; first < n; first += kBatch) {
@@ -290,12 +273,12 @@ int detect_boxes(ab_ctx *ctx, const ab_plane *imgs, size_t n, float threshold, s
         uint32_t wgs = 0;
         const int64_t cap = wg_cap(ctx, count, kBoxPerCu);
         for (size_t k = 0; k < count; ++k) {
-            const StagedPlane &p = st.in[first + k];
+            const ab_plane &p = imgs[first + k];
             BoxEnt &e = a.e[k];
-            e.src = p.dptr;
+            e.src = src[first + k];
             e.rows = (uint32_t)p.rows, e.cols = (uint32_t)p.cols, e.n = (uint32_t)(p.rows * p.cols);
             e.wg0 = wgs;
-            wgs += split((uintptr_t)p.dptr, e.n, kBoxBlock, cap, &e.head, &e.quads, &e.per);
+            wgs += split((uintptr_t)e.src, e.n, kBoxBlock, cap, &e.head, &e.quads, &e.per);
             e.step_r = 4u * kBoxBlock / e.cols, e.step_c = 4u * kBoxBlock % e.cols;
         }
         hipLaunchKernelGGL(bbox_init_kernel, dim3(1), dim3(64), 0, ctx->stream, a);
@@ -363,8 +346,8 @@ int out_check(ab_ctx *ctx, const ab_plane *src, const Window &w, const ab_plane_
 int crop_planes(ab_ctx *ctx, const ab_plane *imgs, size_t n, const Window *win, ab_plane_mut *outs, ab_image_stats *stats) {
     AB_HIP(ctx, hipSetDevice(ctx->device));
     AB_TRY(ab_cancel_point(ctx));
-    StagedIns si(ctx, n);
-    StagedOuts so(ctx, n);
+    Scope sc(ctx);
+    std::vector<float *> dst(n, nullptr);
     std::vector<size_t> live;  // the planes with something to copy
     for (size_t i = 0; i < n; ++i)
         if (win[i].area() > 0) live.push_back(i);
@@ -375,10 +358,11 @@ int crop_planes(ab_ctx *ctx, const ab_plane *imgs, size_t n, const Window *win, 
             origin[i] = reinterpret_cast<const uint32_t *>(imgs[i].data) + w.t * imgs[i].cols + w.l;
         } else {  // rows [t, b) of a host plane are one contiguous block
             const ab_plane band{imgs[i].data + w.t * imgs[i].cols, w.rows(), imgs[i].cols, 0};
-            AB_TRY(ab_stage_in(ctx, &band, &si.in[i]));
-            origin[i] = reinterpret_cast<const uint32_t *>(si.in[i].dptr) + w.l;
+            const float *staged = nullptr;
+            AB_TRY(sc.stage_in(&band, &staged));
+            origin[i] = reinterpret_cast<const uint32_t *>(staged) + w.l;
         }
-        AB_TRY(ab_stage_out_begin(ctx, &outs[i], &so.out[i]));
+        AB_TRY(sc.stage_out(&outs[i], &dst[i]));
     }
     for (size_t first = 0; first < live.size(); first += kBatch) {
         const size_t count = std::min<size_t>(kBatch, live.size() - first);
@@ -391,7 +375,7 @@ int crop_planes(ab_ctx *ctx, const ab_plane *imgs, size_t n, const Window *win, 
             const size_t i = live[first + k];
             CropEnt &e = a.e[k];
             e.src = origin[i];
-            e.dst = reinterpret_cast<uint32_t *>(so.out[i].dptr);
+            e.dst = reinterpret_cast<uint32_t *>(dst[i]);
             e.ld = (uint32_t)imgs[i].cols, e.ocols = (uint32_t)win[i].cols(), e.n = (uint32_t)win[i].area();
             e.wg0 = wgs;
             wgs += split((uintptr_t)e.dst, e.n, kBlock, cap, &e.head, &e.quads, &e.per);
@@ -403,11 +387,10 @@ int crop_planes(ab_ctx *ctx, const ab_plane *imgs, size_t n, const Window *win, 
     if (stats) {
         for (size_t i = 0; i < n; ++i) {
             memset(&stats[i], 0, sizeof stats[i]);  // ImageStats::default()
-            if (win[i].area() > 0) AB_TRY(ab_stats_device(ctx, so.out[i].dptr, win[i].area(), 0, 0.0, 0.0, &stats[i]));
+            if (win[i].area() > 0) AB_TRY(ab_stats_device(ctx, dst[i], win[i].area(), 0, 0.0, 0.0, &stats[i]));
         }
     }
-    for (size_t i : live) AB_TRY(ab_stage_out_finish(ctx, &so.out[i]));
-    return AB_OK;
+    return sc.finish_outs();
 }
 
 }  // namespace
@@ -417,7 +400,7 @@ extern "C" {
 int ab_detect_valid_region(ab_ctx *ctx, const ab_plane *img, float threshold, ab_crop_box *out) try {
     if (!ctx) return AB_ERR_INVALID;
     AB_CHECK(ctx, out, "null output");
-    AB_TRY(plane_check(ctx, img, 0));
+    AB_TRY(plane_check(ctx, img, size_t(0)));
     std::vector<uint32_t> boxes;
     AB_TRY(detect_boxes(ctx, img, 1, threshold, &boxes));
     *out = box_of(boxes.data());
@@ -439,7 +422,7 @@ int ab_detect_valid_regions(ab_ctx *ctx, const ab_plane *imgs, size_t n, float t
 int ab_crop_array(ab_ctx *ctx, const ab_plane *src, const ab_crop_box *box, ab_plane_mut *out) try {
     if (!ctx) return AB_ERR_INVALID;
     AB_CHECK(ctx, box, "null box");
-    AB_TRY(plane_check(ctx, src, 0));
+    AB_TRY(plane_check(ctx, src, size_t(0)));
     const Window w = clamp_window(box, src->rows, src->cols);
     AB_TRY(out_check(ctx, src, w, out, 0));
     return crop_planes(ctx, src, 1, &w, out, nullptr);

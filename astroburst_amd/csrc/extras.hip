@@ -15,10 +15,6 @@ namespace {
 
 constexpr int kBlock = 256;
 
-int stream_grid(ab_ctx *ctx, int64_t n) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8));
-}
-
 #define AB_GRID_LOOP(i, n) \
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride_ = (int64_t)gridDim.x * kBlock; i < (n); i += stride_)
 
@@ -127,7 +123,7 @@ int ab_apply_lrgb(ab_ctx *ctx, const ab_plane *l, ab_plane_mut *r, ab_plane_mut 
         }
     }
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(lrgb_kernel, dim3(stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, sl.dptr, d[0], d[1], d[2], n, lightness_weight,
+        hipLaunchKernelGGL(lrgb_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, sl.dptr, d[0], d[1], d[2], n, lightness_weight,
                            chrominance_weight);
         e = hipGetLastError();
     }
@@ -159,7 +155,7 @@ int ab_synthesize_luminance(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, c
     if (rc == AB_OK) {
         const int64_t n = r->rows * r->cols;
         if (n > 0) {
-            hipLaunchKernelGGL(lum_plain_kernel, dim3(stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in[0].dptr, in[1].dptr, in[2].dptr, n,
+            hipLaunchKernelGGL(lum_plain_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in[0].dptr, in[1].dptr, in[2].dptr, n,
                                so.dptr);
             if (hipGetLastError() != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "luminance launch failed");
         }
@@ -201,7 +197,7 @@ int ab_calibrate_channel(ab_ctx *ctx, const ab_plane *orig, float factor, const 
         const int64_t n = in.rows * in.cols;
         memset(out_stats, 0, sizeof *out_stats);
         if (n > 0) {
-            hipLaunchKernelGGL(scale_kernel, dim3(stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in.dptr, n, factor, so.dptr);
+            hipLaunchKernelGGL(scale_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in.dptr, n, factor, so.dptr);
             if (hipGetLastError() != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "scale launch failed");
             if (rc == AB_OK) {
                 if (n <= 4000000) {  // PAR_THRESHOLD, color.rs:19,28-32
@@ -255,7 +251,7 @@ int ab_create_master(ab_ctx *ctx, int32_t kind, const ab_plane *frames, size_t n
             if (rc != AB_OK) break;
             float *dst = pre + f * (size_t)n;
             if (n > 0) {
-                hipLaunchKernelGGL(preprocess_kernel, dim3(stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, sf.dptr, bias ? sb.dptr : nullptr,
+                hipLaunchKernelGGL(preprocess_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, sf.dptr, bias ? sb.dptr : nullptr,
                                    dark ? sd.dptr : nullptr, n, dst);
                 if (hipGetLastError() != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "preprocess launch failed");
             }
@@ -278,7 +274,7 @@ int ab_create_master(ab_ctx *ctx, int32_t kind, const ab_plane *frames, size_t n
         AB_HIP(ctx, hipMalloc(&tmp, (size_t)n * sizeof(float)));
         d = (float *)tmp;
     }
-    const int grid = stream_grid(ctx, n);
+    const int grid = ab_stream_grid(ctx, n);
     double *psum = nullptr;
     unsigned long long *pcnt = nullptr;
     hipError_t e = hipMalloc((void **)&psum, grid * sizeof(double));

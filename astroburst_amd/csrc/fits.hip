@@ -17,10 +17,6 @@ namespace {
 
 constexpr int kBlock = 256;
 
-int stream_grid(ab_ctx *ctx, int64_t n) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8));
-}
-
 #define AB_GRID_LOOP(i, n) \
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride_ = (int64_t)gridDim.x * kBlock; i < (n); i += stride_)
 
@@ -116,7 +112,7 @@ int bytes_per_pixel(int64_t bitpix) {
 int ab_fits_decode_device(ab_ctx *ctx, const uint8_t *raw, int64_t n, int64_t bitpix, double bscale, double bzero, float *out) {
     if (n <= 0) return AB_OK;
     const int identity = std::fabs(bscale - 1.0) < 1e-15 && std::fabs(bzero) < 1e-15;  // reader.rs:36-39
-    const dim3 grid(stream_grid(ctx, n)), block(kBlock);
+    const dim3 grid(ab_stream_grid(ctx, n)), block(kBlock);
     switch (bitpix) {
         case 8: hipLaunchKernelGGL(fits_decode_kernel<8>, grid, block, 0, ctx->stream, raw, n, identity, bscale, bzero, out); break;
         case 16: hipLaunchKernelGGL(fits_decode_kernel<16>, grid, block, 0, ctx->stream, raw, n, identity, bscale, bzero, out); break;
@@ -176,7 +172,7 @@ int ab_fits_compute_bzero_bscale(ab_ctx *ctx, const ab_plane *img, double *bzero
     StagedPlane in;
     AB_TRY(ab_stage_in(ctx, img, &in));
     const int64_t n = in.rows * in.cols;
-    const int grid = stream_grid(ctx, n);
+    const int grid = ab_stream_grid(ctx, n);
     void *d = nullptr;
     int rc = ab_scratch(ctx, (size_t)grid * 2 * sizeof(double), &d);
     std::vector<double> h((size_t)grid * 2);
@@ -221,7 +217,7 @@ int ab_fits_encode_pixels(ab_ctx *ctx, const ab_plane *img, int32_t bitpix, doub
         dst = (uint8_t *)tmp;
     }
     if (e == hipSuccess) {
-        const dim3 grid(stream_grid(ctx, n)), block(kBlock);
+        const dim3 grid(ab_stream_grid(ctx, n)), block(kBlock);
         if (bitpix == -32)
             hipLaunchKernelGGL(fits_encode_kernel<-32>, grid, block, 0, ctx->stream, in.dptr, n, bzero, bscale, dst);
         else if (bitpix == 16)

@@ -13,13 +13,13 @@
 // and selects a P-sized Vec serially, masked_stretch.rs:213-229) and one fused kernel doing apply_mtf + the
 // mask-weighted blend in place (the reference materialises the stretched copy first).
 #include "ab_common.hpp"
+#include "entry_host.hpp"
 
 #include <algorithm>
 #include <cmath>
 
 namespace {
 
-constexpr int kBlock = 256;
 
 struct StarDisc {
     double x, y, fwhm;
@@ -128,33 +128,6 @@ __global__ __launch_bounds__(kBlock) void mtf_blend_kernel(float *__restrict__ w
     }
 }
 
-int stream_grid(ab_ctx *ctx, int64_t n) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8));
-}
-
-// frees / aborts everything registered with it when the entry point returns
-struct Scope {
-    ab_ctx *ctx;
-    std::vector<StagedPlane *> ins;
-    std::vector<StagedOut *> outs;
-    std::vector<void *> dev;
-    int next_slot = 0;
-    explicit Scope(ab_ctx *c) : ctx(c) {}
-    ~Scope() {
-        for (StagedOut *o : outs) ab_stage_out_abort(ctx, o);
-        if (!dev.empty()) (void)hipStreamSynchronize(ctx->stream);
-        for (void *p : dev) (void)hipFree(p);
-        for (StagedPlane *p : ins) ab_stage_release(ctx, p);
-    }
-    // the call's device planes come out of the context's scope slots (kept between calls); a ninth one would be allocated and freed
-    int alloc(void **p, size_t bytes) {
-        if (next_slot < 8) return ab_workspace(ctx, AB_WS_SCOPE0 + next_slot++, std::max<size_t>(bytes, 16), p);
-        AB_HIP(ctx, hipMalloc(p, bytes));
-        dev.push_back(*p);
-        return AB_OK;
-    }
-};
-
 // generate_star_mask_from_detection on device planes (mask: rows * cols floats)
 int star_mask_device(ab_ctx *ctx, const float *img, int64_t rows, int64_t cols, const std::vector<StarDisc> &all, const ab_star_mask_config &cfg,
                      float *mask, ab_star_mask_info *info, Scope &sc) {
@@ -183,7 +156,7 @@ int star_mask_device(ab_ctx *ctx, const float *img, int64_t rows, int64_t cols, 
     AB_HIP(ctx, hipMemsetAsync(dcov, 0, sizeof(unsigned long long), ctx->stream));
     const float ceiling = (float)cfg.luminance_ceiling;
     const float inv_range = ceiling < 1.0f ? 1.0f / (1.0f - ceiling) : 1.0f;
-    hipLaunchKernelGGL(mask_protect_count_kernel, dim3(stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, img, mask, n, cfg.luminance_protect ? 1 : 0,
+    hipLaunchKernelGGL(mask_protect_count_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, img, mask, n, cfg.luminance_protect ? 1 : 0,
                        ceiling, inv_range, dcov);
     AB_HIP(ctx, hipGetLastError());
     unsigned long long covered = 0;
@@ -587,7 +560,7 @@ int masked_stretch_enqueue(ab_ctx *ctx, hipStream_t stream, const float *img, co
     unsigned int *hist = (unsigned int *)((char *)scratch + ((sizeof(MsState) + 63) & ~(size_t)63));
     if (!have_range) hipLaunchKernelGGL(ms_init_kernel, dim3(4), dim3(1024), 0, stream, st, hist);  // (no fill, no copy: the chain's state starts on the device)
     if (n <= 0) return AB_OK;
-    const int grid = stream_grid(ctx, n);
+    const int grid = ab_stream_grid(ctx, n);
     const int iterations = (int)std::min<size_t>(cfg.iterations, 1000000);
     const float protection = (float)cfg.protection_amount;
     const int predict = ab_dev_env("AB_MS_NO_PREDICT") ? 0 : 1;  // (developer A/B: both forms of level 1 on the same input)
@@ -671,17 +644,15 @@ int ab_generate_star_mask_from_stars(ab_ctx *ctx, const ab_plane *img, const ab_
     AB_CHECK(ctx, out_mask->rows == img->rows && out_mask->cols == img->cols, "mask must have the image's dims");
     AB_CHECK(ctx, img->rows * img->cols < (int64_t(1) << 31), "image too large for this build");
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedPlane in;
-    StagedOut so;
     Scope sc(ctx);
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    sc.ins.push_back(&in);
-    AB_TRY(ab_stage_out_begin(ctx, out_mask, &so));
-    sc.outs.push_back(&so);
+    const float *in = nullptr;
+    float *out_dev = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    AB_TRY(sc.stage_out(out_mask, &out_dev));
     std::vector<StarDisc> discs;
     for (size_t i = 0; i < n_stars; ++i) discs.push_back({stars[i].x, stars[i].y, stars[i].fwhm});
-    AB_TRY(star_mask_device(ctx, in.dptr, in.rows, in.cols, discs, *cfg, so.dptr, info, sc));
-    return ab_stage_out_finish(ctx, &so);
+    AB_TRY(star_mask_device(ctx, in, img->rows, img->cols, discs, *cfg, out_dev, info, sc));
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 int ab_generate_star_mask(ab_ctx *ctx, const ab_plane *img, const ab_star_mask_config *cfg, ab_plane_mut *out_mask, ab_star_mask_info *info) try {
@@ -690,17 +661,15 @@ int ab_generate_star_mask(ab_ctx *ctx, const ab_plane *img, const ab_star_mask_c
     AB_CHECK(ctx, out_mask->rows == img->rows && out_mask->cols == img->cols, "mask must have the image's dims");
     AB_CHECK(ctx, img->rows * img->cols < (int64_t(1) << 31), "image too large for this build");
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedPlane in;
-    StagedOut so;
     Scope sc(ctx);
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    sc.ins.push_back(&in);
-    AB_TRY(ab_stage_out_begin(ctx, out_mask, &so));
-    sc.outs.push_back(&so);
+    const float *in = nullptr;
+    float *out_dev = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    AB_TRY(sc.stage_out(out_mask, &out_dev));
     std::vector<StarDisc> discs;
-    AB_TRY(detect_discs(ctx, in.dptr, in.rows, in.cols, cfg->detection_sigma, &discs));
-    AB_TRY(star_mask_device(ctx, in.dptr, in.rows, in.cols, discs, *cfg, so.dptr, info, sc));
-    return ab_stage_out_finish(ctx, &so);
+    AB_TRY(detect_discs(ctx, in, img->rows, img->cols, cfg->detection_sigma, &discs));
+    AB_TRY(star_mask_device(ctx, in, img->rows, img->cols, discs, *cfg, out_dev, info, sc));
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 int ab_masked_stretch_with_mask(ab_ctx *ctx, const ab_plane *img, const ab_plane *mask, const ab_star_mask_info *mask_info,
@@ -710,22 +679,19 @@ int ab_masked_stretch_with_mask(ab_ctx *ctx, const ab_plane *img, const ab_plane
     AB_CHECK(ctx, same_dims(mask, img->rows, img->cols) && out->rows == img->rows && out->cols == img->cols,
              "mask and output must have the image's dims");
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedPlane in, mk;
-    StagedOut so;
     Scope sc(ctx);
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    sc.ins.push_back(&in);
-    AB_TRY(ab_stage_in(ctx, mask, &mk));
-    sc.ins.push_back(&mk);
-    AB_TRY(ab_stage_out_begin(ctx, out, &so));
-    sc.outs.push_back(&so);
+    const float *in = nullptr, *mk = nullptr;
+    float *out_dev = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    AB_TRY(sc.stage_in(mask, &mk));
+    AB_TRY(sc.stage_out(out, &out_dev));
     memset(res, 0, sizeof *res);
-    AB_TRY(masked_stretch_device(ctx, in.dptr, mk.dptr, in.rows * in.cols, *cfg, so.dptr, res, sc));
+    AB_TRY(masked_stretch_device(ctx, in, mk, img->rows * img->cols, *cfg, out_dev, res, sc));
     if (mask_info) {
         res->stars_masked = mask_info->stars_masked;
         res->mask_coverage = mask_info->coverage_fraction;
     }
-    return ab_stage_out_finish(ctx, &so);
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 int ab_masked_stretch(ab_ctx *ctx, const ab_plane *img, const ab_masked_stretch_config *cfg, ab_plane_mut *out, ab_masked_stretch_result *res) try {
@@ -734,26 +700,24 @@ int ab_masked_stretch(ab_ctx *ctx, const ab_plane *img, const ab_masked_stretch_
     AB_CHECK(ctx, out->rows == img->rows && out->cols == img->cols, "output must have the image's dims");
     AB_CHECK(ctx, img->rows * img->cols < (int64_t(1) << 31), "image too large for this build");
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedPlane in;
-    StagedOut so;
     Scope sc(ctx);
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    sc.ins.push_back(&in);
-    AB_TRY(ab_stage_out_begin(ctx, out, &so));
-    sc.outs.push_back(&so);
-    const int64_t n = in.rows * in.cols;
+    const float *in = nullptr;
+    float *out_dev = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    AB_TRY(sc.stage_out(out, &out_dev));
+    const int64_t n = img->rows * img->cols;
     float *mask = nullptr;
     AB_TRY(sc.alloc((void **)&mask, std::max<size_t>((size_t)n, 1) * sizeof(float)));
     const ab_star_mask_config mc = mask_config_of(*cfg);
     ab_star_mask_info mi;
     std::vector<StarDisc> discs;
-    AB_TRY(detect_discs(ctx, in.dptr, in.rows, in.cols, mc.detection_sigma, &discs));
-    AB_TRY(star_mask_device(ctx, in.dptr, in.rows, in.cols, discs, mc, mask, &mi, sc));
+    AB_TRY(detect_discs(ctx, in, img->rows, img->cols, mc.detection_sigma, &discs));
+    AB_TRY(star_mask_device(ctx, in, img->rows, img->cols, discs, mc, mask, &mi, sc));
     memset(res, 0, sizeof *res);
-    AB_TRY(masked_stretch_device(ctx, in.dptr, mask, n, *cfg, so.dptr, res, sc));
+    AB_TRY(masked_stretch_device(ctx, in, mask, n, *cfg, out_dev, res, sc));
     res->stars_masked = mi.stars_masked;
     res->mask_coverage = mi.coverage_fraction;
-    return ab_stage_out_finish(ctx, &so);
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 int ab_masked_stretch_rgb_shared(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, const ab_masked_stretch_config *cfg,
@@ -768,15 +732,12 @@ int ab_masked_stretch_rgb_shared(ab_ctx *ctx, const ab_plane *r, const ab_plane 
     for (const ab_plane_mut *o : outs) AB_CHECK(ctx, o->rows == r->rows && o->cols == r->cols, "outputs must have the channels' dims");
     AB_CHECK(ctx, r->rows * r->cols < (int64_t(1) << 31), "image too large for this build");
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedPlane in[3];
-    StagedOut so[3];
     Scope sc(ctx);
     const ab_plane *ins[3] = {r, g, b};
-    for (int c = 0; c < 3; ++c) {
-        AB_TRY(ab_stage_in(ctx, ins[c], &in[c]));
-        sc.ins.push_back(&in[c]);
-    }
-    const int64_t rows = in[0].rows, cols = in[0].cols, n = rows * cols;
+    const float *in[3];
+    float *out_dev[3];
+    for (int c = 0; c < 3; ++c) AB_TRY(sc.stage_in(ins[c], &in[c]));
+    const int64_t rows = r->rows, cols = r->cols, n = rows * cols;
     float *lum = nullptr, *mask = nullptr;
     AB_TRY(sc.alloc((void **)&lum, std::max<size_t>((size_t)n, 1) * sizeof(float)));
     AB_TRY(sc.alloc((void **)&mask, std::max<size_t>((size_t)n, 1) * sizeof(float)));
@@ -789,7 +750,7 @@ int ab_masked_stretch_rgb_shared(ab_ctx *ctx, const ab_plane *r, const ab_plane 
                            (unsigned int *)(scratch + (size_t)c * kMsScratch + ((sizeof(MsState) + 63) & ~(size_t)63)));
     }
     if (n > 0) {
-        hipLaunchKernelGGL(luminance_range_kernel, dim3(stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in[0].dptr, in[1].dptr, in[2].dptr, n, lum,
+        hipLaunchKernelGGL(luminance_range_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in[0], in[1], in[2], n, lum,
                            states[0], states[1], states[2]);
         AB_HIP(ctx, hipGetLastError());
     }
@@ -806,15 +767,14 @@ int ab_masked_stretch_rgb_shared(ab_ctx *ctx, const ab_plane *r, const ab_plane 
     hipStream_t streams[3] = {ctx->stream, ctx->aux_stream, ctx->warp_stream};
     if (!ctx->switch_ev) AB_HIP(ctx, hipEventCreateWithFlags(&ctx->switch_ev, hipEventDisableTiming));
     for (int c = 0; c < 3; ++c) {
-        AB_TRY(ab_stage_out_begin(ctx, outs[c], &so[c]));
-        sc.outs.push_back(&so[c]);
+        AB_TRY(sc.stage_out(outs[c], &out_dev[c]));
         memset(&res3[c], 0, sizeof res3[c]);
     }
     AB_HIP(ctx, hipEventRecord(ctx->switch_ev, ctx->stream));  // mask, staged inputs and outputs are in place
     int rc = AB_OK;
     for (int c = 0; c < 3 && rc == AB_OK; ++c) {
         if (c > 0 && hipStreamWaitEvent(streams[c], ctx->switch_ev, 0) != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "hipStreamWaitEvent failed");
-        if (rc == AB_OK) rc = masked_stretch_enqueue(ctx, streams[c], in[c].dptr, mask, n, *cfg, so[c].dptr, scratch + (size_t)c * kMsScratch, /*have_range=*/true);
+        if (rc == AB_OK) rc = masked_stretch_enqueue(ctx, streams[c], in[c], mask, n, *cfg, out_dev[c], scratch + (size_t)c * kMsScratch, /*have_range=*/true);
     }
     // (whatever was enqueued is drained before anything is released, also on an error path)
     for (int c = 1; c < 3; ++c)
@@ -832,8 +792,7 @@ int ab_masked_stretch_rgb_shared(ab_ctx *ctx, const ab_plane *r, const ab_plane 
         res3[c].stars_masked = mi.stars_masked;
         res3[c].mask_coverage = mi.coverage_fraction;
     }
-    for (int c = 0; c < 3; ++c) AB_TRY(ab_stage_out_finish(ctx, &so[c]));
-    return AB_OK;
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 }  // extern "C"

@@ -257,9 +257,8 @@ Span make_span(const float *src, uintptr_t align_addr, int bytes_per_pixel, int6
 
 // workgroups for a sweep: enough for its groups (or, when it has none, for its pixels), at most per_cu per compute unit
 int grid_for(const ab_ctx *ctx, const Span &s, int per_cu) {
-    const int64_t cap = (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * per_cu;
     const int64_t lanes = std::max<int64_t>(s.quads, s.n - 4 * s.quads);
-    return (int)std::max<int64_t>(1, std::min<int64_t>((lanes + kBlock - 1) / kBlock, cap));
+    return ab_stream_grid(ctx, lanes, kBlock, per_cu);
 }
 
 int plane_check(ab_ctx *ctx, const ab_plane *img) {

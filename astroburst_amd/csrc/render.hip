@@ -10,6 +10,7 @@
 // 4 pixels per lane as whole dwords.  Arithmetic is the reference's (f32 for the linear maps, f64 for the STF, f64 for
 // the nearest-neighbour source index), so every byte is bit-exact against the CPU restatement.
 #include "ab_common.hpp"
+#include "entry_host.hpp"
 #include "stf_device.hpp"
 
 #include <algorithm>
@@ -17,8 +18,6 @@
 #include <cmath>
 
 namespace {
-
-constexpr int kBlock = 256;
 
 // `f32 as u8` (saturating, NaN -> 0)
 __device__ __forceinline__ unsigned char sat_u8(float v) { return !(v > 0.0f) ? 0 : (v >= 255.0f ? 255 : (unsigned char)v); }
@@ -31,12 +30,6 @@ struct Stf3 {
     StfTx t[3];
     int on;  // 0: the plain [0, 1] -> u8 map
 };
-
-// nearest-neighbour source index: ((d as f64) * ratio).min((len - 1) as f64) as usize  (helpers.rs:306,309)
-__device__ __forceinline__ int64_t nn_index(int64_t d, double ratio, int64_t len) {
-    const double s = (double)d * ratio, hi = (double)(len - 1);
-    return (int64_t)(s < hi ? s : hi);
-}
 
 template <bool ROUND>
 __device__ __forceinline__ unsigned char channel_u8(float v, const Stf3 &s, int c) {
@@ -194,11 +187,6 @@ __global__ __launch_bounds__(kBlock) void tile_level_kernel(Rgb in, int rows, in
     }
 }
 
-int grid_for(ab_ctx *ctx, int64_t items, int per_block) {
-    const int64_t cap = (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8;
-    return (int)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, cap));
-}
-
 void preview_dims(int64_t rows, int64_t cols, int64_t max_dim, int64_t *ph, int64_t *pw, double *y_ratio, double *x_ratio) {  // helpers.rs:283-290
     if (rows <= max_dim && cols <= max_dim) {
         *ph = rows;
@@ -253,22 +241,15 @@ int bytes_finish(ab_ctx *ctx, BytesOut *b, int rc) {
     return rc;
 }
 
-struct Staged3 {
-    StagedPlane p[3];
-    int n = 0;
-};
-int stage3(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, Staged3 *s) {
+// the three channels staged into the caller's scope, which releases them
+int stage3(Scope &sc, const ab_plane *r, const ab_plane *g, const ab_plane *b, Rgb *in) {
     const ab_plane *ch[3] = {r, g, b};
+    const float **d[3] = {&in->r, &in->g, &in->b};
     for (int c = 0; c < 3; ++c) {
-        AB_CHECK(ctx, ch[c] && ch[c]->rows == r->rows && ch[c]->cols == r->cols, "the three channels must share their dims");
-        const int rc = ab_stage_in(ctx, ch[c], &s->p[c]);
-        if (rc != AB_OK) return rc;
-        s->n = c + 1;
+        AB_CHECK(sc.ctx, ch[c] && ch[c]->rows == r->rows && ch[c]->cols == r->cols, "the three channels must share their dims");
+        AB_TRY(sc.stage_in(ch[c], d[c]));
     }
     return AB_OK;
-}
-void release3(ab_ctx *ctx, Staged3 *s) {
-    for (int c = 0; c < s->n; ++c) ab_stage_release(ctx, &s->p[c]);
 }
 
 int num_levels(int64_t width, int64_t height, int64_t ts) {  // tiles.rs:137-147
@@ -328,7 +309,7 @@ int percentile_bounds(ab_ctx *ctx, const float *data, int64_t n, double low_pct,
         return AB_OK;
     }
     // no pixel above the padding threshold: find_minmax_simd's portable branch (math/simd.rs:263-271)
-    const int grid = grid_for(ctx, n, kBlock * 8);
+    const int grid = ab_stream_grid(ctx, n, kBlock * 8);
     void *d = nullptr;
     AB_TRY(ab_scratch(ctx, grid * sizeof(float2), &d));
     hipLaunchKernelGGL(minmax_finite_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, data, n, (float2 *)d);
@@ -397,26 +378,21 @@ int ab_render_rgb_preview(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, con
     AB_CHECK(ctx, max_dim > 0, "max_dim must be > 0");
     Stf3 s3;
     AB_TRY(make_stf3(ctx, stf, stats, &s3));
-    Staged3 in;
-    int rc = stage3(ctx, r, g, b, &in);
+    Scope sc(ctx);
+    Rgb in;
+    AB_TRY(stage3(sc, r, g, b, &in));
+    int64_t ph, pw;
+    double yr, xr;
+    preview_dims(r->rows, r->cols, max_dim, &ph, &pw, &yr, &xr);
     BytesOut bo;
+    int rc = bytes_begin(ctx, out_rgb, out_on_device, (size_t)(ph * pw * 3), &bo);
+    if (rc == AB_OK && ((uintptr_t)bo.dptr & 3) != 0) rc = ab_set_error(ctx, AB_ERR_INVALID, "the preview buffer must be 4-byte aligned");
     if (rc == AB_OK) {
-        int64_t ph, pw;
-        double yr, xr;
-        preview_dims(r->rows, r->cols, max_dim, &ph, &pw, &yr, &xr);
-        rc = bytes_begin(ctx, out_rgb, out_on_device, (size_t)(ph * pw * 3), &bo);
-        if (rc == AB_OK) {
-            if (((uintptr_t)bo.dptr & 3) != 0) rc = ab_set_error(ctx, AB_ERR_INVALID, "the preview buffer must be 4-byte aligned");
-        }
-        if (rc == AB_OK) {
-            hipLaunchKernelGGL(preview_rgb_kernel, dim3(ab_div_up(ph * pw, kBlock * 4)), dim3(kBlock), 0, ctx->stream,
-                               Rgb{in.p[0].dptr, in.p[1].dptr, in.p[2].dptr}, r->rows, r->cols, ph, pw, yr, xr, s3, bo.dptr);
-            if (hipGetLastError() != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "preview launch failed");
-        }
-        rc = bytes_finish(ctx, &bo, rc);
+        hipLaunchKernelGGL(preview_rgb_kernel, dim3(ab_div_up(ph * pw, kBlock * 4)), dim3(kBlock), 0, ctx->stream, in, r->rows, r->cols, ph, pw, yr, xr,
+                           s3, bo.dptr);
+        if (hipGetLastError() != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "preview launch failed");
     }
-    release3(ctx, &in);
-    return rc;
+    return bytes_finish(ctx, &bo, rc);
 } AB_CATCH(ctx)
 
 int ab_ipc_encode_with_header(ab_ctx *ctx, const ab_plane *img, int64_t max_dim, void *out, int32_t out_on_device, size_t *out_len) try {
@@ -434,7 +410,7 @@ int ab_ipc_encode_with_header(ab_ctx *ctx, const ab_plane *img, int64_t max_dim,
     int rc = bytes_begin(ctx, out, out_on_device, bytes, &bo);
     if (rc == AB_OK && ((uintptr_t)bo.dptr & 3) != 0) rc = ab_set_error(ctx, AB_ERR_INVALID, "the IPC buffer must be 4-byte aligned");
     if (rc == AB_OK) {
-        const int grid = grid_for(ctx, ph * pw, kBlock * 8);
+        const int grid = ab_stream_grid(ctx, ph * pw, kBlock * 8);
         void *d = nullptr;
         rc = ab_scratch(ctx, grid * sizeof(float2), &d);
         std::vector<float2> part(grid);
@@ -559,20 +535,17 @@ int ab_generate_tile_pyramid_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane 
     int nl = 0;
     const size_t total = layout(r->rows, r->cols, tile_size, 3, levels, &nl);
     *num_levels_out = nl;
-    Staged3 in;
-    int rc = stage3(ctx, r, g, b, &in);
+    Scope sc(ctx);
+    Rgb in;
+    AB_TRY(stage3(sc, r, g, b, &in));
     BytesOut bo;
+    int rc = bytes_begin(ctx, tiles, tiles_on_device, total, &bo);
+    if (rc == AB_OK && ((uintptr_t)bo.dptr & 3) != 0) rc = ab_set_error(ctx, AB_ERR_INVALID, "the tile buffer must be 4-byte aligned");
     if (rc == AB_OK) {
-        rc = bytes_begin(ctx, tiles, tiles_on_device, total, &bo);
-        if (rc == AB_OK && ((uintptr_t)bo.dptr & 3) != 0) rc = ab_set_error(ctx, AB_ERR_INVALID, "the tile buffer must be 4-byte aligned");
-        if (rc == AB_OK) {
-            const float *base[3] = {in.p[0].dptr, in.p[1].dptr, in.p[2].dptr};
-            rc = pyramid<3>(ctx, base, levels, nl, tile_size, 0.0f, 1.0f, s3, bo.dptr);
-        }
-        rc = bytes_finish(ctx, &bo, rc);
+        const float *base[3] = {in.r, in.g, in.b};
+        rc = pyramid<3>(ctx, base, levels, nl, tile_size, 0.0f, 1.0f, s3, bo.dptr);
     }
-    release3(ctx, &in);
-    return rc;
+    return bytes_finish(ctx, &bo, rc);
 } AB_CATCH(ctx)
 
 }  // extern "C"

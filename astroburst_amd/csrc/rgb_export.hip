@@ -18,6 +18,7 @@
 // placed by it); the at most six pixels around the groups, or every pixel when a 16-bit output sits at an odd address, are done one
 // per lane by the first lanes of the grid.  Any float-aligned plane and any byte address of an output are served.
 #include "ab_common.hpp"
+#include "entry_host.hpp"
 #include "scnr_device.hpp"
 #include "stf_device.hpp"
 
@@ -26,7 +27,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kPackNone = -1;
 
 struct FinishArgs {
@@ -72,7 +72,8 @@ __device__ __forceinline__ void finish_px(const FinishArgs &a, float (&w)[3], fl
 // (v.clamp(0, 1) * top) [.round()] as uN: f32::clamp keeps a NaN, `as` truncates, saturates and sends NaN to 0 (rgb.rs:29-31, :71-73,
 // drizzle_rgb.rs:244-246); f32::round is half away from zero, written out for the x >= 0 that arrives here (x - trunc(x) is exact)
 template <int PACK>
-__device__ __forceinline__ uint32_t quantise(float s) {
+__device__ __forceinline__ uint32_t quantise_as(float s) {
+    if constexpr (PACK == AB_RGB_PACK_8) return quantise(s);  // the truncated byte is the preview's
     const float c = s < 0.0f ? 0.0f : (s > 1.0f ? 1.0f : s);
     float x = c * (PACK == AB_RGB_PACK_16BE ? 65535.0f : 255.0f);
     if constexpr (PACK == AB_RGB_PACK_8_ROUND) {
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(kBlock) void rgb_finish_kernel(const FinishArgs a) 
 #pragma unroll
             for (int k = 0; k < 4; ++k)
 #pragma unroll
-                for (int c = 0; c < 3; ++c) d[(3 * k + c) >> 1] |= be16(quantise<PACK>(s[c][k])) << (16 * ((3 * k + c) & 1));
+                for (int c = 0; c < 3; ++c) d[(3 * k + c) >> 1] |= be16(quantise_as<PACK>(s[c][k])) << (16 * ((3 * k + c) & 1));
             uint32_t *o = reinterpret_cast<uint32_t *>(a.out + 6 * i);
 #pragma unroll
             for (int j = 0; j < 6; ++j) o[j] = d[j];
@@ -138,7 +139,7 @@ __global__ __launch_bounds__(kBlock) void rgb_finish_kernel(const FinishArgs a) 
 #pragma unroll
             for (int k = 0; k < 4; ++k)
 #pragma unroll
-                for (int c = 0; c < 3; ++c) d[(3 * k + c) >> 2] |= quantise<PACK>(s[c][k]) << (8 * ((3 * k + c) & 3));
+                for (int c = 0; c < 3; ++c) d[(3 * k + c) >> 2] |= quantise_as<PACK>(s[c][k]) << (8 * ((3 * k + c) & 3));
             uint32_t *o = reinterpret_cast<uint32_t *>(a.out + 3 * i);
 #pragma unroll
             for (int j = 0; j < 3; ++j) o[j] = d[j];
@@ -157,11 +158,11 @@ __global__ __launch_bounds__(kBlock) void rgb_finish_kernel(const FinishArgs a) 
             if (a.out_wb[0]) a.out_wb[c][i] = w[c];
             if (a.out_s[0]) a.out_s[c][i] = s[c];
             if constexpr (PACK == AB_RGB_PACK_16BE) {
-                const uint32_t q = quantise<PACK>(s[c]);
+                const uint32_t q = quantise_as<PACK>(s[c]);
                 a.out[6 * i + 2 * c] = (uint8_t)(q >> 8);
                 a.out[6 * i + 2 * c + 1] = (uint8_t)(q & 255u);
             } else if constexpr (PACK != kPackNone) {
-                a.out[3 * i + c] = (uint8_t)quantise<PACK>(s[c]);
+                a.out[3 * i + c] = (uint8_t)quantise_as<PACK>(s[c]);
             }
         }
     }
@@ -175,69 +176,12 @@ __global__ __launch_bounds__(kBlock) void merge3_div_kernel(const float *__restr
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
-int grid_for(const ab_ctx *ctx, int64_t lanes) {
-    const int64_t cap = (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8;
-    return (int)std::max<int64_t>(1, std::min<int64_t>((lanes + kBlock - 1) / kBlock, cap));
-}
-
 int pack_bytes(int32_t pack) { return pack == AB_RGB_PACK_16BE ? 6 : 3; }
-
-bool fits31(int64_t rows, int64_t cols) { return rows <= ((int64_t(1) << 31) - 1) / cols; }  // rows * cols < 2^31 (cols >= 1)
 
 int pack_check(ab_ctx *ctx, int32_t pack) {
     AB_CHECK(ctx, pack == AB_RGB_PACK_8 || pack == AB_RGB_PACK_8_ROUND || pack == AB_RGB_PACK_16BE, "unknown RGB packer %d", (int)pack);
     return AB_OK;
 }
-
-int plane_check(ab_ctx *ctx, const ab_plane *p, const char *what) {
-    AB_CHECK(ctx, p && p->data, "null %s plane", what);
-    AB_CHECK(ctx, p->rows >= 1 && p->cols >= 1, "the %s plane has a zero dimension (%lld x %lld)", what, (long long)p->rows, (long long)p->cols);
-    AB_CHECK(ctx, fits31(p->rows, p->cols), "the %s plane holds 2^31 pixels or more", what);
-    AB_CHECK(ctx, ((uintptr_t)p->data & 3u) == 0, "the %s plane is not float-aligned", what);
-    return AB_OK;
-}
-
-const char *const kChan[3] = {"R", "G", "B"};
-
-// three present channels of one size (render_rgb takes its dims from r, rgb.rs:13)
-int same_dims_check(ab_ctx *ctx, const ab_plane *const ch[3]) {
-    for (int c = 0; c < 3; ++c) AB_TRY(plane_check(ctx, ch[c], kChan[c]));
-    for (int c = 1; c < 3; ++c)
-        AB_CHECK(ctx, ch[c]->rows == ch[0]->rows && ch[c]->cols == ch[0]->cols, "the %s plane is %lld x %lld, R is %lld x %lld", kChan[c],
-                 (long long)ch[c]->rows, (long long)ch[c]->cols, (long long)ch[0]->rows, (long long)ch[0]->cols);
-    return AB_OK;
-}
-
-// a device output of `out_bytes` at `out` may not overlap a device plane
-int overlap_check(ab_ctx *ctx, const ab_plane *in, const void *out, size_t out_bytes, int32_t out_on_device) {
-    if (!in || !in->on_device || !out_on_device) return AB_OK;
-    const uintptr_t a = (uintptr_t)in->data, al = (uintptr_t)in->rows * (uintptr_t)in->cols * sizeof(float), b = (uintptr_t)out;
-    AB_CHECK(ctx, a + al <= b || b + out_bytes <= a, "an output overlaps an input plane");
-    return AB_OK;
-}
-
-struct Scope {  // releases / aborts everything registered with it when the entry point returns
-    ab_ctx *ctx;
-    std::vector<StagedPlane *> ins;  // the entry point's own (declared before the scope)
-    StagedOut outs[6];               // out_wb[3] and out_stretched[3]: they live here because the scope outlives process_device
-    int n_outs = 0, next_slot = 0;
-    explicit Scope(ab_ctx *c) : ctx(c) {}
-    ~Scope() {
-        for (int i = 0; i < n_outs; ++i) ab_stage_out_abort(ctx, &outs[i]);  // (a finished output owns nothing any more)
-        for (StagedPlane *p : ins) ab_stage_release(ctx, p);
-    }
-    int stage_out(const ab_plane_mut *p, StagedOut **o) {
-        AB_CHECK(ctx, n_outs < 6, "out of staged outputs");
-        *o = &outs[n_outs];
-        AB_TRY(ab_stage_out_begin(ctx, p, *o));
-        ++n_outs;
-        return AB_OK;
-    }
-    int alloc(float **p, int64_t n) {  // a plane for the length of the call, out of the context's scope slots (kept between calls)
-        AB_CHECK(ctx, next_slot < 8, "out of scope slots");
-        return ab_workspace(ctx, AB_WS_SCOPE0 + next_slot++, (size_t)n * sizeof(float), (void **)p);
-    }
-};
 
 template <int PACK>
 void launch_pack(ab_ctx *ctx, int grid, bool stf, const FinishArgs &a) {
@@ -255,7 +199,7 @@ int launch_finish(ab_ctx *ctx, FinishArgs a, int pack, bool stf) {
     if (pack != kPackNone) {
         const uintptr_t addr = (uintptr_t)a.out;
         if (pack_bytes(pack) == 3) {
-            a.head = (int64_t)((3 * ((4 - addr % 4) % 4)) % 4);  // 3 head = -addr (mod 4)
+            a.head = head_bytes(a.out, a.n);
         } else if (addr & 1u) {
             groups = false;  // 6 head + addr is odd for every head
         } else {
@@ -277,7 +221,7 @@ int launch_finish(ab_ctx *ctx, FinishArgs a, int pack, bool stf) {
     a.in16 = a.flat && (in_bits & 15u) == 0;
     a.wb16 = (wb_bits & 15u) == 0;
     a.st16 = (st_bits & 15u) == 0;
-    const int grid = grid_for(ctx, std::max<int64_t>(a.quads, a.n - 4 * a.quads));
+    const int grid = ab_stream_grid(ctx, std::max<int64_t>(a.quads, a.n - 4 * a.quads));
     switch (pack) {
         case AB_RGB_PACK_8: launch_pack<AB_RGB_PACK_8>(ctx, grid, stf, a); break;
         case AB_RGB_PACK_8_ROUND: launch_pack<AB_RGB_PACK_8_ROUND>(ctx, grid, stf, a); break;
@@ -328,17 +272,12 @@ int render_planes(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_pl
     AB_TRY(pack_check(ctx, pack));
     AB_CHECK(ctx, out, "null output");
     const size_t nbytes = (size_t)(r->rows * r->cols) * (size_t)pack_bytes(pack);
-    for (int c = 0; c < 3; ++c) AB_TRY(overlap_check(ctx, ch[c], out, nbytes, out_on_device));
+    AB_TRY(overlap_check(ctx, {device_span(*r), device_span(*g), device_span(*b)}, {device_span(out, nbytes, out_on_device)}));
     AB_HIP(ctx, hipSetDevice(ctx->device));
     AB_TRY(ab_cancel_point(ctx));
-    StagedPlane in[3];
     Scope sc(ctx);
     const float *d[3];
-    for (int c = 0; c < 3; ++c) {
-        AB_TRY(ab_stage_in(ctx, ch[c], &in[c]));
-        sc.ins.push_back(&in[c]);
-        d[c] = in[c].dptr;
-    }
+    for (int c = 0; c < 3; ++c) AB_TRY(sc.stage_in(ch[c], &d[c]));
     return render_device(ctx, d, r->rows, r->cols, stf, stats, pack, out, out_on_device);
 }
 
@@ -372,14 +311,12 @@ int process_device(ab_ctx *ctx, Scope &sc, const float *const d[3], const int64_
     info->rows = (uint64_t)rows;
     info->cols = (uint64_t)cols;
     // the white-balanced planes are materialised: in the caller's planes, else in scope slots
-    StagedOut *so_wb[3] = {nullptr, nullptr, nullptr}, *so_s[3] = {nullptr, nullptr, nullptr};
     float *wbp[3];
     for (int c = 0; c < 3; ++c) {
         if (out_wb) {
-            AB_TRY(sc.stage_out(&out_wb[c], &so_wb[c]));
-            wbp[c] = so_wb[c]->dptr;
+            AB_TRY(sc.stage_out(&out_wb[c], &wbp[c]));
         } else {
-            AB_TRY(sc.alloc(&wbp[c], n));
+            AB_TRY(sc.alloc((void **)&wbp[c], (size_t)n * sizeof(float)));
         }
     }
     // :54-74 the statistics of the cropped, unscaled planes (they want a contiguous plane: a channel cropped in its columns is gathered
@@ -428,8 +365,8 @@ int process_device(ab_ctx *ctx, Scope &sc, const float *const d[3], const int64_
     for (int c = 0; c < 3; ++c) AB_TRY(stats_of(c));
     if (cfg->auto_stretch && cfg->linked_stf) {  // :89-96
         float *comb = nullptr;
-        AB_TRY(sc.alloc(&comb, n));
-        hipLaunchKernelGGL(merge3_div_kernel, dim3(grid_for(ctx, n)), dim3(kBlock), 0, ctx->stream, wbp[0], wbp[1], wbp[2], n, comb);
+        AB_TRY(sc.alloc((void **)&comb, (size_t)n * sizeof(float)));
+        hipLaunchKernelGGL(merge3_div_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, wbp[0], wbp[1], wbp[2], n, comb);
         AB_HIP(ctx, hipGetLastError());
         ab_image_stats st;
         memset(&st, 0, sizeof st);
@@ -453,10 +390,7 @@ int process_device(ab_ctx *ctx, Scope &sc, const float *const d[3], const int64_
             fa.src[c] = wbp[c];
             fa.ld[c] = cols;
             fa.tx[c] = make_tx(&info->stf[c], &wbst[c]);
-            if (out_stretched) {
-                AB_TRY(sc.stage_out(&out_stretched[c], &so_s[c]));
-                fa.out_s[c] = so_s[c]->dptr;
-            }
+            if (out_stretched) AB_TRY(sc.stage_out(&out_stretched[c], &fa.out_s[c]));
         }
         if (cfg->has_scnr) {  // scnr.rs:28-31
             const float amount = cfg->scnr.amount < 0.0f ? 0.0f : (cfg->scnr.amount > 1.0f ? 1.0f : cfg->scnr.amount);
@@ -472,11 +406,7 @@ int process_device(ab_ctx *ctx, Scope &sc, const float *const d[3], const int64_
         AB_TRY(launch_finish(ctx, fa, out_rgb8 ? AB_RGB_PACK_8_ROUND : kPackNone, true));
         if (out_rgb8) AB_TRY(bytes_finish(ctx, out_rgb8, out_on_device, nbytes, fa.out));
     }
-    for (int c = 0; c < 3; ++c) {
-        if (so_wb[c]) AB_TRY(ab_stage_out_finish(ctx, so_wb[c]));
-        if (so_s[c]) AB_TRY(ab_stage_out_finish(ctx, so_s[c]));
-    }
-    return AB_OK;
+    return sc.finish_outs();
 }
 
 // the checks process_device relies on: output dims = the minimum per axis over the present channels, n < 2^31
@@ -538,23 +468,20 @@ int ab_export_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_pl
     AB_CHECK(ctx, fits31(rows, cols), "the output holds 2^31 pixels or more");
     const int64_t n = rows * cols;
     const size_t nbytes = (size_t)n * (size_t)pack_bytes(pack);
-    for (int c = 0; c < 3; ++c) AB_TRY(overlap_check(ctx, ch[c], out, nbytes, out_on_device));
+    AB_TRY(overlap_check(ctx, {device_span(*r), device_span(*g), device_span(*b)}, {device_span(out, nbytes, out_on_device)}));
     AB_HIP(ctx, hipSetDevice(ctx->device));
     AB_TRY(ab_cancel_point(ctx));
     memset(info, 0, sizeof *info);
     info->rows = (uint64_t)rows;
     info->cols = (uint64_t)cols;
-    StagedPlane in[3];
     Scope sc(ctx);
     const float *d[3];
     for (int c = 0; c < 3; ++c) {
-        AB_TRY(ab_stage_in(ctx, ch[c], &in[c]));
-        sc.ins.push_back(&in[c]);
-        d[c] = in[c].dptr;
+        AB_TRY(sc.stage_in(ch[c], &d[c]));
         if (ch[c]->rows != rows || ch[c]->cols != cols) {  // :399-405
             float *h = nullptr;
-            AB_TRY(sc.alloc(&h, n));
-            AB_TRY(ab_resample_device(ctx, in[c].dptr, ch[c]->rows, ch[c]->cols, rows, cols, h));
+            AB_TRY(sc.alloc((void **)&h, (size_t)n * sizeof(float)));
+            AB_TRY(ab_resample_device(ctx, d[c], ch[c]->rows, ch[c]->cols, rows, cols, h));
             d[c] = h;
             info->resampled = 1;
         }
@@ -585,24 +512,20 @@ int ab_process_drizzle_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, co
     }
     AB_TRY(process_check(ctx, rows_c, cols_c, present, cfg, out_stretched, out_wb, info));
     const size_t on = (size_t)info_dims(rows_c, cols_c, present);
-    for (int c = 0; c < 3; ++c) {
-        AB_TRY(overlap_check(ctx, ch[c], out_rgb8, on * 3, out_rgb8 ? out_on_device : 0));
-        for (int o = 0; o < 3; ++o) {
-            if (out_stretched) AB_TRY(overlap_check(ctx, ch[c], out_stretched[o].data, on * sizeof(float), out_stretched[o].on_device));
-            if (out_wb) AB_TRY(overlap_check(ctx, ch[c], out_wb[o].data, on * sizeof(float), out_wb[o].on_device));
-        }
+    std::vector<Span> ins;
+    for (int c = 0; c < 3; ++c)
+        if (present[c]) ins.push_back(device_span(*ch[c]));
+    AB_TRY(overlap_check(ctx, ins, {device_span(out_rgb8, on * 3, out_on_device)}));
+    for (int o = 0; o < 3; ++o) {
+        if (out_stretched) AB_TRY(overlap_check(ctx, ins, {device_span(out_stretched[o].data, on * sizeof(float), out_stretched[o].on_device)}));
+        if (out_wb) AB_TRY(overlap_check(ctx, ins, {device_span(out_wb[o].data, on * sizeof(float), out_wb[o].on_device)}));
     }
     AB_HIP(ctx, hipSetDevice(ctx->device));
     AB_TRY(ab_cancel_point(ctx));
-    StagedPlane in[3];
     Scope sc(ctx);
     const float *d[3] = {nullptr, nullptr, nullptr};
-    for (int c = 0; c < 3; ++c) {
-        if (!present[c]) continue;
-        AB_TRY(ab_stage_in(ctx, ch[c], &in[c]));
-        sc.ins.push_back(&in[c]);
-        d[c] = in[c].dptr;
-    }
+    for (int c = 0; c < 3; ++c)
+        if (present[c]) AB_TRY(sc.stage_in(ch[c], &d[c]));
     return process_device(ctx, sc, d, rows_c, cols_c, cfg, out_stretched, out_wb, out_rgb8, out_on_device, info);
 } AB_CATCH(ctx)
 

@@ -15,13 +15,13 @@
 // synthesised from the detections' own sky positions (:257-273), so the cross-match is the identity
 // whenever 0 < (pixel_scale * 3 / 3600)^2.  Header parsing (wcs.rs) stays with the caller.
 #include "ab_common.hpp"
+#include "entry_host.hpp"
 
 #include <algorithm>
 #include <cmath>
 
 namespace {
 
-constexpr int kBlock = 256;
 
 // synthesize_luminance (:185-196) and, in the same pass, the one number spcc_calibrate_rgb takes from compute_image_stats(luminance)
 // (:88-89): its maximum over the valid pixels (finite and above the padding threshold, stats.rs:10-13; 0 without any, :95-97).  A
@@ -223,24 +223,6 @@ int spcc_from_detection(ab_ctx *ctx, const float *r, const float *g, const float
     return AB_OK;
 }
 
-struct Staged3 {
-    StagedPlane p[3];
-    ab_ctx *ctx;
-    int n = 0;
-    explicit Staged3(ab_ctx *c) : ctx(c) {}
-    ~Staged3() {
-        for (int i = 0; i < n; ++i) ab_stage_release(ctx, &p[i]);
-    }
-    int stage(const ab_plane *r, const ab_plane *g, const ab_plane *b) {
-        const ab_plane *in[3] = {r, g, b};
-        for (int i = 0; i < 3; ++i) {
-            AB_TRY(ab_stage_in(ctx, in[i], &p[i]));
-            n = i + 1;
-        }
-        return AB_OK;
-    }
-};
-
 int check_planes(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b) {
     AB_CHECK(ctx, r && g && b, "null plane");
     AB_CHECK(ctx, g->rows == r->rows && g->cols == r->cols && b->rows == r->rows && b->cols == r->cols, "SPCC channels must share dims");
@@ -264,10 +246,12 @@ int ab_spcc_from_detection(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, co
     AB_CHECK(ctx, cfg && res && (stars || n_stars == 0), "null argument");
     AB_TRY(check_planes(ctx, r, g, b));
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    Staged3 st(ctx);
-    AB_TRY(st.stage(r, g, b));
+    Scope sc(ctx);
+    const ab_plane *ch[3] = {r, g, b};
+    const float *d[3];
+    for (int c = 0; c < 3; ++c) AB_TRY(sc.stage_in(ch[c], &d[c]));
     std::vector<ab_detected_star> v(stars, stars + n_stars);
-    return spcc_from_detection(ctx, st.p[0].dptr, st.p[1].dptr, st.p[2].dptr, r->rows, r->cols, v, lum_max, pixel_scale_arcsec, *cfg, res);
+    return spcc_from_detection(ctx, d[0], d[1], d[2], r->rows, r->cols, v, lum_max, pixel_scale_arcsec, *cfg, res);
 } AB_CATCH(ctx)
 
 int ab_spcc_calibrate_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, double pixel_scale_arcsec,
@@ -276,8 +260,10 @@ int ab_spcc_calibrate_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, con
     AB_CHECK(ctx, cfg && res, "null argument");
     AB_TRY(check_planes(ctx, r, g, b));
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    Staged3 st(ctx);
-    AB_TRY(st.stage(r, g, b));
+    Scope sc(ctx);
+    const ab_plane *ch[3] = {r, g, b};
+    const float *d[3];
+    for (int c = 0; c < 3; ++c) AB_TRY(sc.stage_in(ch[c], &d[c]));
     const int64_t h = r->rows, w = r->cols, n = h * w;
     float *lum = nullptr;
     AB_TRY(ab_workspace(ctx, AB_WS_SCOPE0, std::max<size_t>((size_t)n, 1) * sizeof(float), (void **)&lum));
@@ -289,7 +275,7 @@ int ab_spcc_calibrate_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, con
     if (n > 0) {
         AB_HIP(ctx, hipMemsetAsync(dmax, 0, sizeof(unsigned int), ctx->stream));
         const int grid = (int)std::min<int64_t>((n + kBlock - 1) / kBlock, (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8);
-        hipLaunchKernelGGL(spcc_luminance_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, st.p[0].dptr, st.p[1].dptr, st.p[2].dptr, n, lum, dmax);
+        hipLaunchKernelGGL(spcc_luminance_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, d[0], d[1], d[2], n, lum, dmax);
         if (hipGetLastError() != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "luminance launch failed");
         if (rc == AB_OK && hipMemcpyAsync(&bits, dmax, sizeof bits, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
             rc = ab_set_error(ctx, AB_ERR_HIP, "hipMemcpyAsync failed");
@@ -302,7 +288,7 @@ int ab_spcc_calibrate_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, con
     if (rc == AB_OK) rc = ab_detect_stars_device(ctx, lum, h, w, 5.0, &stars, &bm, &bs);  // :86
     (void)hipStreamSynchronize(ctx->stream);
     if (rc != AB_OK) return rc;
-    return spcc_from_detection(ctx, st.p[0].dptr, st.p[1].dptr, st.p[2].dptr, h, w, stars, lum_max, pixel_scale_arcsec, *cfg, res);
+    return spcc_from_detection(ctx, d[0], d[1], d[2], h, w, stars, lum_max, pixel_scale_arcsec, *cfg, res);
 } AB_CATCH(ctx)
 
 }  // extern "C"

@@ -96,19 +96,13 @@ __global__ __launch_bounds__(256) void copy_kernel(const float4 *__restrict__ sr
     }
 }
 
-int stream_grid(ab_ctx *ctx, int64_t n4) {
-    const int64_t want = (n4 + 255) / 256;
-    const int64_t cap = (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8;
-    return (int)std::max<int64_t>(1, std::min(want, cap));
-}
-
 }  // namespace
 
 int ab_stf_u8_device(ab_ctx *ctx, const float *in, int64_t n, const ab_stf_params *p, const ab_image_stats *st,
                      uint8_t *out) {
     AB_HIP(ctx, hipSetDevice(ctx->device));
     const int vec = ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 3) == 0;
-    hipLaunchKernelGGL(stf_u8_kernel, dim3(stream_grid(ctx, vec ? (n >> 2) : n)), dim3(256), 0, ctx->stream, in, n, make_tx(p, st), out, vec);
+    hipLaunchKernelGGL(stf_u8_kernel, dim3(ab_stream_grid(ctx, vec ? (n >> 2) : n)), dim3(256), 0, ctx->stream, in, n, make_tx(p, st), out, vec);
     AB_HIP(ctx, hipGetLastError());
     return AB_OK;
 }
@@ -116,7 +110,7 @@ int ab_stf_u8_device(ab_ctx *ctx, const float *in, int64_t n, const ab_stf_param
 int ab_stf_u8_device_tx(ab_ctx *ctx, const float *in, int64_t n, const void *tx_dev, uint8_t *out) {
     AB_HIP(ctx, hipSetDevice(ctx->device));
     const int vec = ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 3) == 0;
-    hipLaunchKernelGGL(stf_u8_tx_kernel, dim3(stream_grid(ctx, vec ? (n >> 2) : n)), dim3(256), 0, ctx->stream, in, n, (const StfTx *)tx_dev, out,
+    hipLaunchKernelGGL(stf_u8_tx_kernel, dim3(ab_stream_grid(ctx, vec ? (n >> 2) : n)), dim3(256), 0, ctx->stream, in, n, (const StfTx *)tx_dev, out,
                        vec);
     AB_HIP(ctx, hipGetLastError());
     return AB_OK;
@@ -126,7 +120,7 @@ int ab_stf_f32_device(ab_ctx *ctx, const float *in, int64_t n, const ab_stf_para
                       float *out) {
     AB_HIP(ctx, hipSetDevice(ctx->device));
     const int vec = (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
-    hipLaunchKernelGGL(stf_f32_kernel, dim3(stream_grid(ctx, vec ? (n >> 2) : n)), dim3(256), 0, ctx->stream, in, n, make_tx(p, st), out, vec);
+    hipLaunchKernelGGL(stf_f32_kernel, dim3(ab_stream_grid(ctx, vec ? (n >> 2) : n)), dim3(256), 0, ctx->stream, in, n, make_tx(p, st), out, vec);
     AB_HIP(ctx, hipGetLastError());
     return AB_OK;
 }
@@ -194,7 +188,7 @@ int ab_bench_copy(ab_ctx *ctx, const float *src_dev, float *dst_dev, size_t n_fl
     AB_CHECK(ctx, src_dev && dst_dev && (n_floats % 4) == 0, "copy needs 16-byte multiples");
     AB_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t n4 = (int64_t)(n_floats / 4);
-    hipLaunchKernelGGL(copy_kernel, dim3(stream_grid(ctx, (n4 + 3) / 4)), dim3(256), 0, ctx->stream, (const float4 *)src_dev,
+    hipLaunchKernelGGL(copy_kernel, dim3(ab_stream_grid(ctx, (n4 + 3) / 4)), dim3(256), 0, ctx->stream, (const float4 *)src_dev,
                        (float4 *)dst_dev, n4);
     AB_HIP(ctx, hipGetLastError());
     return AB_OK;

@@ -24,6 +24,7 @@
 // Compiled with -ffp-contract=off like everything else: each stage is the instruction sequence of the kernel it restates, so the
 // fused result is bit for bit what the library's own chain of entry points gives.
 #include "ab_common.hpp"
+#include "entry_host.hpp"
 #include "scnr_device.hpp"
 #include "stf_device.hpp"
 
@@ -32,7 +33,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kBlockCurves = 512;  // CURVES: twice the waves behind each 48 KiB copy of the LUTs
 constexpr int kLut = 4096;
 constexpr int kCurveGroupsPerCu = 3;  // 160 KiB of LDS per CU / the 48 KiB of three LUTs
@@ -55,12 +55,6 @@ struct ToneArgs {
     float *out_s[3] = {nullptr, nullptr, nullptr};  // all three or none
     uint8_t *out = nullptr;
 };
-
-// ((d as f64) * ratio).min((len - 1) as f64) as usize (helpers.rs:306, :309)
-__device__ __forceinline__ int64_t nn_index(int64_t d, double ratio, int64_t len) {
-    const double s = (double)d * ratio, hi = (double)(len - 1);
-    return (int64_t)(s < hi ? s : hi);
-}
 
 // where output pixel i is read from
 template <bool SAMPLED>
@@ -104,13 +98,6 @@ __device__ __forceinline__ void tone_px(const ToneArgs &a, const float *lut, flo
         v[c] = s;
     }
     if (a.scnr) scnr_px(v[0], v[1], v[2], a.method, a.amount, a.preserve);
-}
-
-// (v.clamp(0, 1) * 255f32) as u8: f32::clamp keeps a NaN, `as` truncates and sends NaN to 0 (helpers.rs:243-245)
-__device__ __forceinline__ uint32_t quantise(float s) {
-    const float c = s < 0.0f ? 0.0f : (s > 1.0f ? 1.0f : s);
-    const float x = c * 255.0f;
-    return x == x ? (uint32_t)x : 0u;
 }
 
 template <bool LEVELS, bool CURVES, bool SAMPLED>
@@ -251,38 +238,6 @@ int tone_plan(const ab_image_stats stats[3], const ab_tone_config *cfg, ab_tone_
 }
 
 // ---- host: checks, staging, launches -------------------------------------------------------------------------------------------
-const char *const kChan[3] = {"R", "G", "B"};
-
-bool fits31(int64_t rows, int64_t cols) { return rows <= ((int64_t(1) << 31) - 1) / cols; }  // rows * cols < 2^31 (cols >= 1)
-
-int plane_check(ab_ctx *ctx, const ab_plane *p, const char *what) {
-    AB_CHECK(ctx, p && p->data, "null %s plane", what);
-    AB_CHECK(ctx, p->rows >= 1 && p->cols >= 1, "the %s plane has a zero dimension (%lld x %lld)", what, (long long)p->rows, (long long)p->cols);
-    AB_CHECK(ctx, fits31(p->rows, p->cols), "the %s plane holds 2^31 pixels or more", what);
-    AB_CHECK(ctx, ((uintptr_t)p->data & 3u) == 0, "the %s plane is not float-aligned", what);
-    return AB_OK;
-}
-
-// a device output of `out_bytes` at `out` may not overlap a device plane
-int overlap_check(ab_ctx *ctx, const ab_plane *in, const void *out, size_t out_bytes, int32_t out_on_device) {
-    if (!in->on_device || !out_on_device || !out) return AB_OK;
-    const uintptr_t a = (uintptr_t)in->data, al = (uintptr_t)in->rows * (uintptr_t)in->cols * sizeof(float), b = (uintptr_t)out;
-    AB_CHECK(ctx, a + al <= b || b + out_bytes <= a, "an output overlaps an input plane");
-    return AB_OK;
-}
-
-struct Scope {  // releases / aborts everything registered with it when the entry point returns
-    ab_ctx *ctx;
-    StagedPlane ins[3];
-    StagedOut outs[3];
-    int n_ins = 0, n_outs = 0;
-    explicit Scope(ab_ctx *c) : ctx(c) {}
-    ~Scope() {
-        for (int i = 0; i < n_outs; ++i) ab_stage_out_abort(ctx, &outs[i]);  // (a finished output owns nothing any more)
-        for (int i = 0; i < n_ins; ++i) ab_stage_release(ctx, &ins[i]);
-    }
-};
-
 template <bool LEVELS, bool CURVES>
 void launch_sampled(ab_ctx *ctx, int grid, bool sampled, const ToneArgs &a) {
     constexpr int block = CURVES ? kBlockCurves : kBlock;
@@ -295,8 +250,7 @@ void launch_sampled(ab_ctx *ctx, int grid, bool sampled, const ToneArgs &a) {
 
 // places the groups by the byte output's address and launches; everything else in `a` is the caller's
 int launch_tone(ab_ctx *ctx, ToneArgs a, bool levels, bool curves, bool sampled) {
-    a.head = a.out ? (int64_t)((3 * ((4 - (uintptr_t)a.out % 4) % 4)) % 4) : 0;  // 3 head = -addr (mod 4)
-    a.head = std::min(a.head, a.n);
+    a.head = a.out ? head_bytes(a.out, a.n) : 0;
     a.quads = (a.n - a.head) / 4;
     uintptr_t in_bits = 0, st_bits = 0;
     for (int c = 0; c < 3; ++c) {
@@ -309,9 +263,7 @@ int launch_tone(ab_ctx *ctx, ToneArgs a, bool levels, bool curves, bool sampled)
     // a persistent, grid-strided launch: at most three workgroups per CU hold the LUTs' 48 KiB of LDS each, eight otherwise (sizing the
     // grid by the runtime's occupancy answer per kernel instead -- two per CU where the f64 pow's registers leave room for no more --
     // measured the same within the run-to-run spread, so the fixed counts of the other streaming kernels stay)
-    const int64_t cap = (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * (curves ? kCurveGroupsPerCu : 8);
-    const int block = curves ? kBlockCurves : kBlock;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((lanes + block - 1) / block, cap));
+    const int grid = ab_stream_grid(ctx, lanes, curves ? kBlockCurves : kBlock, curves ? kCurveGroupsPerCu : 8);
     if (levels && curves) {
         launch_sampled<true, true>(ctx, grid, sampled, a);
     } else if (levels) {
@@ -370,30 +322,21 @@ int ab_apply_tone_composite(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, c
                             int64_t max_dim, ab_plane_mut *out_planes, uint8_t *out_rgb8, int32_t out_on_device, ab_tone_info *info) try {
     if (!ctx) return AB_ERR_INVALID;
     const ab_plane *ch[3] = {r, g, b};
-    for (int c = 0; c < 3; ++c) AB_TRY(plane_check(ctx, ch[c], kChan[c]));
-    for (int c = 1; c < 3; ++c)  // (the command takes its dims from R, :80; its planes are one composite's)
-        AB_CHECK(ctx, ch[c]->rows == r->rows && ch[c]->cols == r->cols, "the %s plane is %lld x %lld, R is %lld x %lld", kChan[c], (long long)ch[c]->rows,
-                 (long long)ch[c]->cols, (long long)r->rows, (long long)r->cols);
+    AB_TRY(same_dims_check(ctx, ch));  // (the command takes its dims from R, :80; its planes are one composite's)
     AB_CHECK(ctx, stats && cfg, "null statistics or configuration");
     AB_CHECK(ctx, max_dim >= 1, "max_dim must be >= 1 (got %lld)", (long long)max_dim);
     AB_CHECK(ctx, out_planes || out_rgb8, "nothing to do: out_planes and out_rgb8 are both null");
     const int64_t rows = r->rows, cols = r->cols, n = rows * cols;
-    int64_t ph = rows, pw = cols;
-    AB_CHECK(ctx, ab_preview_dims(rows, cols, max_dim, &ph, &pw) == AB_OK, "the preview's dimensions could not be computed");
-    const bool above = ph != rows || pw != cols;  // the image exceeds max_dim: the preview is a pick (helpers.rs:283-290)
+    Preview pv;
+    AB_TRY(preview_of(ctx, rows, cols, max_dim, &pv));
+    const int64_t ph = pv.ph, pw = pv.pw;
+    const bool above = pv.sampled;
     const size_t nbytes = (size_t)(ph * pw) * 3;
-    if (out_planes) {
-        for (int c = 0; c < 3; ++c) {
-            AB_CHECK(ctx, out_planes[c].data, "null output %s plane", kChan[c]);
-            AB_CHECK(ctx, out_planes[c].rows == rows && out_planes[c].cols == cols, "the output %s plane must be %lld x %lld (got %lld x %lld)", kChan[c],
-                     (long long)rows, (long long)cols, (long long)out_planes[c].rows, (long long)out_planes[c].cols);
-            AB_CHECK(ctx, ((uintptr_t)out_planes[c].data & 3u) == 0, "the output %s plane is not float-aligned", kChan[c]);
-        }
-    }
-    for (int c = 0; c < 3; ++c) {
-        AB_TRY(overlap_check(ctx, ch[c], out_rgb8, nbytes, out_on_device));
-        for (int o = 0; out_planes && o < 3; ++o) AB_TRY(overlap_check(ctx, ch[c], out_planes[o].data, (size_t)n * sizeof(float), out_planes[o].on_device));
-    }
+    if (out_planes) AB_TRY(out_planes_check(ctx, out_planes, rows, cols));
+    const std::vector<Span> ins{device_span(*r), device_span(*g), device_span(*b)};
+    AB_TRY(overlap_check(ctx, ins, {device_span(out_rgb8, nbytes, out_on_device)}));
+    for (int o = 0; out_planes && o < 3; ++o)
+        AB_TRY(overlap_check(ctx, ins, {device_span(out_planes[o].data, (size_t)n * sizeof(float), out_planes[o].on_device)}));
     ab_tone_info plan;
     std::vector<float> lut(3 * kLut);
     {
@@ -409,9 +352,7 @@ int ab_apply_tone_composite(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, c
     ToneArgs a;
     a.rows = rows, a.cols = cols, a.n = n;
     for (int c = 0; c < 3; ++c) {
-        AB_TRY(ab_stage_in(ctx, ch[c], &sc.ins[c]));
-        ++sc.n_ins;
-        a.src[c] = sc.ins[c].dptr;
+        AB_TRY(sc.stage_in(ch[c], &a.src[c]));
         a.tx[c] = make_tx(&plan.stf[c], &plan.norm[c]);
         a.lev[c] = !levels_identity(cfg->levels[c]);
         if (a.lev[c]) {  // core/imaging/curves.rs:36-39
@@ -431,11 +372,7 @@ int ab_apply_tone_composite(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, c
         a.preserve = cfg->scnr.preserve_luminance;
     }
     if (out_planes) {
-        for (int c = 0; c < 3; ++c) {
-            AB_TRY(ab_stage_out_begin(ctx, &out_planes[c], &sc.outs[c]));
-            ++sc.n_outs;
-            a.out_s[c] = sc.outs[c].dptr;
-        }
+        for (int c = 0; c < 3; ++c) AB_TRY(sc.stage_out(&out_planes[c], &a.out_s[c]));
     }
     uint8_t *bytes_dev = nullptr;  // the caller's buffer, or the scratch arena for a host output (nothing below asks for scratch)
     if (out_rgb8) {
@@ -469,7 +406,7 @@ int ab_apply_tone_composite(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, c
         AB_HIP(ctx, hipMemcpyAsync(out_rgb8, bytes_dev, nbytes, hipMemcpyDeviceToHost, ctx->stream));
         AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
-    for (int c = 0; c < sc.n_outs; ++c) AB_TRY(ab_stage_out_finish(ctx, &sc.outs[c]));
+    AB_TRY(sc.finish_outs());
     if (info) *info = plan;
     return AB_OK;
 } AB_CATCH(ctx)

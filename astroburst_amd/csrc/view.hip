@@ -24,6 +24,7 @@
 // address allows it.  Persistent grids sized from the context's CU count.  -ffp-contract=off like everything else: each stage is the
 // instruction sequence of the kernel it restates, so bytes and bins equal the library's own unfused calls bit for bit.
 #include "ab_common.hpp"
+#include "entry_host.hpp"
 #include "stf_device.hpp"
 #include "view_hist.hpp"
 
@@ -32,7 +33,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 constexpr int kPerWaveMax = 1024;  // display bins up to which every wave owns a copy (4 x 4 KiB)
 constexpr int kLdsMax = 16384;     // ... up to which the workgroup owns one (64 KiB)
@@ -181,12 +181,6 @@ struct RgbArgs {
     HistArgs hist;
 };
 
-// ((d as f64) * ratio).min((len - 1) as f64) as usize (helpers.rs:306, :309)
-__device__ __forceinline__ int64_t nn_index(int64_t d, double ratio, int64_t len) {
-    const double s = (double)d * ratio, hi = (double)(len - 1);
-    return (int64_t)(s < hi ? s : hi);
-}
-
 template <bool SAMPLED>
 __device__ __forceinline__ int64_t source_of(const RgbArgs &a, int64_t i) {
     if constexpr (SAMPLED) {
@@ -196,13 +190,6 @@ __device__ __forceinline__ int64_t source_of(const RgbArgs &a, int64_t i) {
     } else {
         return i;
     }
-}
-
-// (v.clamp(0, 1) * 255f32) as u8: f32::clamp keeps a NaN, `as` truncates and sends NaN to 0 (helpers.rs:243-245)
-__device__ __forceinline__ uint32_t quantise(float s) {
-    const float c = s < 0.0f ? 0.0f : (s > 1.0f ? 1.0f : s);
-    const float x = c * 255.0f;
-    return x == x ? (uint32_t)x : 0u;
 }
 
 template <bool SAMPLED, bool HIST>
@@ -270,36 +257,6 @@ __global__ __launch_bounds__(kBlock) void view_rgb_kernel(const RgbArgs a) {
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-const char *const kChan[3] = {"R", "G", "B"};
-
-bool fits31(int64_t rows, int64_t cols) { return rows <= ((int64_t(1) << 31) - 1) / cols; }  // rows * cols < 2^31 (cols >= 1)
-
-int plane_check(ab_ctx *ctx, const ab_plane *p, const char *what) {
-    AB_CHECK(ctx, p && p->data, "null %s plane", what);
-    AB_CHECK(ctx, p->rows >= 1 && p->cols >= 1, "the %s plane has a zero dimension (%lld x %lld)", what, (long long)p->rows, (long long)p->cols);
-    AB_CHECK(ctx, fits31(p->rows, p->cols), "the %s plane holds 2^31 pixels or more", what);
-    AB_CHECK(ctx, ((uintptr_t)p->data & 3u) == 0, "the %s plane is not float-aligned", what);
-    return AB_OK;
-}
-
-// a device output of `out_bytes` at `out` may not overlap a device plane
-int overlap_check(ab_ctx *ctx, const ab_plane *in, const void *out, size_t out_bytes, int32_t out_on_device) {
-    if (!in->on_device || !out_on_device || !out) return AB_OK;
-    const uintptr_t a = (uintptr_t)in->data, al = (uintptr_t)in->rows * (uintptr_t)in->cols * sizeof(float), b = (uintptr_t)out;
-    AB_CHECK(ctx, a + al <= b || b + out_bytes <= a, "an output overlaps an input plane");
-    return AB_OK;
-}
-
-struct Staged {  // releases the staged input planes when the entry point returns
-    ab_ctx *ctx;
-    StagedPlane ins[3];
-    int n = 0;
-    explicit Staged(ab_ctx *c) : ctx(c) {}
-    ~Staged() {
-        for (int i = 0; i < n; ++i) ab_stage_release(ctx, &ins[i]);
-    }
-};
-
 struct ViewWs {  // carved from AB_WS_VIEW
     unsigned int *src_bins;  // the 65 536 bins of the two-step route
     unsigned int *out_bins;  // up to 65 536 display bins on their way to a host output
@@ -367,20 +324,15 @@ int hist_finish(ab_ctx *ctx, const HistPlan &p, const ViewWs &w, unsigned int *o
     return AB_OK;
 }
 
-int persistent_grid(ab_ctx *ctx, int64_t lanes) {
-    const int64_t cap = (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8;
-    return (int)std::max<int64_t>(1, std::min<int64_t>((lanes + kBlock - 1) / kBlock, cap));
-}
-
 // one pass over a plane: the apply_stf bytes (tx_dev, out; both or neither) and / or the histogram (hist nullable)
 int launch_mono(ab_ctx *ctx, const float *src, int64_t n, const StfTx *tx_dev, uint8_t *out, const HistArgs *hist, size_t lds_bytes) {
     MonoArgs a;
     a.src = src, a.n = n, a.tx_dev = tx_dev, a.out = out;
-    a.head = std::min<int64_t>(n, (int64_t)(((16 - (uintptr_t)src % 16) % 16) / sizeof(float)));
+    a.head = head16(src, n);
     a.quads = (n - a.head) / 4;
     a.out4 = out && ((uintptr_t)(out + a.head) & 3u) == 0;
     if (hist) a.hist = *hist;
-    const int grid = persistent_grid(ctx, std::max<int64_t>(a.quads, n - 4 * a.quads));
+    const int grid = ab_stream_grid(ctx, std::max<int64_t>(a.quads, n - 4 * a.quads));
     if (out && hist) {
         hipLaunchKernelGGL((view_mono_kernel<true, true>), dim3(grid), dim3(kBlock), lds_bytes, ctx->stream, a);
     } else if (out) {
@@ -393,14 +345,13 @@ int launch_mono(ab_ctx *ctx, const float *src, int64_t n, const StfTx *tx_dev, u
 }
 
 int launch_rgb(ab_ctx *ctx, RgbArgs a, bool sampled, const HistArgs *hist, size_t lds_bytes) {
-    a.head = (int64_t)((3 * ((4 - (uintptr_t)a.out % 4) % 4)) % 4);  // 3 head = -addr (mod 4)
-    a.head = std::min(a.head, a.n);
+    a.head = head_bytes(a.out, a.n);
     a.quads = (a.n - a.head) / 4;
     uintptr_t in_bits = 0;
     for (int c = 0; c < 3; ++c) in_bits |= (uintptr_t)(a.src[c] + a.head);
     a.in16 = !sampled && (in_bits & 15u) == 0;
     if (hist) a.hist = *hist;
-    const int grid = persistent_grid(ctx, std::max<int64_t>(a.quads, a.n - 4 * a.quads));
+    const int grid = ab_stream_grid(ctx, std::max<int64_t>(a.quads, a.n - 4 * a.quads));
     if (sampled) {
         hipLaunchKernelGGL((view_rgb_kernel<true, false>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
     } else if (hist) {
@@ -460,19 +411,19 @@ int ab_display_histogram(ab_ctx *ctx, const ab_plane *img, double dmin, double d
     AB_CHECK(ctx, out_bins, "null output");
     AB_CHECK(ctx, target_bins >= 1, "target_bins must be >= 1");
     const HistPlan plan = plan_hist(target_bins);
-    AB_TRY(overlap_check(ctx, img, out_bins, plan.out_len * sizeof(uint32_t), out_on_device));
+    AB_TRY(overlap_check(ctx, {device_span(*img)}, {device_span(out_bins, plan.out_len * sizeof(uint32_t), out_on_device)}));
     AB_HIP(ctx, hipSetDevice(ctx->device));
     AB_TRY(ab_cancel_point(ctx));
-    Staged sg(ctx);
-    AB_TRY(ab_stage_in(ctx, img, &sg.ins[0]));
-    sg.n = 1;
+    Scope sc(ctx);
+    const float *src = nullptr;
+    AB_TRY(sc.stage_in(img, &src));
     ViewWs w;
     AB_TRY(carve(ctx, &w));
     unsigned int *out_dev = out_on_device ? out_bins : w.out_bins;
     HistArgs h;
     h.dmin = dmin, h.dmax = dmax;
     AB_TRY(hist_prepare(ctx, plan, w, out_dev, &h));
-    AB_TRY(launch_mono(ctx, sg.ins[0].dptr, img->rows * img->cols, nullptr, nullptr, &h, plan.lds_bytes));
+    AB_TRY(launch_mono(ctx, src, img->rows * img->cols, nullptr, nullptr, &h, plan.lds_bytes));
     AB_TRY(hist_finish(ctx, plan, w, out_dev));
     if (!out_on_device) {
         AB_HIP(ctx, hipMemcpyAsync(out_bins, out_dev, plan.out_len * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -496,13 +447,13 @@ int ab_process_fits_view(ab_ctx *ctx, const ab_plane *img, const ab_fits_view_co
     AB_CHECK(ctx, cfg->hist_bins == 0 || out_bins, "hist_bins is %zu and out_bins is null", cfg->hist_bins);
     const int64_t n = img->rows * img->cols;
     const HistPlan plan = plan_hist(cfg->hist_bins);
-    AB_TRY(overlap_check(ctx, img, out_u8, (size_t)n, out_on_device));
-    if (plan.route != ROUTE_NONE) AB_TRY(overlap_check(ctx, img, out_bins, plan.out_len * sizeof(uint32_t), bins_on_device));
+    AB_TRY(overlap_check(ctx, {device_span(*img)}, {device_span(out_u8, (size_t)n, out_on_device)}));
+    AB_TRY(overlap_check(ctx, {device_span(*img)}, {device_span(out_bins, plan.out_len * sizeof(uint32_t), bins_on_device)}));  // (no bins: no bytes)
     AB_HIP(ctx, hipSetDevice(ctx->device));
     AB_TRY(ab_cancel_point(ctx));
-    Staged sg(ctx);
-    AB_TRY(ab_stage_in(ctx, img, &sg.ins[0]));
-    sg.n = 1;
+    Scope sc(ctx);
+    const float *src = nullptr;
+    AB_TRY(sc.stage_in(img, &src));
     ViewWs w;
     AB_TRY(carve(ctx, &w));
     uint8_t *bytes_dev = out_u8;  // the caller's buffer, or the scratch arena for a host output (the statistics chain asks for none)
@@ -510,12 +461,12 @@ int ab_process_fits_view(ab_ctx *ctx, const ab_plane *img, const ab_fits_view_co
     const ab_image_stats *res = nullptr;
     const void *tx = nullptr;
     const ab_stf_params *stf = nullptr;
-    AB_TRY(ab_stats_enqueue(ctx, nullptr, sg.ins[0].dptr, n, n, 0, 0.0, 0.0, &cfg->stf, &res, &tx, &stf));
+    AB_TRY(ab_stats_enqueue(ctx, nullptr, src, n, n, 0, 0.0, 0.0, &cfg->stf, &res, &tx, &stf));
     unsigned int *bins_dev = bins_on_device ? out_bins : w.out_bins;
     HistArgs h;
     h.st_dev = res;
     if (plan.route != ROUTE_NONE) AB_TRY(hist_prepare(ctx, plan, w, bins_dev, &h));
-    AB_TRY(launch_mono(ctx, sg.ins[0].dptr, n, (const StfTx *)tx, bytes_dev, plan.route != ROUTE_NONE ? &h : nullptr, plan.lds_bytes));
+    AB_TRY(launch_mono(ctx, src, n, (const StfTx *)tx, bytes_dev, plan.route != ROUTE_NONE ? &h : nullptr, plan.lds_bytes));
     AB_TRY(hist_finish(ctx, plan, w, bins_dev));
     char *pin = nullptr;
     bool wait = false;
@@ -548,27 +499,24 @@ int ab_process_rgb_fits_view(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, 
                              uint8_t *out_rgb8, int32_t out_on_device, uint32_t *out_bins, int32_t bins_on_device, ab_rgb_fits_view_info *info) try {
     if (!ctx) return AB_ERR_INVALID;
     const ab_plane *ch[3] = {r, g, b};
-    for (int c = 0; c < 3; ++c) AB_TRY(plane_check(ctx, ch[c], kChan[c]));
-    for (int c = 1; c < 3; ++c)  // (the command takes its dims from R, cmd/io/mod.rs:56)
-        AB_CHECK(ctx, ch[c]->rows == r->rows && ch[c]->cols == r->cols, "the %s plane is %lld x %lld, R is %lld x %lld", kChan[c], (long long)ch[c]->rows,
-                 (long long)ch[c]->cols, (long long)r->rows, (long long)r->cols);
+    AB_TRY(same_dims_check(ctx, ch));  // (the command takes its dims from R, cmd/io/mod.rs:56)
     AB_CHECK(ctx, cfg, "null configuration");
     AB_CHECK(ctx, max_dim >= 1, "max_dim must be >= 1 (got %lld)", (long long)max_dim);
     AB_CHECK(ctx, out_rgb8 || cfg->hist_bins > 0, "nothing to do: out_rgb8 is null and hist_bins is 0");
     AB_CHECK(ctx, cfg->hist_bins == 0 || out_bins, "hist_bins is %zu and out_bins is null", cfg->hist_bins);
     const int64_t rows = r->rows, cols = r->cols, n = rows * cols;
-    int64_t ph = rows, pw = cols;
-    AB_CHECK(ctx, ab_preview_dims(rows, cols, max_dim, &ph, &pw) == AB_OK, "the preview's dimensions could not be computed");
-    const bool above = ph != rows || pw != cols;  // the image exceeds max_dim: the preview is a pick (helpers.rs:283-290)
+    Preview pv;
+    AB_TRY(preview_of(ctx, rows, cols, max_dim, &pv));
+    const int64_t ph = pv.ph, pw = pv.pw;
+    const bool above = pv.sampled;
     const size_t nbytes = (size_t)(ph * pw) * 3;
     const HistPlan plan = plan_hist(cfg->hist_bins);
-    for (int c = 0; c < 3; ++c) {
-        AB_TRY(overlap_check(ctx, ch[c], out_rgb8, nbytes, out_on_device));
-        if (plan.route != ROUTE_NONE) AB_TRY(overlap_check(ctx, ch[c], out_bins, plan.out_len * sizeof(uint32_t), bins_on_device));
-    }
+    const std::vector<Span> ins{device_span(*r), device_span(*g), device_span(*b)};
+    AB_TRY(overlap_check(ctx, ins, {device_span(out_rgb8, nbytes, out_on_device)}));
+    AB_TRY(overlap_check(ctx, ins, {device_span(out_bins, plan.out_len * sizeof(uint32_t), bins_on_device)}));  // (no bins: no bytes)
     AB_HIP(ctx, hipSetDevice(ctx->device));
     AB_TRY(ab_cancel_point(ctx));
-    Staged sg(ctx);
+    Scope sc(ctx);
     ViewWs w;
     AB_TRY(carve(ctx, &w));
     uint8_t *bytes_dev = out_rgb8;
@@ -576,9 +524,7 @@ int ab_process_rgb_fits_view(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, 
     RgbArgs a;
     a.rows = rows, a.cols = cols, a.n = n, a.chan = w.chan, a.out = bytes_dev;
     for (int c = 0; c < 3; ++c) {  // cmd/io/mod.rs:44-50, one chain per channel; its result leaves the state block before the next
-        AB_TRY(ab_stage_in(ctx, ch[c], &sg.ins[c]));
-        ++sg.n;
-        a.src[c] = sg.ins[c].dptr;
+        AB_TRY(sc.stage_in(ch[c], &a.src[c]));
         const ab_image_stats *res = nullptr;
         const void *tx = nullptr;
         const ab_stf_params *stf = nullptr;

@@ -6,7 +6,7 @@
 // (dst = ((n as f64) * scale).round().max(1.0), scale = max_dim / max(width, height), cmd/common.rs:162-164; both kept when both fit,
 // :158-160) are cmd/helpers.rs:285-287's rule, which render.hip's preview_dims restates: ab_preview_dims gives a mono preview's dims
 // as it gives a composite's.  Its pick, ((d as f64) * ratio).min((n - 1) as f64) as usize with ratio = n as f64 / dst as f64
-// (:166-176), is wizard_host.hpp's nn_index.
+// (:166-176), is entry_host.hpp's nn_index.
 //   mono_preview_kernel  one or two planes of one size, each with its own transform (read from HBM, where the statistics chain left it)
 //                        and its own output.  SAMPLED: a lane owns one output byte; a workgroup walks preview rows, the source row is
 //                        found once per row (uniform), the source column once per lane for all its rows.  Not SAMPLED (every pixel is
@@ -24,7 +24,7 @@
 #include "ab_common.hpp"
 #include "background_device.hpp"
 #include "stf_device.hpp"
-#include "wizard_host.hpp"
+#include "entry_host.hpp"
 
 #include <cmath>
 
@@ -161,18 +161,13 @@ __global__ __launch_bounds__(kBlock) void mono_preview_kernel(const PreviewArgs 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
 const ab_auto_stf_config kStfDefault = {0.25, -2.8};  // AutoStfConfig::default() (types/image.rs:52-65; common.rs:18-22)
 
-struct Preview {  // the preview of ab_preview_dims
-    int64_t ph = 0, pw = 0;
-    bool sampled = false;  // the image exceeds max_dim: the preview is a pick (cmd/common.rs:158-160)
-};
-
 // one launch for a.planes planes; a.src / a.tx / a.out are set
 int launch_preview(ab_ctx *ctx, PreviewArgs a, int64_t rows, int64_t cols, const Preview &pv) {
     a.rows = rows, a.cols = cols, a.n = rows * cols;
     if (pv.sampled) {
         a.ph = pv.ph, a.pw = pv.pw;
         a.y_ratio = (double)rows / (double)pv.ph, a.x_ratio = (double)cols / (double)pv.pw;
-        const int64_t gx = (pv.pw + kBlock - 1) / kBlock, cap = (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8;
+        const int64_t gx = (pv.pw + kBlock - 1) / kBlock, cap = ab_stream_cap(ctx);
         const int64_t gy = std::max<int64_t>(1, std::min<int64_t>(pv.ph, (cap + gx - 1) / gx));
         hipLaunchKernelGGL(mono_preview_kernel<true>, dim3((unsigned)gx, (unsigned)gy), dim3(kBlock), 0, ctx->stream, a);
     } else {
@@ -183,7 +178,7 @@ int launch_preview(ab_ctx *ctx, PreviewArgs a, int64_t rows, int64_t cols, const
             if (((uintptr_t)(a.src[p] + a.head[p]) & 15u) == 0) a.vec |= 1 << p;
             lanes = std::max<int64_t>(lanes, std::max<int64_t>(a.quads[p], a.n - 4 * a.quads[p]));
         }
-        hipLaunchKernelGGL(mono_preview_kernel<false>, dim3(persistent_grid(ctx, lanes)), dim3(kBlock), 0, ctx->stream, a);
+        hipLaunchKernelGGL(mono_preview_kernel<false>, dim3(ab_stream_grid(ctx, lanes)), dim3(kBlock), 0, ctx->stream, a);
     }
     AB_HIP(ctx, hipGetLastError());
     return AB_OK;
@@ -208,20 +203,13 @@ int carve(ab_ctx *ctx, size_t bytes_each, bool want_model, int64_t n, Carved *w)
     return AB_OK;
 }
 
-int preview_of(ab_ctx *ctx, int64_t rows, int64_t cols, int64_t max_dim, Preview *pv) {
-    AB_CHECK(ctx, max_dim >= 1, "max_dim must be >= 1 (got %lld)", (long long)max_dim);
-    AB_CHECK(ctx, ab_preview_dims(rows, cols, max_dim, &pv->ph, &pv->pw) == AB_OK, "the preview's dimensions could not be computed");
-    pv->sampled = pv->ph != rows || pv->pw != cols;
-    return AB_OK;
-}
-
 // plane_select.hip keeps its three 2048-bin histograms at the start of the context's pinned buffer; the model's range words land
 // behind them, so the median's first synchronisation delivers both
 constexpr size_t kSelectPinned = 3 * 2048 * sizeof(unsigned int);
 
 template <int DEG>
 void launch_model(ab_ctx *ctx, const PolyArgs &pa, float *model, int pow2_cols, double inv_cols, BgState *st) {
-    const int64_t gx = ((int64_t)pa.cols + kPolyBlock * kPolyPx - 1) / (kPolyBlock * kPolyPx), cap = (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8;
+    const int64_t gx = ((int64_t)pa.cols + kPolyBlock * kPolyPx - 1) / (kPolyBlock * kPolyPx), cap = ab_stream_cap(ctx);
     const int64_t gy = std::max<int64_t>(1, std::min<int64_t>(pa.rows, (cap + gx - 1) / gx));
     hipLaunchKernelGGL(model_range_kernel<DEG>, dim3((unsigned)gx, (unsigned)gy), dim3(kPolyBlock), 0, ctx->stream, pa, model, pow2_cols, inv_cols, st);
 }
@@ -236,7 +224,8 @@ int ab_auto_stretch_preview_sampled(ab_ctx *ctx, const ab_plane *img, const ab_a
     AB_TRY(plane_check(ctx, img, "image"));
     AB_CHECK(ctx, out_u8, "null output bytes");
     const int64_t rows = img->rows, cols = img->cols, n = rows * cols;
-    Preview pv;
+    AB_CHECK(ctx, max_dim >= 1, "max_dim must be >= 1 (got %lld)", (long long)max_dim);
+    Preview pv;  // (the image exceeds max_dim: the preview is a pick, cmd/common.rs:158-160)
     AB_TRY(preview_of(ctx, rows, cols, max_dim, &pv));
     const size_t nbytes = (size_t)(pv.ph * pv.pw);
     {
@@ -250,7 +239,6 @@ int ab_auto_stretch_preview_sampled(ab_ctx *ctx, const ab_plane *img, const ab_a
     Carved w;
     AB_TRY(carve(ctx, out_on_device ? 0 : nbytes, false, n, &w));
     PreviewArgs a;
-    sc.ins.reserve(1);
     AB_TRY(sc.stage_in(img, &a.src[0]));
     const ab_image_stats *res = nullptr;
     const void *tx = nullptr;
@@ -293,7 +281,8 @@ int ab_background_step(ab_ctx *ctx, const ab_plane *img, const ab_background_con
                  (long long)cols, (long long)outs_p[k]->rows, (long long)outs_p[k]->cols);
         AB_CHECK(ctx, ((uintptr_t)outs_p[k]->data & 3u) == 0, "the %s plane is not float-aligned", what[k]);
     }
-    Preview pv;
+    AB_CHECK(ctx, max_dim >= 1, "max_dim must be >= 1 (got %lld)", (long long)max_dim);
+    Preview pv;  // (the image exceeds max_dim: the preview is a pick, cmd/common.rs:158-160)
     AB_TRY(preview_of(ctx, rows, cols, max_dim, &pv));
     const size_t nbytes = (size_t)(pv.ph * pv.pw);
     {
@@ -314,7 +303,6 @@ int ab_background_step(ab_ctx *ctx, const ab_plane *img, const ab_background_con
     char *pin = nullptr;  // (the largest request first: the buffer is not reallocated under the copies below)
     AB_TRY(ab_pinned(ctx, kSelectPinned + std::max(sizeof(BgState), (size_t)64), (void **)&pin));
     const float *src = nullptr;
-    sc.ins.reserve(1);
     AB_TRY(sc.stage_in(img, &src));
 
     // 1. sampling and fit: ab_extract_background's (ticks 1 and 2, its cancel points and errors)
@@ -337,8 +325,7 @@ int ab_background_step(ab_ctx *ctx, const ab_plane *img, const ab_background_con
     AB_TRY(ab_progress(ctx, "generating model", 3, 4));  // background.rs:88-93
     float *model = w.model;
     if (out_model) {
-        AB_TRY(ab_stage_out_begin(ctx, out_model, &sc.outs[sc.n_outs]));
-        model = sc.outs[sc.n_outs++].dptr;
+        AB_TRY(sc.stage_out(out_model, &model));
     }
     AB_HIP(ctx, hipMemsetAsync(w.st, 0, 4 * sizeof(unsigned int), ctx->stream));
     {
@@ -369,9 +356,9 @@ int ab_background_step(ab_ctx *ctx, const ab_plane *img, const ab_background_con
 
     // 3. the correction
     AB_TRY(ab_progress(ctx, "applying correction", 4, 4));  // background.rs:97-99
-    AB_TRY(ab_stage_out_begin(ctx, out_corrected, &sc.outs[sc.n_outs]));
-    float *corrected = sc.outs[sc.n_outs++].dptr;
-    hipLaunchKernelGGL(correct_kernel, dim3(persistent_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, src, model, n, (int)cfg->mode, model_median, corrected);
+    float *corrected = nullptr;
+    AB_TRY(sc.stage_out(out_corrected, &corrected));
+    hipLaunchKernelGGL(correct_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, src, model, n, (int)cfg->mode, model_median, corrected);
     AB_HIP(ctx, hipGetLastError());
 
     // 4. the statistics, once each: the corrected plane's (what :53 and :73 both compute), then the model's with its range known
@@ -412,11 +399,7 @@ int ab_background_step(ab_ctx *ctx, const ab_plane *img, const ab_background_con
             AB_HIP(ctx, hipMemcpyAsync(u8_out[k], u8_dev[k], nbytes, hipMemcpyDeviceToHost, ctx->stream));
             wait = true;
         }
-    for (int c = 0; c < sc.n_outs; ++c)  // (the scope frees the staging buffers)
-        if (sc.outs[c].owned) {
-            AB_HIP(ctx, hipMemcpyAsync(sc.outs[c].host, sc.outs[c].dptr, sc.outs[c].bytes, hipMemcpyDeviceToHost, ctx->stream));
-            wait = true;
-        }
+    AB_TRY(sc.enqueue_host_outs(&wait));
     if (wait) AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (info) {
         BgState st;

@@ -23,7 +23,7 @@
 #include "ab_common.hpp"
 #include "scnr_device.hpp"
 #include "stf_device.hpp"
-#include "wizard_host.hpp"
+#include "entry_host.hpp"
 
 #include <cfloat>
 #include <cmath>
@@ -190,12 +190,12 @@ __global__ __launch_bounds__(kBlock) void preview_stf_kernel(const PreviewArgs a
 const ab_auto_stf_config kStfDefault = {0.25, -2.8};  // AutoStfConfig::default() (types/image.rs:52-65; color.rs:163, blend.rs:200)
 
 int launch_wb(ab_ctx *ctx, WbArgs a, bool scnr) {
-    a.head = std::min<int64_t>(a.n, (int64_t)(((16 - (uintptr_t)a.src[0] % 16) % 16) / sizeof(float)));
+    a.head = head16(a.src[0], a.n);
     a.quads = (a.n - a.head) / 4;
     uintptr_t bits = 0;
     for (int c = 0; c < 3; ++c) bits |= (uintptr_t)(a.src[c] + a.head) | (uintptr_t)(a.out[c] + a.head);
     const bool vec = (bits & 15u) == 0;
-    const int grid = persistent_grid(ctx, std::max<int64_t>(a.quads, a.n - 4 * a.quads));
+    const int grid = ab_stream_grid(ctx, std::max<int64_t>(a.quads, a.n - 4 * a.quads));
     if (scnr && vec) {
         hipLaunchKernelGGL((wb_scnr_kernel<true, true>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
     } else if (scnr) {
@@ -210,12 +210,11 @@ int launch_wb(ab_ctx *ctx, WbArgs a, bool scnr) {
 }
 
 int launch_preview(ab_ctx *ctx, PreviewArgs a, bool sampled) {
-    a.head = (int64_t)((3 * ((4 - (uintptr_t)a.out % 4) % 4)) % 4);  // 3 head = -addr (mod 4)
-    a.head = std::min(a.head, a.n);
+    a.head = head_bytes(a.out, a.n);
     a.quads = (a.n - a.head) / 4;
     for (int c = 0; c < 3 && !sampled; ++c)
         if (((uintptr_t)(a.src[c] + a.head) & 15u) == 0) a.in16 |= 1 << c;
-    const int grid = persistent_grid(ctx, std::max<int64_t>(a.quads, a.n - 4 * a.quads));
+    const int grid = ab_stream_grid(ctx, std::max<int64_t>(a.quads, a.n - 4 * a.quads));
     if (sampled) {
         hipLaunchKernelGGL(preview_stf_kernel<true>, dim3(grid), dim3(kBlock), 0, ctx->stream, a);
     } else {
@@ -251,7 +250,8 @@ void color_plan(uint64_t n, const ab_image_stats st[3], const double factors[3],
 // The common tail of the two commands over three device planes: the statistics (known == nullptr: compute_image_stats x 3), the linked
 // STF, the preview, the one synchronisation and info's common fields.  outs: the staged output planes behind `planes`.
 struct Tail {
-    int64_t rows, cols, ph, pw;
+    int64_t rows, cols;
+    Preview pv;
     uint8_t *out_rgb8;
     int32_t out_on_device;
     bool want_info;
@@ -260,7 +260,7 @@ struct Tail {
 
 int run_tail(ab_ctx *ctx, Scope &sc, WizState *ws, const ab_color_plan *known, Tail *t) {
     const int64_t n = t->rows * t->cols;
-    const float *planes[3] = {sc.outs[0].dptr, sc.outs[1].dptr, sc.outs[2].dptr};
+    const float *planes[3] = {sc.outs[0].dptr, sc.outs[1].dptr, sc.outs[2].dptr};  // (the step's three planes are staged first)
     for (int c = 0; c < 3; ++c) {
         const ab_image_stats *res = nullptr;
         const bool use_known = known && known->route[c] == AB_COLOR_STATS_KNOWN_RANGE;
@@ -271,19 +271,18 @@ int run_tail(ab_ctx *ctx, Scope &sc, WizState *ws, const ab_color_plan *known, T
     }
     hipLaunchKernelGGL(linked_stf_kernel, dim3(1), dim3(64), 0, ctx->stream, ws, kStfDefault);
     AB_HIP(ctx, hipGetLastError());
-    const size_t nbytes = (size_t)(t->ph * t->pw) * 3;
+    const size_t nbytes = (size_t)(t->pv.ph * t->pv.pw) * 3;
     uint8_t *bytes_dev = t->out_rgb8;  // the caller's buffer, or the scratch arena for a host output (the statistics chain asks for none)
     if (t->out_rgb8) {
         if (!t->out_on_device) AB_TRY(ab_scratch(ctx, nbytes, (void **)&bytes_dev));
         PreviewArgs a;
         a.rows = t->rows, a.cols = t->cols, a.n = n, a.tx = ws->tx, a.out = bytes_dev;
         for (int c = 0; c < 3; ++c) a.src[c] = planes[c];
-        const bool above = t->ph != t->rows || t->pw != t->cols;  // the image exceeds max_dim: the preview is a pick (helpers.rs:282-289)
-        if (above) {
-            a.n = t->ph * t->pw, a.pw = t->pw;
-            a.y_ratio = (double)t->rows / (double)t->ph, a.x_ratio = (double)t->cols / (double)t->pw;
+        if (t->pv.sampled) {
+            a.n = t->pv.ph * t->pv.pw, a.pw = t->pv.pw;
+            a.y_ratio = (double)t->rows / (double)t->pv.ph, a.x_ratio = (double)t->cols / (double)t->pv.pw;
         }
-        AB_TRY(launch_preview(ctx, a, above));
+        AB_TRY(launch_preview(ctx, a, t->pv.sampled));
     }
     char *pin = nullptr;
     bool wait = false;
@@ -296,11 +295,7 @@ int run_tail(ab_ctx *ctx, Scope &sc, WizState *ws, const ab_color_plan *known, T
         AB_HIP(ctx, hipMemcpyAsync(t->out_rgb8, bytes_dev, nbytes, hipMemcpyDeviceToHost, ctx->stream));
         wait = true;
     }
-    for (int c = 0; c < sc.n_outs; ++c)
-        if (sc.outs[c].owned) {  // a host plane: its copy joins the one synchronisation (the scope frees the staging buffer)
-            AB_HIP(ctx, hipMemcpyAsync(sc.outs[c].host, sc.outs[c].dptr, sc.outs[c].bytes, hipMemcpyDeviceToHost, ctx->stream));
-            wait = true;
-        }
+    AB_TRY(sc.enqueue_host_outs(&wait));
     if (wait) AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (t->want_info) memcpy(&t->result, pin, sizeof t->result);
     return AB_OK;
@@ -347,21 +342,18 @@ int ab_calibrate_and_scnr(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, con
                           ab_color_step_info *info) try {
     if (!ctx) return AB_ERR_INVALID;
     const ab_plane *ch[3] = {r, g, b};
-    for (int c = 0; c < 3; ++c) AB_TRY(plane_check(ctx, ch[c], kChan[c]));
-    for (int c = 1; c < 3; ++c)  // (the planes of one composite)
-        AB_CHECK(ctx, ch[c]->rows == r->rows && ch[c]->cols == r->cols, "the %s plane is %lld x %lld, R is %lld x %lld", kChan[c], (long long)ch[c]->rows,
-                 (long long)ch[c]->cols, (long long)r->rows, (long long)r->cols);
+    AB_TRY(same_dims_check(ctx, ch));  // (the planes of one composite)
     AB_CHECK(ctx, orig_stats && factors, "null statistics or factors");
     AB_CHECK(ctx, !has_scnr || scnr, "has_scnr is set and the SCNR configuration is null");
     AB_CHECK(ctx, max_dim >= 1, "max_dim must be >= 1 (got %lld)", (long long)max_dim);
     const int64_t rows = r->rows, cols = r->cols, n = rows * cols;
     AB_TRY(out_planes_check(ctx, out_planes, rows, cols));
-    int64_t ph = rows, pw = cols;
-    AB_CHECK(ctx, ab_preview_dims(rows, cols, max_dim, &ph, &pw) == AB_OK, "the preview's dimensions could not be computed");
+    Preview pv;
+    AB_TRY(preview_of(ctx, rows, cols, max_dim, &pv));
     {
         std::vector<Span> ins, outs;
         for (int c = 0; c < 3; ++c) ins.push_back(span_of(*ch[c])), outs.push_back(span_of(out_planes[c]));
-        if (out_rgb8) outs.push_back(Span{(uintptr_t)out_rgb8, (size_t)(ph * pw) * 3, out_on_device != 0});
+        if (out_rgb8) outs.push_back(Span{(uintptr_t)out_rgb8, (size_t)(pv.ph * pv.pw) * 3, out_on_device != 0});
         AB_TRY(overlap_check(ctx, ins, outs));
     }
     ab_color_plan plan;
@@ -370,7 +362,6 @@ int ab_calibrate_and_scnr(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, con
     AB_HIP(ctx, hipSetDevice(ctx->device));
     AB_TRY(ab_cancel_point(ctx));
     Scope sc(ctx);
-    sc.ins.reserve(3);
     WizState *ws = nullptr;
     AB_TRY(carve(ctx, 0, &ws, nullptr));
     WbArgs a;
@@ -379,23 +370,19 @@ int ab_calibrate_and_scnr(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, con
         AB_TRY(sc.stage_in(ch[c], &a.src[c]));
         a.factor[c] = plan.factors[c];
     }
-    for (int c = 0; c < 3; ++c) {
-        AB_TRY(ab_stage_out_begin(ctx, &out_planes[c], &sc.outs[c]));
-        ++sc.n_outs;
-        a.out[c] = sc.outs[c].dptr;
-    }
+    for (int c = 0; c < 3; ++c) AB_TRY(sc.stage_out(&out_planes[c], &a.out[c]));
     if (plan.scnr_applied) {
         a.method = scnr->method;
         a.amount = scnr->amount > 1.0f ? 1.0f : scnr->amount;  // scnr.rs:28 (above 1e-7 already)
         a.preserve = scnr->preserve_luminance;
     }
     AB_TRY(launch_wb(ctx, a, plan.scnr_applied != 0));
-    Tail t{rows, cols, ph, pw, out_rgb8, out_on_device, info != nullptr, {}};
+    Tail t{rows, cols, pv, out_rgb8, out_on_device, info != nullptr, {}};
     AB_TRY(run_tail(ctx, sc, ws, &plan, &t));
     if (info) {
         memset(info, 0, sizeof *info);
         info->rows = (uint64_t)rows, info->cols = (uint64_t)cols;
-        info->preview_rows = (uint64_t)ph, info->preview_cols = (uint64_t)pw;
+        info->preview_rows = (uint64_t)pv.ph, info->preview_cols = (uint64_t)pv.pw;
         info->scnr_applied = plan.scnr_applied;
         for (int c = 0; c < 3; ++c) info->factors[c] = plan.factors[c], info->route[c] = plan.route[c], info->stats[c] = t.result.stats[c];
         info->stf = t.result.stf;
@@ -425,20 +412,19 @@ int ab_blend_composite(ab_ctx *ctx, const ab_plane *channels, size_t n_channels,
     for (size_t i = 0; i < n_channels; ++i) n_resampled += channels[i].rows != rows || channels[i].cols != cols;  // :152
     AB_CHECK(ctx, n_resampled == 0 || rows <= 65535, "a resample to %lld rows is not in this build", (long long)rows);
     AB_TRY(out_planes_check(ctx, out_planes, rows, cols));
-    int64_t ph = rows, pw = cols;
-    AB_CHECK(ctx, ab_preview_dims(rows, cols, max_dim, &ph, &pw) == AB_OK, "the preview's dimensions could not be computed");
+    Preview pv;
+    AB_TRY(preview_of(ctx, rows, cols, max_dim, &pv));
     {
         std::vector<Span> ins, outs;
         for (size_t i = 0; i < n_channels; ++i) ins.push_back(span_of(channels[i]));
         for (int c = 0; c < 3; ++c) outs.push_back(span_of(out_planes[c]));
-        if (out_rgb8) outs.push_back(Span{(uintptr_t)out_rgb8, (size_t)(ph * pw) * 3, out_on_device != 0});
+        if (out_rgb8) outs.push_back(Span{(uintptr_t)out_rgb8, (size_t)(pv.ph * pv.pw) * 3, out_on_device != 0});
         AB_TRY(overlap_check(ctx, ins, outs));
     }
 
     AB_HIP(ctx, hipSetDevice(ctx->device));
     AB_TRY(ab_cancel_point(ctx));
     Scope sc(ctx);
-    sc.ins.reserve(n_channels);
     WizState *ws = nullptr;
     char *extra = nullptr;
     const size_t plane_bytes = ((size_t)n * sizeof(float) + 255) & ~(size_t)255;
@@ -453,17 +439,15 @@ int ab_blend_composite(ab_ctx *ctx, const ab_plane *channels, size_t n_channels,
             src[i] = dst;
         }
     }
-    for (int c = 0; c < 3; ++c) {
-        AB_TRY(ab_stage_out_begin(ctx, &out_planes[c], &sc.outs[c]));
-        ++sc.n_outs;
-    }
-    AB_TRY(ab_blend_device(ctx, src, n_channels, weights, n_weights, n, sc.outs[0].dptr, sc.outs[1].dptr, sc.outs[2].dptr));  // :185
-    Tail t{rows, cols, ph, pw, out_rgb8, out_on_device, info != nullptr, {}};
+    float *dst[3];
+    for (int c = 0; c < 3; ++c) AB_TRY(sc.stage_out(&out_planes[c], &dst[c]));
+    AB_TRY(ab_blend_device(ctx, src, n_channels, weights, n_weights, n, dst[0], dst[1], dst[2]));  // :185
+    Tail t{rows, cols, pv, out_rgb8, out_on_device, info != nullptr, {}};
     AB_TRY(run_tail(ctx, sc, ws, nullptr, &t));  // :187-205
     if (info) {
         memset(info, 0, sizeof *info);
         info->rows = (uint64_t)rows, info->cols = (uint64_t)cols;
-        info->preview_rows = (uint64_t)ph, info->preview_cols = (uint64_t)pw;
+        info->preview_rows = (uint64_t)pv.ph, info->preview_cols = (uint64_t)pv.pw;
         info->resampled = n_resampled ? 1 : 0;
         for (int c = 0; c < 3; ++c) info->stats[c] = t.result.stats[c];
         info->stf = t.result.stf;

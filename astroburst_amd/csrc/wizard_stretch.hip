@@ -21,7 +21,7 @@
 // the output address.  Persistent grids sized from the context's CU count.  -ffp-contract=off like everything else.
 #include "ab_common.hpp"
 #include "arcsinh_device.hpp"
-#include "wizard_host.hpp"
+#include "entry_host.hpp"
 
 #include <cmath>
 
@@ -223,10 +223,6 @@ __global__ __launch_bounds__(kBlock) void stretch_kernel(const StretchArgs a) {
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-int64_t head16(const void *p, int64_t n) { return std::min<int64_t>(n, (int64_t)(((16 - (uintptr_t)p % 16) % 16) / sizeof(float))); }
-// the pixels before the first one whose byte triple starts a dword: 3 head = -addr (mod 4)
-int64_t head_bytes(const uint8_t *out, int64_t n) { return std::min<int64_t>(n, (int64_t)((3 * ((4 - (uintptr_t)out % 4) % 4)) % 4)); }
-
 int launch_range(ab_ctx *ctx, const float *const *src, int planes, int64_t n, unsigned int *enc) {
     AB_HIP(ctx, hipMemsetAsync(enc, 0, 6 * sizeof(unsigned int), ctx->stream));
     RangeArgs a;
@@ -236,15 +232,10 @@ int launch_range(ab_ctx *ctx, const float *const *src, int planes, int64_t n, un
         a.head[c] = head16(src[c], n);
         a.quads[c] = (n - a.head[c]) / 4;
     }
-    hipLaunchKernelGGL(range_kernel, dim3(persistent_grid(ctx, (n + 3) / 4)), dim3(kBlock), 0, ctx->stream, a, enc);
+    hipLaunchKernelGGL(range_kernel, dim3(ab_stream_grid(ctx, (n + 3) / 4)), dim3(kBlock), 0, ctx->stream, a, enc);
     AB_HIP(ctx, hipGetLastError());
     return AB_OK;
 }
-
-struct Preview {  // the preview of ab_preview_dims
-    int64_t ph = 0, pw = 0;
-    bool sampled = false;  // the image exceeds max_dim: the preview is a pick (helpers.rs:282-289)
-};
 
 // one launch: the planes (a.out, when planes), the bytes (a.bytes, when non-null) or both; a.src / a.n and the stretch's scalars are set
 template <int CH, bool STRETCH>
@@ -264,7 +255,7 @@ int launch_stretch(ab_ctx *ctx, StretchArgs a, bool planes, const Preview &pv) {
         a.bquads = (a.pn - a.bhead) / 4;
         lanes = std::max<int64_t>(lanes, std::max<int64_t>(a.bquads, a.pn - 4 * a.bquads));
     }
-    const dim3 grid(persistent_grid(ctx, lanes)), block(kBlock);
+    const dim3 grid(ab_stream_grid(ctx, lanes)), block(kBlock);
     if constexpr (CH == 1) {
         hipLaunchKernelGGL((stretch_kernel<1, STRETCH, true, 0>), grid, block, 0, ctx->stream, a);
     } else if (planes) {
@@ -319,14 +310,7 @@ struct Finish {
         wait = true;
         return AB_OK;
     }
-    int host_planes(Scope &sc) {  // (the scope frees the staging buffers)
-        for (int c = 0; c < sc.n_outs; ++c)
-            if (sc.outs[c].owned) {
-                AB_HIP(ctx, hipMemcpyAsync(sc.outs[c].host, sc.outs[c].dptr, sc.outs[c].bytes, hipMemcpyDeviceToHost, ctx->stream));
-                wait = true;
-            }
-        return AB_OK;
-    }
+    int host_planes(Scope &sc) { return sc.enqueue_host_outs(&wait); }
     int join() {
         if (wait) AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return AB_OK;
@@ -336,16 +320,12 @@ struct Finish {
 // the checks the three composite calls share, before anything touches the device
 int composite_check(ab_ctx *ctx, const ab_plane *const ch[3], int64_t max_dim, const ab_plane_mut *out_planes, const uint8_t *out_rgb8, int32_t out_on_device,
                     Preview *pv) {
-    for (int c = 0; c < 3; ++c) AB_TRY(plane_check(ctx, ch[c], kChan[c]));
-    for (int c = 1; c < 3; ++c)  // (the planes of one composite)
-        AB_CHECK(ctx, ch[c]->rows == ch[0]->rows && ch[c]->cols == ch[0]->cols, "the %s plane is %lld x %lld, R is %lld x %lld", kChan[c],
-                 (long long)ch[c]->rows, (long long)ch[c]->cols, (long long)ch[0]->rows, (long long)ch[0]->cols);
+    AB_TRY(same_dims_check(ctx, ch));  // (the planes of one composite)
     const int64_t rows = ch[0]->rows, cols = ch[0]->cols;
     AB_CHECK(ctx, max_dim >= 1, "max_dim must be >= 1 (got %lld)", (long long)max_dim);
     AB_CHECK(ctx, out_planes || out_rgb8, "both outputs are null");
     if (out_planes) AB_TRY(out_planes_check(ctx, out_planes, rows, cols));
-    AB_CHECK(ctx, ab_preview_dims(rows, cols, max_dim, &pv->ph, &pv->pw) == AB_OK, "the preview's dimensions could not be computed");
-    pv->sampled = pv->ph != rows || pv->pw != cols;
+    AB_TRY(preview_of(ctx, rows, cols, max_dim, pv));
     std::vector<Span> ins, outs;
     for (int c = 0; c < 3; ++c) ins.push_back(span_of(*ch[c]));
     for (int c = 0; c < 3 && out_planes; ++c) outs.push_back(span_of(out_planes[c]));
@@ -358,13 +338,8 @@ int arcsinh_rgb_chain(ab_ctx *ctx, Scope &sc, const ab_plane *const ch[3], const
                       ab_plane_mut *out_planes, uint8_t *bytes_dev, const Preview &pv, StretchState *st) {
     StretchArgs a;
     a.rows = ch[0]->rows, a.cols = ch[0]->cols, a.n = a.rows * a.cols;
-    sc.ins.reserve(3);
     for (int c = 0; c < 3; ++c) AB_TRY(sc.stage_in(ch[c], &a.src[c]));
-    for (int c = 0; c < 3 && out_planes; ++c) {
-        AB_TRY(ab_stage_out_begin(ctx, &out_planes[c], &sc.outs[c]));
-        ++sc.n_outs;
-        a.out[c] = sc.outs[c].dptr;
-    }
+    for (int c = 0; c < 3 && out_planes; ++c) AB_TRY(sc.stage_out(&out_planes[c], &a.out[c]));
     a.bytes = bytes_dev;
     a.enc = st->enc, a.state = st;
     if (global_min) {
@@ -402,13 +377,12 @@ int ab_arcsinh_stretch_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, co
     Scope sc(ctx);
     Finish fin{ctx};
     if (std::fabs(factor) < 1e-10f) {  // stretch.rs:65-67: the clones; no range is formed
-        sc.ins.reserve(3);
         for (int c = 0; c < 3; ++c) {
             const float *src = nullptr;
+            float *dst = nullptr;
             AB_TRY(sc.stage_in(ch[c], &src));
-            AB_TRY(ab_stage_out_begin(ctx, &out_planes[c], &sc.outs[c]));
-            ++sc.n_outs;
-            AB_HIP(ctx, hipMemcpyAsync(sc.outs[c].dptr, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+            AB_TRY(sc.stage_out(&out_planes[c], &dst));
+            AB_HIP(ctx, hipMemcpyAsync(dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
         }
         AB_TRY(fin.host_planes(sc));
         AB_TRY(fin.join());
@@ -495,11 +469,8 @@ int ab_arcsinh_stretch_view(ab_ctx *ctx, const ab_plane *img, double factor, ab_
     AB_TRY(carve(ctx, out_u8 && !out_on_device ? (size_t)n : 0, 0, n, &w));
     StretchArgs a;
     a.rows = rows, a.cols = cols, a.n = n;
-    sc.ins.reserve(1);
     AB_TRY(sc.stage_in(img, &a.src[0]));
-    AB_TRY(ab_stage_out_begin(ctx, out_plane, &sc.outs[0]));
-    ++sc.n_outs;
-    a.out[0] = sc.outs[0].dptr;
+    AB_TRY(sc.stage_out(out_plane, &a.out[0]));
     a.enc = w.st->enc, a.state = w.st;
     AB_TRY(launch_range(ctx, a.src, 1, n, w.st->enc));  // stretch.rs:6-7: stats.min / .max as f32
     set_stretch_scalars(&a, f, 1.0f);

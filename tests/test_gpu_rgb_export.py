@@ -351,6 +351,15 @@ def test_invalid_arguments_are_refused_with_a_message(ctx):
     refused(L.ab_process_drizzle_rgb(ctx._h, P(p), P(p), P(p), P(dcfg), small, None, o, 0, P(dinfo)), "out_stretched of the wrong dims")
     dcfg.white_balance = 3
     refused(L.ab_process_drizzle_rgb(ctx._h, P(p), P(p), P(p), P(dcfg), None, None, o, 0, P(dinfo)), "bad white balance")
+    # a device output over a device input plane (5 x 7: a head, whole four-pixel groups and loose pixels)
+    import torch
+    t = [torch.rand((5, 7), device="cuda") for _ in range(3)]
+    before = [x.clone() for x in t]
+    d = [_lib.Plane(C.c_void_p(x.data_ptr()), 5, 7, 1) for x in t]
+    refused(L.ab_render_rgb(ctx._h, P(d[0]), P(d[1]), P(d[2]), 0, C.c_void_p(t[2].data_ptr()), 1), "a device output over a device input")
+    assert b"an output overlaps an input plane" in L.ab_last_error(ctx._h)
+    torch.cuda.synchronize()
+    assert all(torch.equal(x, y) for x, y in zip(t, before))
     for fn in (L.ab_render_rgb, L.ab_render_rgb_stf, L.ab_export_rgb, L.ab_process_drizzle_rgb, L.ab_drizzle_rgb):   # a NULL context
         nothing = [0 if t in (C.c_int32, C.c_int64, C.c_size_t) else None for t in fn.argtypes]
         assert fn(*nothing) == _lib.AB_ERR_INVALID

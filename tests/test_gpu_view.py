@@ -325,4 +325,13 @@ def test_process_rgb_fits_view_errors(ctx):
         with pytest.raises(AstroBurstError) as e:
             ctx.process_rgb_fits_view(*planes, **kw)
         assert e.value.code == _lib.AB_ERR_INVALID and e.value.message, kw
+    # a device output over a device input plane (5 x 7: a head, whole four-pixel groups and loose pixels)
+    import torch
+    dev = [_dev(p) for p in _rgb((5, 7))]
+    before = [d.clone() for d in dev]
+    over = dev[1].view(-1).view(torch.uint8)[:5 * 7 * 3]
+    with pytest.raises(AstroBurstError) as e:
+        ctx.process_rgb_fits_view(*dev, hist_bins=0, out=over)
+    assert e.value.code == _lib.AB_ERR_INVALID and "an output overlaps an input plane" in e.value.message
+    assert all(torch.equal(d, x) for d, x in zip(dev, before))
     assert ctx.process_rgb_fits_view(r, g, b).rgb8.shape == (67, 93, 3)     # and the context still works
