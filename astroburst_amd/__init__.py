@@ -16,6 +16,7 @@ from .core import color_step_plan, compute_auto_wb  # noqa: F401
 from .core import MASK_PER_CHANNEL, MASK_SHARED_LUMINANCE, ArcsinhCompositeResult, ArcsinhViewResult, MaskedStretchCompositeResult  # noqa: F401
 from .core import arcsinh_rgb_range  # noqa: F401
 from .core import BackgroundStepResult  # noqa: F401
+from .core import ComposeRgbResult  # noqa: F401
 from .core import matches_from_votes, triangle_votes_host  # noqa: F401
 from .core import SynthFrames, synth_chacha_block, synth_config, synth_noise_params, synth_psf_type, synth_rng_f64, synth_star_field  # noqa: F401
 

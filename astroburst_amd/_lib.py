@@ -351,6 +351,11 @@ class BackgroundStepInfoC(C.Structure):  # ab_background_step_info: extract_back
                 ("corrected_stats", ImageStatsC), ("model_stats", ImageStatsC), ("corrected_stf", StfParamsC), ("model_stf", StfParamsC)]
 
 
+class ComposeRgbInfoC(C.Structure):  # ab_compose_rgb_info: compose_rgb_cmd's JSON and cache entries (cmd/compose/rgb.rs:106-116, :163-203)
+    _fields_ = [("rgb", ProcessedRgbInfoC), ("preview_rows", C.c_uint64), ("preview_cols", C.c_uint64), ("lrgb_applied", C.c_int32),
+                ("l_resampled", C.c_int32), ("l_stats", ImageStatsC), ("l_stf", StfParamsC)]
+
+
 class DrizzleResultC(C.Structure):  # DrizzleResult's scalars (drizzle.rs:335-344)
     _fields_ = [("frame_count", C.c_size_t), ("output_scale", C.c_double), ("in_rows", C.c_int64), ("in_cols", C.c_int64),
                 ("out_rows", C.c_int64), ("out_cols", C.c_int64), ("rejected_pixels", C.c_uint64)]
@@ -671,6 +676,9 @@ def lib() -> C.CDLL:
     L.ab_masked_stretch_composite.argtypes = [vp, pp, pp, pp, msc, C.c_int32, C.c_int64, pmp, vp, C.c_int32, C.POINTER(MaskedStretchCompositeInfoC)]
     L.ab_auto_stretch_preview_sampled.argtypes = [vp, pp, C.POINTER(AutoStfConfigC), C.c_int64, vp, C.c_int32, isp, C.POINTER(StfParamsC)]
     L.ab_background_step.argtypes = [vp, pp, C.POINTER(BackgroundConfigC), C.c_int64, pmp, pmp, vp, vp, C.c_int32, C.POINTER(BackgroundStepInfoC)]
+    L.ab_compose_rgb.argtypes = [vp, pp, pp, pp, pp, C.POINTER(RgbComposeConfigC), C.c_float, C.c_float, C.c_int64, pmp, pmp, vp, C.c_int32,
+                                 C.POINTER(ComposeRgbInfoC)]
+    L.ab_restretch_composite.argtypes = [vp, pp, pp, pp, isp, C.POINTER(StfParamsC), C.c_int32, C.POINTER(ScnrConfigC), C.c_int64, pmp, vp, C.c_int32]
     for name in declared_symbols():
         fn = getattr(L, name)  # AttributeError here = header / library drift
         if fn.restype is C.c_int and name not in ("ab_last_error", "ab_version", "ab_ctx_get_stream", "ab_comm_collectives_issued"):

@@ -457,6 +457,28 @@ class BackgroundStepResult:  # extract_background_cmd's (cmd/processing/backgrou
     model_stf: object
 
 
+@dataclass
+class ComposeRgbResult:  # compose_rgb_cmd's (cmd/compose/rgb.rs:43-205) outputs up to the PNG encoder
+    pre_stretch: tuple     # (r, g, b) white-balanced, aligned, pre-stretch planes: what the command caches as __composite_*
+    planes: object         # (r, g, b) final planes the command drops, or None (want_planes=False)
+    rgb8: object           # uint8 (preview_rows, preview_cols, 3), or None
+    rows: int
+    cols: int
+    preview_rows: int
+    preview_cols: int
+    stf: object            # (StfParams r, g, b), or None (fetch=False), like everything below
+    channel_stats: object  # 3 x (min, max, median, mean) before white balance
+    offset_g: object
+    offset_b: object
+    scnr_applied: object
+    resampled: object
+    stats_wb: object       # 3 x ImageStats after white balance: what the command caches with the planes
+    lrgb_applied: object
+    l_resampled: object
+    l_stats: object        # ImageStats of the matched L, or None (no L, or auto_stretch off)
+    l_stf: object
+
+
 def arcsinh_rgb_range(sr, sg, sb) -> tuple:
     """(global_min, global_max) of arcsinh_stretch_rgb_with_stats (core/imaging/stretch.rs:72-78): the f32 fold of three channels'
     ImageStats.  Host-only."""
@@ -1983,18 +2005,9 @@ class Context:
             raise AstroBurstError(rc, "select_wb_reference: null argument")
         return tuple(out)
 
-    def process_rgb(self, r, g, b, white_balance="auto", auto_stretch=True, stf=(None, None, None), linked_stf=False,
-                    align=True, align_method="phase_correlation", scnr=None, num_threads=8, want_pre_stretch=True
-                    ) -> ProcessedRgb:
-        """process_rgb(r?, g?, b?, &RgbComposeConfig) (rgb.rs:209-323).  Absent channels are None.
-        white_balance: "auto" | "none" | (r, g, b) manual multipliers; stf: per-channel StfParams or None (used when
-        auto_stretch is False); scnr: None or dict(method=, amount=, preserve_luminance=)."""
-        keep = []
-        chans = [None if x is None else self._plane(x, keep) for x in (r, g, b)]
-        present = [p for p in chans if p is not None]
-        first = next((x for x in (r, g, b) if x is not None), None)
-        rows = max((p.rows for p in present), default=0)
-        cols = max((p.cols for p in present), default=0)
+    @staticmethod
+    def _rgb_compose_config(white_balance, auto_stretch, stf, linked_stf, align, align_method, scnr, num_threads):
+        """ab_rgb_compose_config of process_rgb's keyword arguments"""
         cfg = _lib.RgbComposeConfigC()
         if isinstance(white_balance, str):
             cfg.white_balance = {"auto": 0, "none": 2}[white_balance]
@@ -2014,6 +2027,21 @@ class Context:
             cfg.scnr = _lib.ScnrConfigC(0 if m in ("average", "AverageNeutral", 0) else 1, scnr.get("amount", 1.0),
                                         int(bool(scnr.get("preserve_luminance", False))))
         cfg.num_threads = num_threads
+        return cfg
+
+    def process_rgb(self, r, g, b, white_balance="auto", auto_stretch=True, stf=(None, None, None), linked_stf=False,
+                    align=True, align_method="phase_correlation", scnr=None, num_threads=8, want_pre_stretch=True
+                    ) -> ProcessedRgb:
+        """process_rgb(r?, g?, b?, &RgbComposeConfig) (rgb.rs:209-323).  Absent channels are None.
+        white_balance: "auto" | "none" | (r, g, b) manual multipliers; stf: per-channel StfParams or None (used when
+        auto_stretch is False); scnr: None or dict(method=, amount=, preserve_luminance=)."""
+        keep = []
+        chans = [None if x is None else self._plane(x, keep) for x in (r, g, b)]
+        present = [p for p in chans if p is not None]
+        first = next((x for x in (r, g, b) if x is not None), None)
+        rows = max((p.rows for p in present), default=0)
+        cols = max((p.cols for p in present), default=0)
+        cfg = self._rgb_compose_config(white_balance, auto_stretch, stf, linked_stf, align, align_method, scnr, num_threads)
         if first is None:
             first = np.empty((0, 0), np.float32)
         outs = [self._new_like(first, rows, cols) for _ in range(3)]
@@ -2757,6 +2785,74 @@ class Context:
         self._check(self._L.ab_apply_tone_composite(self._h, C.byref(pr), C.byref(pg), C.byref(pb), st, C.byref(cfg), int(max_dim), pp, ptr, dev,
                                                     C.byref(info)))
         return ToneResult(planes, rgb8, _tone_info(info))
+
+    # ---- the RGB Compose panel: cmd/compose/rgb.rs ----------------------------------------------------------------------
+    def compose_rgb(self, l, r, g, b, white_balance="auto", auto_stretch=True, stf=(None, None, None), linked_stf=False, align=True,
+                    align_method="phase_correlation", scnr=None, num_threads=8, lrgb_lightness=1.0, lrgb_chrominance=1.0, max_dim=4096,
+                    want_planes=False, want_rgb8=True, fetch=True, out_pre=None, out_planes=None, out=None) -> ComposeRgbResult:
+        """compose_rgb_cmd (cmd/compose/rgb.rs:43-205) from its loaded entries to the PNG encoder's input and the JSON, as one chain:
+        process_rgb, L's resample / auto-STF / stretch, apply_lrgb and render_rgb_preview.  l and up to one of r, g, b may be None.
+        The keyword arguments up to num_threads are process_rgb's.  Numpy in, numpy out; CUDA tensors in, CUDA tensors out.
+        out_pre / out_planes: three planes of the composite's dims each; out: contiguous uint8 of preview_rows * preview_cols * 3,
+        any address.  fetch=False (info NULL) leaves only the white-balance synchronisation, and none for "none" / manual."""
+        keep = []
+        chans = [None if x is None else self._plane(x, keep) for x in (r, g, b)]
+        pl = None if l is None else self._plane(l, keep)
+        present = [p for p in chans if p is not None]
+        first = next((x for x in (r, g, b, l) if x is not None), None)
+        if first is None:
+            first = np.empty((0, 0), np.float32)
+        rows = max((int(p.rows) for p in present), default=0)
+        cols = max((int(p.cols) for p in present), default=0)
+        cfg = self._rgb_compose_config(white_balance, auto_stretch, stf, linked_stf, align, align_method, scnr, num_threads)
+        if out_pre is None:
+            out_pre = tuple(self._new_like(first, rows, cols) for _ in range(3))
+        ppre = (Plane * 3)(*[self._out_plane(a, keep, a.shape[0], a.shape[1]) for a in out_pre])   # (their own dims: the library refuses a mismatch)
+        pout = None
+        if want_planes or out_planes is not None:
+            if out_planes is None:
+                out_planes = tuple(self._new_like(first, rows, cols) for _ in range(3))
+            pout = (Plane * 3)(*[self._out_plane(a, keep, a.shape[0], a.shape[1]) for a in out_planes])
+        rgb8, ptr, dev = None, None, int(_is_torch(first) and first.is_cuda)
+        ph, pw = self.preview_dims(rows, cols, int(max_dim)) if (max_dim >= 1 and rows >= 1 and cols >= 1) else (1, 1)
+        if want_rgb8 or out is not None:
+            rgb8, ptr, dev = self._bytes_out(first, (ph, pw, 3), out)
+        info = _lib.ComposeRgbInfoC()
+        self._check(self._L.ab_compose_rgb(self._h, None if pl is None else C.byref(pl), *[None if p is None else C.byref(p) for p in chans],
+                                           C.byref(cfg), float(lrgb_lightness), float(lrgb_chrominance), int(max_dim), ppre, pout, ptr, dev,
+                                           C.byref(info) if fetch else None))
+        if not fetch:
+            return ComposeRgbResult(tuple(out_pre), None if pout is None else tuple(out_planes), rgb8, rows, cols, ph, pw, *([None] * 11))
+        pi = info.rgb
+        has_l_stats = pl is not None and bool(auto_stretch)
+        return ComposeRgbResult(tuple(out_pre), None if pout is None else tuple(out_planes), rgb8, int(pi.rows), int(pi.cols),
+                                int(info.preview_rows), int(info.preview_cols), tuple(StfParams(p.shadow, p.midtone, p.highlight) for p in pi.stf),
+                                tuple(tuple(row) for row in pi.chan_stats), tuple(pi.offset_g), tuple(pi.offset_b), bool(pi.scnr_applied),
+                                bool(pi.resampled), tuple(self._stats_out(s) for s in pi.stats_wb), bool(info.lrgb_applied), bool(info.l_resampled),
+                                self._stats_out(info.l_stats) if has_l_stats else None,
+                                StfParams(info.l_stf.shadow, info.l_stf.midtone, info.l_stf.highlight) if has_l_stats else None)
+
+    def restretch_composite(self, r, g, b, stats, stf, scnr=None, max_dim=4096, want_planes=False, want_rgb8=True, out=None):
+        """restretch_composite_cmd (cmd/compose/rgb.rs:208-241), the STF slider loop of the RGB Compose panel, on the tone editor's
+        kernel: the three explicit StfParams (or (shadow, midtone, highlight)) normalised with the cached ImageStats, SCNR whenever
+        scnr is not None (apply_scnr_inplace's own threshold decides), the preview's pick and pack.  -> (planes | None, rgb8 | None)."""
+        keep = []
+        pr, pg, pb = (self._plane(x, keep) for x in (r, g, b))
+        rows, cols = int(pr.rows), int(pr.cols)
+        st = (_lib.ImageStatsC * 3)(*[self._stats_in(s) for s in stats])
+        sp = (StfParamsC * 3)(*[StfParamsC(*(p if isinstance(p, (tuple, list)) else (p.shadow, p.midtone, p.highlight))) for p in stf])
+        sc = None
+        if scnr is not None:
+            m = scnr.get("method", "average")
+            sc = _lib.ScnrConfigC(0 if m in ("average", "AverageNeutral", 0) else 1, scnr.get("amount", 1.0), int(bool(scnr.get("preserve_luminance", False))))
+        planes, pp = self._plane3(r, rows, cols, keep) if want_planes else (None, None)
+        rgb8, ptr, dev = None, None, 0
+        if want_rgb8 or out is not None:
+            ph, pw = self.preview_dims(rows, cols, max_dim) if max_dim > 0 else (1, 1)   # (max_dim < 1 is the library's AB_ERR_INVALID)
+            rgb8, ptr, dev = self._bytes_out(r, (ph, pw, 3), out)
+        self._check(self._L.ab_restretch_composite(self._h, C.byref(pr), C.byref(pg), C.byref(pb), st, sp, int(sc is not None),
+                                                   None if sc is None else C.byref(sc), int(max_dim), pp, ptr, dev))
+        return planes, rgb8
 
     # ---- cmd/io/mod.rs: opening a file (process_fits, process_fits_full, process_rgb_fits) and the histogram panel ------------
     downsample_histogram = staticmethod(downsample_histogram)

@@ -69,6 +69,7 @@ enum {
     AB_WS_WIZARD,             // the blend / colour steps: three channels' statistics, the linked STF and transforms, resampled channels (wizard_color.hip)
     AB_WS_STRETCH,            // the stretch steps: the range words and what info reports, host-bound bytes, planes nobody asked for (wizard_stretch.hip)
     AB_WS_BACKGROUND,         // the background step: the model's range words, the corrected plane's statistics, host-bound bytes, a model nobody asked for (wizard_background.hip)
+    AB_WS_COMPOSE,            // the RGB compose command: the channels', the combined plane's and L's statistics, the STFs and transforms, host-bound bytes (compose_step.hip)
     AB_WS_SLOTS
 };
 
@@ -367,6 +368,17 @@ struct ab_background_fit {
 };
 int ab_background_check(ab_ctx *ctx, int64_t rows, int64_t cols, const ab_background_config *cfg);
 int ab_background_sample_fit(ab_ctx *ctx, const float *img_dev, int64_t rows, int64_t cols, const ab_background_config *cfg, ab_background_fit *fit);
+// compose_rgb.hip: the front half of process_rgb (rgb.rs:216-241), shared with compose_step.hip.  ab_compose_front_check: the channel
+// count and harmonize_dimensions' decisions with the reference's two error strings, host only.  ab_compose_front_device: the bicubic
+// resample of the channels of other dims (into tmp[c]), channel_or_synth and the registration of G and B, over device planes;
+// src[c] is nullptr for an absent channel, img[c] is where channel c lands.  Registration keeps its own synchronisations.
+struct ab_compose_dims {
+    int64_t rows = 0, cols = 0;  // the largest channel's
+    bool resample = false;
+};
+int ab_compose_front_check(ab_ctx *ctx, const ab_plane *const ch[3], ab_compose_dims *d);
+int ab_compose_front_device(ab_ctx *ctx, const ab_plane *const ch[3], const float *const src[3], const ab_compose_dims *d, float *const tmp[3],
+                            const ab_rgb_compose_config *cfg, float *const img[3], double offset_g[2], double offset_b[2]);
 // apply_stf -> u8 with the transform (StfTx) read from device memory
 int ab_stf_u8_device_tx(ab_ctx *ctx, const float *in, int64_t n, const void *tx_dev, uint8_t *out);
 // detect_stars of G frames of one size in lockstep (one launch per step for all of them); bg[f] = {median, sigma} of frame f's background

@@ -11,6 +11,7 @@
 // the registration scalars visit the host.  Every per-pixel map is a streaming f32 kernel at
 // 4 B read + 4 B written per pixel.
 #include "ab_common.hpp"
+#include "compose_device.hpp"
 #include "entry_host.hpp"
 
 #include <algorithm>
@@ -35,29 +36,8 @@ __global__ __launch_bounds__(kBlock) void scale_inplace_kernel(float *__restrict
     AB_GRID_LOOP(i, n) data[i] = data[i] * mult;  // rgb.rs:129
 }
 
-struct ComposeStf {
-    double dmin, inv_range, shadow, clip_range, m;
-};
-
 __global__ __launch_bounds__(kBlock) void compose_stf_kernel(float *__restrict__ data, int64_t n, const ComposeStf t) {
-    AB_GRID_LOOP(i, n) {  // rgb.rs:199-206
-        const float v = data[i];
-        float r;
-        if (!__builtin_isfinite(v) || v <= 1e-7f) {
-            r = 0.0f;
-        } else {
-            const double norm = ((double)v - t.dmin) * t.inv_range;
-            double clipped = (norm - t.shadow) / t.clip_range;
-            clipped = clipped < 0.0 ? 0.0 : (clipped > 1.0 ? 1.0 : clipped);
-            if (clipped <= 0.0)
-                r = 0.0f;
-            else if (clipped >= 1.0)
-                r = 1.0f;
-            else
-                r = (float)((t.m - 1.0) * clipped / ((2.0 * t.m - 1.0) * clipped - t.m));
-        }
-        data[i] = r;
-    }
+    AB_GRID_LOOP(i, n) data[i] = compose_stf_px(data[i], t);  // rgb.rs:199-206 (compose_device.hpp)
 }
 
 int copy_plane(ab_ctx *ctx, float *dst, const float *src, int64_t n) {
@@ -83,6 +63,73 @@ int channel_or_synth(ab_ctx *ctx, const float *primary, const float *alt1, const
 
 }  // namespace
 
+// harmonize_dimensions' decisions (rgb.rs:42-125) and process_rgb's channel count (:217): host only
+int ab_compose_front_check(ab_ctx *ctx, const ab_plane *const ch[3], ab_compose_dims *d) {
+    const int count = (ch[0] != nullptr) + (ch[1] != nullptr) + (ch[2] != nullptr);
+    if (count < 2) return ab_set_error(ctx, AB_ERR_INVALID, "Need at least 2 channels for RGB compose (got %d)", count);  // :217
+    int64_t min_rows = INT64_MAX, min_cols = INT64_MAX, max_rows = 0, max_cols = 0;
+    for (int c = 0; c < 3; ++c)
+        if (ch[c]) {
+            min_rows = std::min(min_rows, ch[c]->rows), min_cols = std::min(min_cols, ch[c]->cols);
+            max_rows = std::max(max_rows, ch[c]->rows), max_cols = std::max(max_cols, ch[c]->cols);
+        }
+    d->resample = !(max_rows == min_rows && max_cols == min_cols);
+    if (d->resample) {
+        const double ratio = std::fmax((double)max_rows / (double)std::max<int64_t>(min_rows, 1),
+                                       (double)max_cols / (double)std::max<int64_t>(min_cols, 1));
+        if (ratio > 8.0) {  // MAX_DIMENSION_RATIO (types/constants.rs:165)
+            char msg[256];
+            int k = snprintf(msg, sizeof msg, "Channel dimension ratio %.1fx exceeds %.0fx limit.", ratio, 8.0);
+            for (int c = 0; c < 3; ++c)
+                if (ch[c] && k > 0 && k < (int)sizeof msg)
+                    k += snprintf(msg + k, sizeof msg - k, " %c=%lldx%lld", "RGB"[c], (long long)ch[c]->cols, (long long)ch[c]->rows);
+            if (k > 0 && k < (int)sizeof msg) snprintf(msg + k, sizeof msg - k, ". Check channel assignments.");
+            return ab_set_error(ctx, AB_ERR_INVALID, "%s", msg);
+        }
+    }
+    d->rows = max_rows, d->cols = max_cols;
+    return AB_OK;
+}
+
+// the resample of the channels that differ in size (:106-119), channel_or_synth (:132-151) and align_channels (:165-189) with
+// align_pair (pair.rs:41-77) over device planes: src[c] is channel c on the device (nullptr: absent), tmp[c] a plane of the
+// composite's size for each present channel of other dims, img[c] where channel c lands.  Registration synchronises for its scalars.
+int ab_compose_front_device(ab_ctx *ctx, const ab_plane *const ch[3], const float *const src[3], const ab_compose_dims *d, float *const tmp[3],
+                            const ab_rgb_compose_config *cfg, float *const img[3], double offset_g[2], double offset_b[2]) {
+    const int64_t rows = d->rows, cols = d->cols, n = rows * cols;
+    const float *eff[3] = {src[0], src[1], src[2]};
+    for (int c = 0; c < 3; ++c)
+        if (ch[c] && d->resample && !(ch[c]->rows == rows && ch[c]->cols == cols)) {
+            AB_TRY(ab_resample_device(ctx, src[c], ch[c]->rows, ch[c]->cols, rows, cols, tmp[c]));
+            eff[c] = tmp[c];
+        }
+    const int alt[3][2] = {{1, 2}, {0, 2}, {0, 1}};
+    const bool do_align = cfg->align != 0;  // && count >= 2 (always true here)
+    for (int c = 0; c < 3; ++c) {
+        if (do_align && c > 0 && ch[c]) continue;  // produced by the registration below
+        AB_TRY(channel_or_synth(ctx, eff[c], eff[alt[c][0]], eff[alt[c][1]], n, img[c]));
+    }
+    if (do_align) {
+        const float *ref_ch = eff[0] ? eff[0] : (eff[1] ? eff[1] : eff[2]);
+        for (int c = 1; c < 3; ++c) {
+            if (!ch[c]) continue;
+            double *off = c == 1 ? offset_g : offset_b;
+            if (cfg->align_method == 0) {
+                double dx, dy, conf;
+                AB_TRY(ab_phase_correlate_device(ctx, ref_ch, rows, cols, cols, eff[c], rows, cols, cols, &dx, &dy, &conf));
+                AB_TRY(ab_shift_device(ctx, eff[c], rows, cols, cols, dy, dx, img[c]));
+                off[0] = dy, off[1] = dx;
+            } else {
+                ab_affine_align_result ar;
+                AB_TRY(ab_align_channel_affine_device(ctx, ref_ch, eff[c], rows, cols, cfg->num_threads > 0 ? cfg->num_threads : 1, &ar));
+                AB_TRY(ab_warp_device(ctx, eff[c], rows, cols, ar.transform, rows, cols, img[c]));
+                off[0] = ar.transform[5], off[1] = ar.transform[2];
+            }
+        }
+    }
+    return AB_OK;
+}
+
 extern "C" {
 
 int ab_select_wb_reference(const ab_image_stats *sr, const ab_image_stats *sg, const ab_image_stats *sb, double out[3]) try {
@@ -107,31 +154,11 @@ int ab_process_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_p
     AB_CHECK(ctx, cfg && out_r && out_g && out_b && info, "null argument");
     const ab_plane *ch[3] = {r, g, b};
     ab_plane_mut *outs[3] = {out_r, out_g, out_b}, *pres[3] = {pre_r, pre_g, pre_b};
-    const int count = (r != nullptr) + (g != nullptr) + (b != nullptr);
     memset(info, 0, sizeof *info);
-    if (count < 2) return ab_set_error(ctx, AB_ERR_INVALID, "Need at least 2 channels for RGB compose (got %d)", count);  // :217
-    // harmonize_dimensions (:42-125)
-    int64_t min_rows = INT64_MAX, min_cols = INT64_MAX, max_rows = 0, max_cols = 0;
-    for (int c = 0; c < 3; ++c)
-        if (ch[c]) {
-            min_rows = std::min(min_rows, ch[c]->rows), min_cols = std::min(min_cols, ch[c]->cols);
-            max_rows = std::max(max_rows, ch[c]->rows), max_cols = std::max(max_cols, ch[c]->cols);
-        }
-    const bool resample = !(max_rows == min_rows && max_cols == min_cols);
-    if (resample) {
-        const double ratio = std::fmax((double)max_rows / (double)std::max<int64_t>(min_rows, 1),
-                                       (double)max_cols / (double)std::max<int64_t>(min_cols, 1));
-        if (ratio > 8.0) {  // MAX_DIMENSION_RATIO (types/constants.rs:165)
-            char msg[256];
-            int k = snprintf(msg, sizeof msg, "Channel dimension ratio %.1fx exceeds %.0fx limit.", ratio, 8.0);
-            for (int c = 0; c < 3; ++c)
-                if (ch[c] && k > 0 && k < (int)sizeof msg)
-                    k += snprintf(msg + k, sizeof msg - k, " %c=%lldx%lld", "RGB"[c], (long long)ch[c]->cols, (long long)ch[c]->rows);
-            if (k > 0 && k < (int)sizeof msg) snprintf(msg + k, sizeof msg - k, ". Check channel assignments.");
-            return ab_set_error(ctx, AB_ERR_INVALID, "%s", msg);
-        }
-    }
-    const int64_t rows = max_rows, cols = max_cols, n = rows * cols;
+    ab_compose_dims dm;
+    AB_TRY(ab_compose_front_check(ctx, ch, &dm));
+    const bool resample = dm.resample;
+    const int64_t rows = dm.rows, cols = dm.cols, n = rows * cols;
     for (int c = 0; c < 3; ++c) {
         AB_CHECK(ctx, outs[c]->rows == rows && outs[c]->cols == cols, "output planes must have the largest channel's dims (%lld x %lld)",
                  (long long)rows, (long long)cols);
@@ -145,42 +172,15 @@ int ab_process_rgb(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_p
 
     Scope sc(ctx);
     const float *eff[3] = {nullptr, nullptr, nullptr};
+    float *tmp[3] = {nullptr, nullptr, nullptr};
     for (int c = 0; c < 3; ++c) {
         if (!ch[c]) continue;
         AB_TRY(sc.stage_in(ch[c], &eff[c]));
-        if (resample && !(ch[c]->rows == rows && ch[c]->cols == cols)) {  // :106-119
-            float *h = nullptr;
-            AB_TRY(sc.alloc((void **)&h, (size_t)n * sizeof(float)));
-            AB_TRY(ab_resample_device(ctx, eff[c], ch[c]->rows, ch[c]->cols, rows, cols, h));
-            eff[c] = h;
-        }
+        if (resample && !(ch[c]->rows == rows && ch[c]->cols == cols)) AB_TRY(sc.alloc((void **)&tmp[c], (size_t)n * sizeof(float)));
     }
     float *img[3];
     for (int c = 0; c < 3; ++c) AB_TRY(sc.stage_out(outs[c], &img[c]));
-    const int alt[3][2] = {{1, 2}, {0, 2}, {0, 1}};
-    const bool do_align = cfg->align != 0;  // && count >= 2 (always true here)
-    for (int c = 0; c < 3; ++c) {
-        if (do_align && c > 0 && ch[c]) continue;  // produced by the registration below
-        AB_TRY(channel_or_synth(ctx, eff[c], eff[alt[c][0]], eff[alt[c][1]], n, img[c]));
-    }
-    if (do_align) {  // align_channels (:165-189) + align_pair (pair.rs:41-77)
-        const float *ref_ch = eff[0] ? eff[0] : (eff[1] ? eff[1] : eff[2]);
-        for (int c = 1; c < 3; ++c) {
-            if (!ch[c]) continue;
-            double *off = c == 1 ? info->offset_g : info->offset_b;
-            if (cfg->align_method == 0) {
-                double dx, dy, conf;
-                AB_TRY(ab_phase_correlate_device(ctx, ref_ch, rows, cols, cols, eff[c], rows, cols, cols, &dx, &dy, &conf));
-                AB_TRY(ab_shift_device(ctx, eff[c], rows, cols, cols, dy, dx, img[c]));
-                off[0] = dy, off[1] = dx;
-            } else {
-                ab_affine_align_result ar;
-                AB_TRY(ab_align_channel_affine_device(ctx, ref_ch, eff[c], rows, cols, cfg->num_threads > 0 ? cfg->num_threads : 1, &ar));
-                AB_TRY(ab_warp_device(ctx, eff[c], rows, cols, ar.transform, rows, cols, img[c]));
-                off[0] = ar.transform[5], off[1] = ar.transform[2];
-            }
-        }
-    }
+    AB_TRY(ab_compose_front_device(ctx, ch, eff, &dm, tmp, cfg, img, info->offset_g, info->offset_b));
     ab_image_stats full[3];
     for (int c = 0; c < 3; ++c) {  // :243-249
         memset(&full[c], 0, sizeof full[c]);

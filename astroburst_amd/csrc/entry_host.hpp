@@ -1,6 +1,6 @@
 // Host plumbing of the display-side entry points: what is refused before anything touches the device, and what is released when an
 // entry point returns, on an error exit included.  Included by view.hip, tone.hip, rgb_export.hip, render.hip, compose_rgb.hip,
-// masked_stretch.hip, wizard_color.hip, wizard_stretch.hip and wizard_background.hip; crop.hip takes fits31 and the scope only (it
+// masked_stretch.hip, wizard_color.hip, wizard_stretch.hip, wizard_background.hip and compose_step.hip; crop.hip takes fits31 and the scope only (it
 // words its messages by plane number), spcc.hip the scope.  preview.hip does not include it: its own Span (a sweep's four-pixel
 // groups) is another thing.
 //   checks      fits31, plane_check, same_dims_check, out_planes_check, preview_of

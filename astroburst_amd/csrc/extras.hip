@@ -7,6 +7,7 @@
 // (the master flat's mean, calibration.rs:228-236) is a two-level f64 sum, so the flat's f32 scale factor
 // can differ from the reference's sequential sum in the last ulp on rare inputs (tests bound it at 1 ulp).
 #include "ab_common.hpp"
+#include "compose_device.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -18,22 +19,12 @@ constexpr int kBlock = 256;
 #define AB_GRID_LOOP(i, n) \
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride_ = (int64_t)gridDim.x * kBlock; i < (n); i += stride_)
 
-__device__ __forceinline__ float clamp01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
-
 __global__ __launch_bounds__(kBlock) void lrgb_kernel(const float *__restrict__ l, float *__restrict__ r, float *__restrict__ g,
                                                       float *__restrict__ b, int64_t n, float lw, float cw) {
-    AB_GRID_LOOP(i, n) {  // lrgb.rs:25-42
-        const float rv = r[i], gv = g[i], bv = b[i], lum_new = l[i];
-        const float lum_old = rv * 0.2126f + gv * 0.7152f + bv * 0.0722f;
-        if (lum_old < 1e-10f) {
-            const float blended = lum_new * lw;
-            r[i] = blended, g[i] = blended, b[i] = blended;
-            continue;
-        }
-        const float ratio = (lum_new * lw + lum_old * (1.0f - lw)) / lum_old;
-        r[i] = clamp01(rv * ratio * cw + lum_new * (1.0f - cw));
-        g[i] = clamp01(gv * ratio * cw + lum_new * (1.0f - cw));
-        b[i] = clamp01(bv * ratio * cw + lum_new * (1.0f - cw));
+    AB_GRID_LOOP(i, n) {  // lrgb.rs:25-42 (compose_device.hpp)
+        float rv = r[i], gv = g[i], bv = b[i];
+        lrgb_px(l[i], rv, gv, bv, lw, cw);
+        r[i] = rv, g[i] = gv, b[i] = bv;
     }
 }
 

@@ -299,28 +299,12 @@ int lut_upload(ab_ctx *ctx, const float *lut, const float **dev) {
     return AB_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-void ab_tone_config_default(ab_tone_config *cfg) {
-    if (!cfg) return;
-    memset(cfg, 0, sizeof *cfg);
-    for (int c = 0; c < 3; ++c) {
-        cfg->stf[c] = ab_stf_params{0.0, 0.5, 1.0};
-        cfg->levels[c] = ab_levels_params{0.0, 1.0, 1.0};  // LevelsParams::default() (core/imaging/curves.rs:11-15)
-    }
-    cfg->scnr = ab_scnr_config{0, 1.0f, 0};
-}
-
-int ab_tone_plan(const ab_image_stats stats[3], const ab_tone_config *cfg, ab_tone_info *info, float *lut3x4096) try {
-    if (!stats || !cfg || !info) return AB_ERR_INVALID;
-    return tone_plan(stats, cfg, info, lut3x4096);
-} AB_CATCH_NOCTX
-
-int ab_apply_tone_composite(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, const ab_image_stats stats[3], const ab_tone_config *cfg,
-                            int64_t max_dim, ab_plane_mut *out_planes, uint8_t *out_rgb8, int32_t out_on_device, ab_tone_info *info) try {
-    if (!ctx) return AB_ERR_INVALID;
+// apply_tone_composite_cmd's pixel work.  restretch: restretch_composite_cmd (cmd/compose/rgb.rs:208-241) on the same kernel -- the
+// caller has set explicit STFs and identity levels and curves; SCNR is decided by apply_scnr_inplace alone (a config that is present
+// reaches it, rgb.rs:232-234; its own clamp and threshold are scnr.rs:28-31), not by the tone command's amount > 1e-7 (curves.rs:149):
+// the two differ for a NaN amount, which apply_scnr_inplace lets through.
+int tone_composite(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, const ab_image_stats stats[3], const ab_tone_config *cfg,
+                   int64_t max_dim, ab_plane_mut *out_planes, uint8_t *out_rgb8, int32_t out_on_device, ab_tone_info *info, bool restretch) {
     const ab_plane *ch[3] = {r, g, b};
     AB_TRY(same_dims_check(ctx, ch));  // (the command takes its dims from R, :80; its planes are one composite's)
     AB_CHECK(ctx, stats && cfg, "null statistics or configuration");
@@ -342,6 +326,10 @@ int ab_apply_tone_composite(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, c
     {
         const int rc = tone_plan(stats, cfg, &plan, lut.data());
         if (rc != AB_OK) return ab_set_error(ctx, rc, "the tone plan could not be computed");
+    }
+    if (restretch) {
+        const float amount = cfg->scnr.amount < 0.0f ? 0.0f : (cfg->scnr.amount > 1.0f ? 1.0f : cfg->scnr.amount);  // scnr.rs:28
+        plan.scnr_applied = cfg->has_scnr && !(amount < 1e-7f) ? 1 : 0;                                           // :29-31
     }
     plan.rows = (uint64_t)rows, plan.cols = (uint64_t)cols;
     plan.preview_rows = (uint64_t)ph, plan.preview_cols = (uint64_t)pw;
@@ -409,6 +397,44 @@ int ab_apply_tone_composite(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, c
     AB_TRY(sc.finish_outs());
     if (info) *info = plan;
     return AB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void ab_tone_config_default(ab_tone_config *cfg) {
+    if (!cfg) return;
+    memset(cfg, 0, sizeof *cfg);
+    for (int c = 0; c < 3; ++c) {
+        cfg->stf[c] = ab_stf_params{0.0, 0.5, 1.0};
+        cfg->levels[c] = ab_levels_params{0.0, 1.0, 1.0};  // LevelsParams::default() (core/imaging/curves.rs:11-15)
+    }
+    cfg->scnr = ab_scnr_config{0, 1.0f, 0};
+}
+
+int ab_tone_plan(const ab_image_stats stats[3], const ab_tone_config *cfg, ab_tone_info *info, float *lut3x4096) try {
+    if (!stats || !cfg || !info) return AB_ERR_INVALID;
+    return tone_plan(stats, cfg, info, lut3x4096);
+} AB_CATCH_NOCTX
+
+int ab_apply_tone_composite(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, const ab_image_stats stats[3], const ab_tone_config *cfg,
+                            int64_t max_dim, ab_plane_mut *out_planes, uint8_t *out_rgb8, int32_t out_on_device, ab_tone_info *info) try {
+    if (!ctx) return AB_ERR_INVALID;
+    return tone_composite(ctx, r, g, b, stats, cfg, max_dim, out_planes, out_rgb8, out_on_device, info, false);
+} AB_CATCH(ctx)
+
+int ab_restretch_composite(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, const ab_image_stats stats[3], const ab_stf_params stf[3],
+                           int32_t has_scnr, const ab_scnr_config *scnr, int64_t max_dim, ab_plane_mut *out_planes, uint8_t *out_rgb8,
+                           int32_t out_on_device) try {
+    if (!ctx) return AB_ERR_INVALID;
+    AB_CHECK(ctx, stf, "null STF parameters");
+    AB_CHECK(ctx, !has_scnr || scnr, "has_scnr is set and the SCNR configuration is null");
+    ab_tone_config cfg;
+    ab_tone_config_default(&cfg);
+    for (int c = 0; c < 3; ++c) cfg.has_stf[c] = 1, cfg.stf[c] = stf[c];  // cmd/compose/rgb.rs:224-230
+    if (has_scnr) cfg.has_scnr = 1, cfg.scnr = *scnr;                     // :232-234
+    return tone_composite(ctx, r, g, b, stats, &cfg, max_dim, out_planes, out_rgb8, out_on_device, nullptr, true);
 } AB_CATCH(ctx)
 
 }  // extern "C"

@@ -10,7 +10,8 @@
 //   blend_kernel        (blend) color.hip's, through ab_blend_device, after the bicubic resample of the channels that differ in size.
 //   statistics          exactly three chains (stats.hip: ab_stats_enqueue), each of a FINAL plane by the route that yields what the
 //                       reference keeps (color_plan below); the statistics the reference computes and overwrites (color.rs:150-154)
-//                       are never computed.  Each result is copied out of the chain's state block before the next chain reuses it.
+//                       are never computed.  Each result is copied out of the chain's state block before the next chain reuses it
+//                       (save_stats_device.hpp's save_stats_kernel).
 //   linked_stf_kernel   one small workgroup: the combined statistics with extras.hip's expressions in their order, ab_auto_stf_hd,
 //                       make_tx x 3 -- the same __host__ __device__ functions the host entry points run, IEEE basic operations only.
 //                       With it no host round trip stands between the statistics and the preview.
@@ -21,6 +22,7 @@
 // allows it.  Persistent grids sized from the context's CU count.  -ffp-contract=off like everything else: each stage is the
 // instruction sequence of the kernel it restates, so planes and bytes equal the library's own unfused calls bit for bit.
 #include "ab_common.hpp"
+#include "save_stats_device.hpp"
 #include "scnr_device.hpp"
 #include "stf_device.hpp"
 #include "entry_host.hpp"
@@ -91,11 +93,6 @@ __global__ __launch_bounds__(kBlock) void wb_scnr_kernel(const WbArgs a) {
         if constexpr (SCNR) scnr_px(rv, gv, bv, a.method, a.amount, a.preserve);
         a.out[0][i] = rv, a.out[1][i] = gv, a.out[2][i] = bv;
     }
-}
-
-// the device-to-device copy of one channel's statistics out of the chain's state block, before the next chain overwrites it
-__global__ void save_stats_kernel(const ab_image_stats *st, ab_image_stats *dst) {
-    if (threadIdx.x == 0) *dst = *st;
 }
 
 // compute_linked_stf_with_stats (cmd/helpers.rs:185-202; extras.hip:178-185, the same expressions in the same order), auto_stf and

@@ -2138,15 +2138,7 @@ pub fn select_wb_reference(sr: &ImageStats, sg: &ImageStats, sb: &ImageStats) ->
     unsafe { sys::ab_select_wb_reference(&stats_to_sys(sr), &stats_to_sys(sg), &stats_to_sys(sb), m.as_mut_ptr()) };
     (m[0], m[1], m[2])
 }
-/// drop-in for process_rgb (rgb.rs:209-323)
-pub fn process_rgb(hip: &Hip, r: Option<&Array2<f32>>, g: Option<&Array2<f32>>, b: Option<&Array2<f32>>, config: &RgbComposeConfig) -> Result<ProcessedRgb> {
-    let count = [r, g, b].iter().filter(|c| c.is_some()).count();
-    if count < 2 {
-        bail!("Need at least 2 channels for RGB compose (got {})", count); // rgb.rs:217
-    }
-    let rows = [r, g, b].iter().flatten().map(|a| a.nrows()).max().unwrap();
-    let cols = [r, g, b].iter().flatten().map(|a| a.ncols()).max().unwrap();
-    let (pr, pg, pb) = (opt_plane(r), opt_plane(g), opt_plane(b));
+fn rgb_compose_cfg(config: &RgbComposeConfig) -> sys::ab_rgb_compose_config {
     let mut cfg: sys::ab_rgb_compose_config = unsafe { std::mem::zeroed() };
     match config.white_balance {
         WhiteBalance::Auto => cfg.white_balance = 0,
@@ -2171,6 +2163,18 @@ pub fn process_rgb(hip: &Hip, r: Option<&Array2<f32>>, g: Option<&Array2<f32>>, 
         cfg.scnr = scnr_to_sys(s);
     }
     cfg.num_threads = num_threads();
+    cfg
+}
+/// drop-in for process_rgb (rgb.rs:209-323)
+pub fn process_rgb(hip: &Hip, r: Option<&Array2<f32>>, g: Option<&Array2<f32>>, b: Option<&Array2<f32>>, config: &RgbComposeConfig) -> Result<ProcessedRgb> {
+    let count = [r, g, b].iter().filter(|c| c.is_some()).count();
+    if count < 2 {
+        bail!("Need at least 2 channels for RGB compose (got {})", count); // rgb.rs:217
+    }
+    let rows = [r, g, b].iter().flatten().map(|a| a.nrows()).max().unwrap();
+    let cols = [r, g, b].iter().flatten().map(|a| a.ncols()).max().unwrap();
+    let (pr, pg, pb) = (opt_plane(r), opt_plane(g), opt_plane(b));
+    let cfg = rgb_compose_cfg(config);
     let z = || Array2::<f32>::zeros((rows, cols));
     let (mut or, mut og, mut ob, mut qr, mut qg, mut qb) = (z(), z(), z(), z(), z(), z());
     let mut info: sys::ab_processed_rgb_info = unsafe { std::mem::zeroed() };
@@ -2202,6 +2206,81 @@ pub fn process_rgb(hip: &Hip, r: Option<&Array2<f32>>, g: Option<&Array2<f32>>, 
         stats_wb_g: Some(stats_from_sys(&info.stats_wb[1])),
         stats_wb_b: Some(stats_from_sys(&info.stats_wb[2])),
     })
+}
+/// what compose_rgb_cmd encodes, caches and reports (cmd/compose/rgb.rs:106-116, :153-203)
+pub struct ComposedRgb {
+    pub pixels: Vec<u8>,
+    pub preview_dims: (usize, usize),
+    /// the white-balanced, aligned, pre-stretch planes: __composite_* / __composite_orig_*, with stats_wb
+    pub pre_stretch: [Array2<f32>; 3],
+    pub stats_wb: [ImageStats; 3],
+    pub rows: usize,
+    pub cols: usize,
+    pub stf: [StfParams; 3],
+    pub stats: [ChannelStats; 3],
+    pub offset_g: (f64, f64),
+    pub offset_b: (f64, f64),
+    pub scnr_applied: bool,
+    pub resampled: bool,
+    pub lrgb_applied: bool,
+    pub elapsed_ms: u64,
+}
+/// compose_rgb_cmd (cmd/compose/rgb.rs:43-205) from its loaded entries to the encoder's input as one chain: process_rgb, the L branch (resample_image,
+/// stf::analyze, auto_stf, apply_stf_f32, apply_lrgb) and render_rgb_preview; above max_dim only the picked pixels are finished
+pub fn compose_rgb(hip: &Hip, l: Option<&Array2<f32>>, r: Option<&Array2<f32>>, g: Option<&Array2<f32>>, b: Option<&Array2<f32>>, config: &RgbComposeConfig,
+                   lrgb_lightness: f32, lrgb_chrominance: f32, max_dim: usize) -> Result<ComposedRgb> {
+    let start = std::time::Instant::now();
+    let count = [r, g, b].iter().filter(|c| c.is_some()).count();
+    if count < 2 {
+        bail!("Need at least 2 channels for RGB compose (got {})", count); // rgb.rs:217
+    }
+    let rows = [r, g, b].iter().flatten().map(|a| a.nrows()).max().unwrap();
+    let cols = [r, g, b].iter().flatten().map(|a| a.ncols()).max().unwrap();
+    let (pl, pr, pg, pb) = (opt_plane(l), opt_plane(r), opt_plane(g), opt_plane(b));
+    let cfg = rgb_compose_cfg(config);
+    let (ph, pw) = preview_dims(rows, cols, max_dim);
+    let mut pre = planes3(rows, cols);
+    let mut pp = [pre[0].ab_mut(), pre[1].ab_mut(), pre[2].ab_mut()];
+    let mut pixels = vec![0u8; ph * pw * 3];
+    let mut info: sys::ab_compose_rgb_info = unsafe { std::mem::zeroed() };
+    hip.check(unsafe {
+        sys::ab_compose_rgb(hip.ctx, opt_ptr(&pl), opt_ptr(&pr), opt_ptr(&pg), opt_ptr(&pb), &cfg, lrgb_lightness, lrgb_chrominance, max_dim as i64, pp.as_mut_ptr(),
+                            std::ptr::null_mut(), pixels.as_mut_ptr(), 0, &mut info)
+    })?;
+    let cs = |i: usize| ChannelStats { min: info.rgb.chan_stats[i][0], max: info.rgb.chan_stats[i][1], median: info.rgb.chan_stats[i][2], mean: info.rgb.chan_stats[i][3] };
+    Ok(ComposedRgb {
+        pixels,
+        preview_dims: (info.preview_rows as usize, info.preview_cols as usize),
+        pre_stretch: pre,
+        stats_wb: [stats_from_sys(&info.rgb.stats_wb[0]), stats_from_sys(&info.rgb.stats_wb[1]), stats_from_sys(&info.rgb.stats_wb[2])],
+        rows: info.rgb.rows as usize,
+        cols: info.rgb.cols as usize,
+        stf: [stf_from_sys(&info.rgb.stf[0]), stf_from_sys(&info.rgb.stf[1]), stf_from_sys(&info.rgb.stf[2])],
+        stats: [cs(0), cs(1), cs(2)],
+        offset_g: (info.rgb.offset_g[0], info.rgb.offset_g[1]),
+        offset_b: (info.rgb.offset_b[0], info.rgb.offset_b[1]),
+        scnr_applied: info.rgb.scnr_applied != 0,
+        resampled: info.rgb.resampled != 0,
+        lrgb_applied: info.lrgb_applied != 0,
+        elapsed_ms: start.elapsed().as_millis() as u64,
+    })
+}
+/// restretch_composite_cmd (cmd/compose/rgb.rs:208-241) on the tone editor's kernel: three explicit STFs normalised with the cached statistics, SCNR whenever a
+/// config is present (apply_scnr_inplace's own threshold decides), the preview's pick and pack -> preview_dims.0 x preview_dims.1 x 3 bytes.
+/// update_composite_channel_cmd (:255-293) beside it is resample_image + compute_image_stats
+pub fn restretch_composite(hip: &Hip, r: &impl PlaneSrc, g: &impl PlaneSrc, b: &impl PlaneSrc, stats: &[ImageStats; 3], stf: &[StfParams; 3], scnr: Option<&ScnrConfig>,
+                           max_dim: usize) -> Result<Vec<u8>> {
+    let (rows, cols) = r.dims();
+    let (ph, pw) = preview_dims(rows, cols, max_dim);
+    let s = [stats_to_sys(&stats[0]), stats_to_sys(&stats[1]), stats_to_sys(&stats[2])];
+    let p = [stf_to_sys(&stf[0]), stf_to_sys(&stf[1]), stf_to_sys(&stf[2])];
+    let sc = scnr.map(scnr_to_sys);
+    let mut pixels = vec![0u8; ph * pw * 3];
+    hip.check(unsafe {
+        sys::ab_restretch_composite(hip.ctx, &r.ab(), &g.ab(), &b.ab(), s.as_ptr(), p.as_ptr(), sc.is_some() as i32, sc.as_ref().map_or(std::ptr::null(), |c| c as *const _),
+                                    max_dim as i64, std::ptr::null_mut(), pixels.as_mut_ptr(), 0)
+    })?;
+    Ok(pixels)
 }
 /// drop-in for apply_lrgb (lrgb.rs:4-45)
 pub fn apply_lrgb(hip: &Hip, l: &impl PlaneSrc, r: &mut impl PlaneDst, g: &mut impl PlaneDst, b: &mut impl PlaneDst, lightness_weight: f32, chrominance_weight: f32) -> Result<()> {

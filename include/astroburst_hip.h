@@ -1286,6 +1286,17 @@ AB_API int ab_tone_plan(const ab_image_stats stats[3], const ab_tone_config *cfg
 AB_API int ab_apply_tone_composite(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, const ab_image_stats stats[3],
                                    const ab_tone_config *cfg, int64_t max_dim, ab_plane_mut *out_planes, uint8_t *out_rgb8,
                                    int32_t out_on_device, ab_tone_info *info);
+/* restretch_composite_cmd (cmd/compose/rgb.rs:208-241), the STF slider loop of the RGB Compose panel, on the tone editor's kernel:
+ * apply_stf_f32 x 3 with the explicit stf[c] normalised with the cached stats[c] (:224-230), no levels, no curves,
+ * apply_scnr_inplace whenever a config is present (has_scnr, :232-234) and render_rgb_preview (:237).  The command has no amount test
+ * of its own; what remains is apply_scnr_inplace's (scnr.rs:28-31: clamp to 0 ..= 1, return below 1e-7), which lets a NaN amount
+ * through where ab_apply_tone_composite's amount > 1e-7 (curves.rs:149) does not.  Planes and bytes are bit for bit ab_apply_stf_f32
+ * x 3 + ab_apply_scnr_inplace + ab_render_rgb_preview with stf NULL; for amount > 1e-7, ab_apply_tone_composite's with the same
+ * explicit STFs.  Arguments, outputs, launches and the AB_ERR_INVALID cases are ab_apply_tone_composite's, and a NULL stf, or has_scnr
+ * with a NULL scnr.  update_composite_channel_cmd (:255-293) beside it is ab_resample_image + ab_compute_image_stats. */
+AB_API int ab_restretch_composite(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_plane *b, const ab_image_stats stats[3],
+                                  const ab_stf_params stf[3], int32_t has_scnr, const ab_scnr_config *scnr, int64_t max_dim,
+                                  ab_plane_mut *out_planes, uint8_t *out_rgb8, int32_t out_on_device);
 
 /* ---- opening a file: cmd/io/mod.rs (process_fits :105-126, process_fits_full :129-172, process_rgb_fits :33-102) and the histogram
  * panel's compute_histogram (cmd/analysis/mod.rs:22-53), up to the PNG encoder and the JSON --------------------------------------- */
@@ -1547,6 +1558,40 @@ typedef struct {
 AB_API int ab_background_step(ab_ctx *ctx, const ab_plane *img, const ab_background_config *cfg, int64_t max_dim, ab_plane_mut *out_corrected,
                               ab_plane_mut *out_model, uint8_t *out_corrected_u8, uint8_t *out_model_u8, int32_t out_on_device,
                               ab_background_step_info *info);
+
+/* ---- the RGB Compose panel: cmd/compose/rgb.rs (compose_rgb_cmd :43-205) ----------------------------------------------------------------- */
+typedef struct {
+    ab_processed_rgb_info rgb;          /* what ab_process_rgb reports: dims, STFs, ChannelStats, offsets, scnr_applied, resampled, stats_wb */
+    uint64_t preview_rows, preview_cols;
+    int32_t lrgb_applied, l_resampled;  /* LRGB_APPLIED (:118-151); L was resampled to the composite's dims (:124-128) */
+    ab_image_stats l_stats;             /* stf::analyze of the matched L (:133) and auto_stf of it (:134); zeros when L is absent or */
+    ab_stf_params l_stf;                /* auto_stretch == 0 */
+} ab_compose_rgb_info;
+/* compose_rgb_cmd (cmd/compose/rgb.rs:43-205) from its loaded entries to the PNG encoder's input and the JSON, as one chain:
+ * process_rgb (:99-104), the L branch (:118-151: resample_image when L's dims differ, stf::analyze + auto_stf + apply_stf_f32 when
+ * auto_stretch, apply_lrgb with lrgb_lightness / lrgb_chrominance) and render_rgb_preview (:155-161).
+ * l, r, g, b: nullable, host or device, any float-aligned address; at least two of r / g / b.  out_pre (required, [3]): what becomes
+ * __composite_* / __composite_orig_* (:106-116) -- the white-balanced, aligned, pre-stretch planes at the largest channel's dims; the
+ * channels land there directly.  out_planes (nullable, [3]): the final processed.r / g / b the command drops.  out_rgb8 (nullable):
+ * preview_rows x preview_cols x 3 bytes with the dims of ab_preview_dims(rows, cols, max_dim), host or device (out_on_device), ANY
+ * byte address.  info (nullable).
+ * The pre-white-balance statistics visit the host once and only for WhiteBalance::Auto (ab_select_wb_reference); every other
+ * statistic, the (linked) auto-STF, the compose-local transforms and L's transform are formed on the device.  One launch scales the
+ * channels whose (mult as f32 - 1).abs() >= 1e-7 and writes merge_for_stf's plane when linked; one launch does the compose-local STF,
+ * SCNR, L's stretch, apply_lrgb and the packing in registers -- only the picked pixels when out_planes is NULL on an image above
+ * max_dim, two launches (planes, then the pick) when it is given there.  One final synchronisation fetches info and the host outputs
+ * (none with info NULL and device outputs); registration keeps its own.
+ * out_pre, out_planes, bytes, offsets, STFs and statistics are bit for bit ab_process_rgb -> ab_resample_image ->
+ * ab_compute_image_stats -> ab_auto_stf -> ab_apply_stf_f32 -> ab_apply_lrgb -> ab_render_rgb_preview (stf NULL), except the
+ * statistics' mean, which agrees to 1e-12 relative (the statistics routes sum in different orders).
+ * Errors: "Need at least 2 channels for RGB compose (got N)" (rgb.rs:217) and "Channel dimension ratio ...x exceeds 8x limit..."
+ * (:61-75) as ab_process_rgb; apply_lrgb's dims error cannot occur (L is resampled first).  A NULL cfg or out_pre, wrong output dims,
+ * rows * cols >= 2^31, max_dim < 1 or an output that overlaps an input or another output -> AB_ERR_INVALID before anything touches
+ * the device. */
+AB_API int ab_compose_rgb(ab_ctx *ctx, const ab_plane *l, const ab_plane *r, const ab_plane *g, const ab_plane *b,
+                          const ab_rgb_compose_config *cfg, float lrgb_lightness, float lrgb_chrominance, int64_t max_dim,
+                          ab_plane_mut *out_pre, ab_plane_mut *out_planes, uint8_t *out_rgb8, int32_t out_on_device,
+                          ab_compose_rgb_info *info);
 
 /* ---- bench support: a plain float4 device copy, the measured HBM ceiling ---- */
 AB_API int ab_bench_copy(ab_ctx *ctx, const float *src_dev, float *dst_dev, size_t n_floats);
