@@ -233,6 +233,115 @@ __global__ __launch_bounds__(256) void warp_kernel(const float *__restrict__ src
         if (live[u]) out[(size_t)piece_y * out_cols + x0 + 256 * u] = r[u];
 }
 
+// one Catmull-Rom weight of catmull_weights_fused (the same expression, so the same bits): the shared path below forms a y weight
+// where it is used instead of holding K x 4 of them in registers
+template <int J>
+__device__ __forceinline__ double catmull_weight_fused(double f) {
+    if constexpr (J == 0) return cr_outer_fused(fabs(f + 1.0));
+    if constexpr (J == 1) return cr_inner(fabs(f));
+    if constexpr (J == 2) return cr_inner(fabs(f - 1.0));
+    return cr_outer_fused(fabs(f - 2.0));
+}
+
+// warp_kernel for transforms that are close to a translation (|d - 1| and |b| <= 1/64: ab_warp_rows_device decides): one lane owns
+// one output column and K consecutive output rows.  The pixel below almost always samples the same four source columns and three of
+// the same four source rows, so where that holds for a whole wave the K footprints are walked as ONE column strip of K + 3 source
+// rows: each tap is loaded and converted once and serves up to four pixels (16 K loads, conversions and 4 K row addresses become
+// 4 (K + 3) and K + 3).  Per pixel the products and sums are the per-pixel kernel's, in its order, so every output bit is unchanged.
+// A wave that cannot share -- frame borders, a column crossing inside a group, a ragged last group or last piece -- runs the
+// per-pixel body for each of its K rows, at the per-pixel kernel's cost.  Groups are aligned to the band's first row (row0), not to
+// the image; `nrows` is the band's height (the grid has ceil(nrows / K) rows of workgroups).
+template <int K>
+__global__ __launch_bounds__(256) void warp_kernel_shared(const float *__restrict__ src, int src_rows, int src_cols, double a, double b,
+                                                          double tx, double c, double d, double ty, int out_rows, int out_cols,
+                                                          float *__restrict__ out, int row0, int nrows) {
+    unsigned int piece_x, piece_y;
+    xcd_band_piece(piece_x, piece_y);
+    const int x = piece_x * 256 + threadIdx.x;
+    const int yb = piece_y * K;  // the group's first row within the band
+    const bool col_live = x < out_cols;
+    const double xf = (double)x;
+    const double axf = a * xf, cxf = c * xf;  // (the same correctly rounded products for each of the K rows)
+    int ix[K], iy[K];
+    double frx[K], fry[K];
+    bool in[K], live[K];
+    bool share = true;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const double yf = (double)(yb + k + row0);
+        const double sx = axf + b * yf + tx;
+        const double sy = cxf + d * yf + ty;
+        const double fx = floor(sx), fy = floor(sy);
+        asm("v_cvt_i32_f64 %0, %1" : "=v"(ix[k]) : "v"(fx));
+        asm("v_cvt_i32_f64 %0, %1" : "=v"(iy[k]) : "v"(fy));
+        live[k] = col_live && yb + k < nrows;
+        in[k] = live[k] && (unsigned)ix[k] < (unsigned)(src_cols - 1) && (unsigned)iy[k] < (unsigned)(src_rows - 1);
+        frx[k] = sx - fx;
+        fry[k] = sy - fy;
+        const bool interior = ix[k] >= 1 && ix[k] + 2 < src_cols && iy[k] >= 1 && iy[k] + 2 < src_rows;
+        share = share && in[k] && interior && ix[k] == ix[0] && iy[k] == iy[0] + k;
+    }
+    float r[K];
+    // THE INVARIANT of the shared path: it loads exactly the union of the taps the K per-pixel samplers would load -- columns
+    // ix[0] - 1 .. ix[0] + 2 of rows iy[0] - 1 .. iy[0] + K + 1 -- and forms no other address.  Every pixel of the group is live, inside
+    // and interior with ix[k] = ix[0] and iy[k] = iy[0] + k, so that rectangle IS the union of the K 4 x 4 footprints; nothing is
+    // loaded for a pixel that would not sample.  ab_warp_image_rows_from_band hands this kernel a base pointer moved back by the
+    // band's first row and only warp_source_rows' exact hull of the sampling pixels' footprints behind it: a row read beyond that
+    // union is a memory fault.
+    if (__all(share)) {
+        const float *p = src + (iy[0] - 1) * src_cols + (ix[0] - 1);
+        double wx[K][4], val[K];
+#pragma unroll
+        for (int s = 0; s < K + 3; ++s) {
+            const float *row = p + s * src_cols;
+            const double t0 = (double)row[0], t1 = (double)row[1], t2 = (double)row[2], t3 = (double)row[3];
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const int j = s - k;  // source row s is tap row j of pixel k
+                if (j < 0 || j > 3) continue;
+                if (j == 0) catmull_weights_fused(frx[k], wx[k][0], wx[k][1], wx[k][2], wx[k][3]);
+                double row_val = t0 * wx[k][0];
+                row_val += t1 * wx[k][1];
+                row_val += t2 * wx[k][2];
+                row_val += t3 * wx[k][3];
+                const double wy = j == 0 ? catmull_weight_fused<0>(fry[k])
+                                : j == 1 ? catmull_weight_fused<1>(fry[k])
+                                : j == 2 ? catmull_weight_fused<2>(fry[k])
+                                         : catmull_weight_fused<3>(fry[k]);
+                const double t = row_val * wy;
+                val[k] = (j == 0) ? t : val[k] + t;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) r[k] = (float)val[k];
+    } else {  // the per-pixel body, row by row
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            double wx0, wx1, wx2, wx3, wy0, wy1, wy2, wy3;
+            catmull_weights_fused(frx[k], wx0, wx1, wx2, wx3);  // (of no consequence where `in` is false)
+            catmull_weights_fused(fry[k], wy0, wy1, wy2, wy3);
+            const bool interior = ix[k] >= 1 && ix[k] + 2 < src_cols && iy[k] >= 1 && iy[k] + 2 < src_rows;
+            r[k] = 0.0f;
+            if (__all(interior || !in[k])) {
+                if (in[k]) r[k] = bicubic_taps_interior(src, src_cols, ix[k], iy[k], wx0, wx1, wx2, wx3, wy0, wy1, wy2, wy3);
+            } else if (in[k]) {
+                r[k] = bicubic_taps(src, src_rows, src_cols, src_cols, ix[k], iy[k], wx0, wx1, wx2, wx3, wy0, wy1, wy2, wy3);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        if (live[k]) out[(size_t)(yb + k) * out_cols + x] = r[k];
+}
+
+template <int K>
+void launch_warp_shared(ab_ctx *ctx, unsigned lds, const float *src, int64_t src_rows, int64_t src_cols, const double t[6], int64_t out_rows,
+                        int64_t out_cols, int64_t row0, int64_t nrows, float *out) {
+    const dim3 grid((unsigned)((out_cols + 255) / 256), (unsigned)((nrows + K - 1) / K)), block(256);
+    hipLaunchKernelGGL(warp_kernel_shared<K>, grid, block, lds, ctx->stream, src, (int)src_rows, (int)src_cols, t[0], t[1], t[2], t[3], t[4],
+                       t[5], (int)out_rows, (int)out_cols, out, (int)row0, (int)nrows);
+}
+
 // resample.rs:41-58: target pixel centres mapped onto the source grid
 __global__ __launch_bounds__(256) void resample_kernel(const float *__restrict__ src, int src_rows, int src_cols, double scale_y,
                                                        double scale_x, double half_shift_y, double half_shift_x, int out_cols,
@@ -298,6 +407,7 @@ int ab_warp_device(ab_ctx *ctx, const float *src, int64_t src_rows, int64_t src_
 
 // rows [row0, row0 + nrows) of warp_image(src, t, out_rows, out_cols) into the contiguous nrows x out_cols plane `out`
 constexpr long kWarpLdsKB = 0;  // (see ab_warp_rows_device)
+constexpr int kWarpShareK = 3;  // output rows per lane of warp_kernel_shared (the K sweep: LABNOTES 33)
 int ab_warp_rows_device(ab_ctx *ctx, const float *src, int64_t src_rows, int64_t src_cols, const double t[6], int64_t out_rows,
                         int64_t out_cols, int64_t row0, int64_t nrows, float *out) {
     AB_HIP(ctx, hipSetDevice(ctx->device));
@@ -335,12 +445,29 @@ int ab_warp_rows_device(ab_ctx *ctx, const float *src, int64_t src_rows, int64_t
         const long kb = e ? atol(e) : kWarpLdsKB;
         return (unsigned)(kb < 0 ? 0 : (kb > 64 ? 64 : kb)) * 1024u;
     }();
-    if (tame)
-        hipLaunchKernelGGL(warp_kernel<false>, grid, block, warp_lds, ctx->stream, src, (int)src_rows, (int)src_cols, t[0], t[1], t[2], t[3],
-                           t[4], t[5], (int)out_rows, (int)out_cols, out, (int)row0);
-    else
-        hipLaunchKernelGGL(warp_kernel<true>, grid, block, warp_lds, ctx->stream, src, (int)src_rows, (int)src_cols, t[0], t[1], t[2], t[3],
-                           t[4], t[5], (int)out_rows, (int)out_cols, out, (int)row0);
+    // Rows can share source taps (warp_kernel_shared) where consecutive output rows step one source row and stay in their source
+    // columns: a property of the transform alone.  Scales, large rotations and the GUARD case keep the per-pixel kernel.
+    int share_k = tame && fabs(t[4] - 1.0) <= 1.0 / 64.0 && fabs(t[1]) <= 1.0 / 64.0 ? kWarpShareK : 0;
+#ifdef AB_DEV_ABLATION  // AB_WARP_SHARE_K = 0 (the per-pixel kernel), 2, 3 or 4: the K sweep (LABNOTES 33)
+    static const int share_env = ab_dev_env("AB_WARP_SHARE_K") ? atoi(ab_dev_env("AB_WARP_SHARE_K")) : kWarpShareK;
+    if (share_k) share_k = share_env;
+#endif
+    switch (share_k) {
+#ifdef AB_DEV_ABLATION
+    case 2: launch_warp_shared<2>(ctx, warp_lds, src, src_rows, src_cols, t, out_rows, out_cols, row0, nrows, out); break;
+    case 3: launch_warp_shared<3>(ctx, warp_lds, src, src_rows, src_cols, t, out_rows, out_cols, row0, nrows, out); break;
+    case 4: launch_warp_shared<4>(ctx, warp_lds, src, src_rows, src_cols, t, out_rows, out_cols, row0, nrows, out); break;
+#else
+    case kWarpShareK: launch_warp_shared<kWarpShareK>(ctx, warp_lds, src, src_rows, src_cols, t, out_rows, out_cols, row0, nrows, out); break;
+#endif
+    default:
+        if (tame)
+            hipLaunchKernelGGL(warp_kernel<false>, grid, block, warp_lds, ctx->stream, src, (int)src_rows, (int)src_cols, t[0], t[1], t[2], t[3],
+                               t[4], t[5], (int)out_rows, (int)out_cols, out, (int)row0);
+        else
+            hipLaunchKernelGGL(warp_kernel<true>, grid, block, warp_lds, ctx->stream, src, (int)src_rows, (int)src_cols, t[0], t[1], t[2], t[3],
+                               t[4], t[5], (int)out_rows, (int)out_cols, out, (int)row0);
+    }
     AB_HIP(ctx, hipGetLastError());
     return AB_OK;
 }

@@ -79,7 +79,7 @@ def main(path):
             fam[k][1] = max(fam[k][1], e - t0)
         print("  first start .. last end (ms): " + ", ".join(f"{k} {v[0] / 1e6:.2f}..{v[1] / 1e6:.2f}" for k, v in sorted(fam.items(), key=lambda kv: kv[1][0])
                                                               if k in ("subsample_many_kernel", "percentiles_many_reg_kernel", "tile_background_stream_kernel", "label_bgtile_many_kernel",
-                                                                       "comp_select_many_kernel", "tri_vote_wide_many_kernel", "votes_reduce_many_kernel", "warp_kernel")))
+                                                                       "comp_select_many_kernel", "tri_vote_wide_many_kernel", "votes_reduce_many_kernel", "warp_kernel", "warp_kernel_shared")))
         # the tail: what runs in the last 1.5 ms
         tail = [(n, s, e) for n, s, e in b if e > t1 - 1_500_000]
         print("  last 1.5 ms: " + ", ".join(f"{k}x{c}" for k, c in collections.Counter(short(n) for n, _, _ in tail).most_common(8)))
