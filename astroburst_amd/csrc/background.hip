@@ -14,16 +14,16 @@
 //     median) is applied in f32.
 // Host work: the <= 32 x 32 samples' kappa-sigma rejection and the <= 21-term least-squares fit
 // (Gaussian elimination with partial pivoting, f64) -- scalar maths the reference also runs serially.
-#include "ab_common.hpp"
 #include "background_device.hpp"
 #include "block_select.hpp"
+#include "entry_host.hpp"
 
 #include <algorithm>
 #include <cmath>
 
 namespace {
 
-constexpr int kBlock = kPolyBlock;
+static_assert(kBlock == kPolyBlock, "the model kernels and the maps share one block size");
 constexpr float kMadToSigmaF32 = (float)1.4826;
 
 // ---- grid-cell medians (background.rs:151-190) ---------------------------------------------------------
@@ -169,34 +169,27 @@ int ab_background_sample_fit(ab_ctx *ctx, const float *img_dev, int64_t rows, in
     const int margin_h = cell_h / 4, margin_w = cell_w / 4, inner_h = cell_h - 2 * margin_h, inner_w = cell_w - 2 * margin_w;
     CellOut *dcells = nullptr;
     fit->degree = degree;
-#define BG_TRY(expr) AB_TRY(expr)
-#define BG_HIP(call)                                                                                         \
-    do {                                                                                                     \
-        hipError_t e_ = (call);                                                                              \
-        if (e_ != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
-
-    BG_TRY(ab_workspace(ctx, AB_WS_SCOPE1, (size_t)grid * grid * sizeof(CellOut), (void **)&dcells));  // (kept between calls: ab_common.hpp)
-    BG_TRY(ab_progress(ctx, "sampling background", 1, 4));  // background.rs:63-66
+    AB_TRY(ab_workspace(ctx, AB_WS_SCOPE1, (size_t)grid * grid * sizeof(CellOut), (void **)&dcells));  // (kept between calls: ab_common.hpp)
+    AB_TRY(ab_progress(ctx, "sampling background", 1, 4));  // background.rs:63-66
 
     // global median / MAD over finite, > 0 pixels (:135-146)
     float global_median, global_mad;
     ab_plane_sel sel;
     sel.data = img_dev;
     sel.n = npix;
-    BG_TRY(ab_plane_median_f32(ctx, sel, &global_median, nullptr));
+    AB_TRY(ab_plane_median_f32(ctx, sel, &global_median, nullptr));
     sel.use_dev = 1;
     sel.center = global_median;
-    BG_TRY(ab_plane_median_f32(ctx, sel, &global_mad, nullptr));
+    AB_TRY(ab_plane_median_f32(ctx, sel, &global_mad, nullptr));
     const float sigma = global_mad * kMadToSigmaF32;
 
     // grid-cell medians (:150-190)
     hipLaunchKernelGGL(cell_median_kernel, dim3(grid * grid), dim3(absel::kBlock), 0, ctx->stream, img_dev, cols, grid, cell_h,
                        cell_w, margin_h, margin_w, inner_h, inner_w, dcells);
-    BG_HIP(hipGetLastError());
+    AB_HIP(ctx, hipGetLastError());
     std::vector<CellOut> cells((size_t)grid * grid);
-    BG_HIP(hipMemcpyAsync(cells.data(), dcells, cells.size() * sizeof(CellOut), hipMemcpyDeviceToHost, ctx->stream));
-    BG_HIP(hipStreamSynchronize(ctx->stream));
+    AB_HIP(ctx, hipMemcpyAsync(cells.data(), dcells, cells.size() * sizeof(CellOut), hipMemcpyDeviceToHost, ctx->stream));
+    AB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<Sample> samples;
     const size_t total_cell = (size_t)inner_h * inner_w;
     for (int gy = 0; gy < grid; ++gy)
@@ -227,7 +220,7 @@ int ab_background_sample_fit(ab_ctx *ctx, const float *img_dev, int64_t rows, in
     if (samples.size() < min_samples)  // :71-77
         return ab_set_error(ctx, AB_ERR_INVALID, "Not enough background samples (%zu) for polynomial degree %d", samples.size(), degree);
 
-    BG_TRY(ab_progress(ctx, "fitting polynomial surface", 2, 4));  // background.rs:79-84 (cancel checked, then tick)
+    AB_TRY(ab_progress(ctx, "fitting polynomial surface", 2, 4));  // background.rs:79-84 (cancel checked, then tick)
     // fit_polynomial_surface (:251-290)
     const double row_scale = (double)rows, col_scale = (double)cols;
     std::vector<double> ata(n_terms * n_terms, 0.0), atb(n_terms, 0.0);
@@ -266,8 +259,6 @@ int ab_background_sample_fit(ab_ctx *ctx, const float *img_dev, int64_t rows, in
     }
     fit->rms_residual = std::sqrt(sum_sq / (double)samples.size());
     return AB_OK;
-#undef BG_TRY
-#undef BG_HIP
 }
 
 extern "C" int ab_extract_background(ab_ctx *ctx, const ab_plane *img, const ab_background_config *cfg, ab_plane_mut *out_model,
@@ -281,40 +272,15 @@ extern "C" int ab_extract_background(ab_ctx *ctx, const ab_plane *img, const ab_
     const int degree = (int)cfg->poly_degree;
     AB_HIP(ctx, hipSetDevice(ctx->device));
 
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    float *model = nullptr;
-    StagedOut so_corr, so_model;
-    bool corr_open = false, model_open = false;
-    int rc = AB_OK;
-    auto cleanup = [&]() {
-        if (corr_open) ab_stage_out_abort(ctx, &so_corr);
-        if (model_open) ab_stage_out_abort(ctx, &so_model);
-        (void)hipStreamSynchronize(ctx->stream);
-        ab_stage_release(ctx, &in);
-    };
-#define BG_TRY(expr)          \
-    do {                      \
-        rc = (expr);          \
-        if (rc != AB_OK) {    \
-            cleanup();        \
-            return rc;        \
-        }                     \
-    } while (0)
-#define BG_HIP(call)                                                                               \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            rc = ab_set_error(ctx, AB_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_));     \
-            cleanup();                                                                             \
-            return rc;                                                                             \
-        }                                                                                          \
-    } while (0)
+    Scope sc(ctx);
+    const float *in = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    float *model = nullptr, *corr = nullptr;
 
     ab_background_fit fit;
-    rc = ab_background_sample_fit(ctx, in.dptr, rows, cols, cfg, &fit);
+    const int rc = ab_background_sample_fit(ctx, in, rows, cols, cfg, &fit);
     if (info) info->sample_count = fit.sample_count;
-    BG_TRY(rc);
+    AB_TRY(rc);
     PolyArgs pa;
     memset(&pa, 0, sizeof pa);
     pa.degree = degree;
@@ -325,15 +291,12 @@ extern "C" int ab_extract_background(ab_ctx *ctx, const ab_plane *img, const ab_
     memcpy(pa.coeffs, fit.coeffs, sizeof pa.coeffs);
     if (info) memcpy(info->coeffs, pa.coeffs, sizeof pa.coeffs);
 
-    BG_TRY(ab_progress(ctx, "generating model", 3, 4));  // background.rs:88-93
+    AB_TRY(ab_progress(ctx, "generating model", 3, 4));  // background.rs:88-93
     // evaluate_polynomial_surface + apply_correction (:307-383)
-    if (out_model) {
-        BG_TRY(ab_stage_out_begin(ctx, out_model, &so_model));
-        model_open = true;
-        model = so_model.dptr;
-    } else {
-        BG_TRY(ab_workspace(ctx, AB_WS_SCOPE0, (size_t)npix * sizeof(float), (void **)&model));
-    }
+    if (out_model)
+        AB_TRY(sc.stage_out(out_model, &model));
+    else
+        AB_TRY(ab_workspace(ctx, AB_WS_SCOPE0, (size_t)npix * sizeof(float), (void **)&model));
     {
         const int pow2_cols = (cols & (cols - 1)) == 0 ? 1 : 0;
         const double inv_cols = 1.0 / (double)cols;  // exact when cols is a power of two
@@ -347,28 +310,19 @@ extern "C" int ab_extract_background(ab_ctx *ctx, const ab_plane *img, const ab_
         default: hipLaunchKernelGGL(poly_model_kernel<5>, pgrid, pblock, 0, ctx->stream, pa, model, pow2_cols, inv_cols); break;
         }
     }
-    BG_HIP(hipGetLastError());
+    AB_HIP(ctx, hipGetLastError());
     float model_median = 0.0f;
     ab_plane_sel msel;
     msel.data = model;
     msel.n = npix;
-    BG_TRY(ab_plane_median_f32(ctx, msel, &model_median, nullptr));
-    BG_TRY(ab_progress(ctx, "applying correction", 4, 4));  // background.rs:97-99
-    BG_TRY(ab_stage_out_begin(ctx, out_corrected, &so_corr));
-    corr_open = true;
+    AB_TRY(ab_plane_median_f32(ctx, msel, &model_median, nullptr));
+    AB_TRY(ab_progress(ctx, "applying correction", 4, 4));  // background.rs:97-99
+    AB_TRY(sc.stage_out(out_corrected, &corr));
     const int g = (int)std::min<int64_t>((npix + kBlock - 1) / kBlock, (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8);
-    hipLaunchKernelGGL(bg_apply_kernel, dim3(g), dim3(kBlock), 0, ctx->stream, in.dptr, model, npix, (int)cfg->mode, model_median,
-                       so_corr.dptr);
-    BG_HIP(hipGetLastError());
-    rc = ab_stage_out_finish(ctx, &so_corr);
-    corr_open = false;
-    if (rc == AB_OK && model_open) {
-        rc = ab_stage_out_finish(ctx, &so_model);
-        model_open = false;
-    }
-    if (rc == AB_OK && info) info->rms_residual = fit.rms_residual;
-    cleanup();
-    return rc;
-#undef BG_TRY
-#undef BG_HIP
+    hipLaunchKernelGGL(bg_apply_kernel, dim3(g), dim3(kBlock), 0, ctx->stream, in, model, npix, (int)cfg->mode, model_median, corr);
+    AB_HIP(ctx, hipGetLastError());
+    AB_TRY(sc.finish_outs());
+    if (info) info->rms_residual = fit.rms_residual;
+    (void)hipStreamSynchronize(ctx->stream);  // device planes too are written when the call returns
+    return AB_OK;
 } AB_CATCH(ctx)

@@ -12,8 +12,8 @@
 // below the HBM ridge, so it is a VALU kernel, not an MFMA one; products and sums are kept as
 // separate f32 operations in weight order (no FMA contraction) so the result is bit-identical to
 // the reference's `rv += v * rw`.  The curve LUT (4096 f32 = 16 KiB) is staged in LDS.
-#include "ab_common.hpp"
 #include "arcsinh_device.hpp"
+#include "entry_host.hpp"
 #include "scnr_device.hpp"
 
 #include <algorithm>
@@ -21,7 +21,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kMaxBlendChannels = 16;
 constexpr int kMaxBlendWeights = 32;
 
@@ -215,21 +214,15 @@ int unary_map(ab_ctx *ctx, const ab_plane *img, ab_plane_mut *out, F launch) {
     AB_CHECK(ctx, img && out, "null plane");
     AB_CHECK(ctx, img->rows == out->rows && img->cols == out->cols, "output dims must equal input dims");
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    StagedOut so;
-    int rc = ab_stage_out_begin(ctx, out, &so);
-    if (rc == AB_OK) {
-        launch(in.dptr, in.rows * in.cols, so.dptr);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-        if (rc == AB_OK)
-            rc = ab_stage_out_finish(ctx, &so);
-        else
-            ab_stage_out_abort(ctx, &so);
-    }
-    ab_stage_release(ctx, &in);
-    return rc;
+    Scope sc(ctx);
+    const float *in = nullptr;
+    float *o = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    AB_TRY(sc.stage_out(out, &o));
+    launch(in, img->rows * img->cols, o);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
+    return sc.finish_outs();
 }
 
 }  // namespace
@@ -272,20 +265,19 @@ int ab_apply_scnr_inplace(ab_ctx *ctx, ab_plane_mut *r, ab_plane_mut *g, ab_plan
     AB_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t n = r->rows * r->cols;
     float *dr = r->data, *dg = g->data, *db = b->data;
+    Scope sc(ctx);
     void *tmp = nullptr;
     if (!r->on_device) {
         const int64_t np4 = (n + 3) & ~int64_t(3);  // keep the three staged planes 16-byte aligned
         AB_HIP(ctx, hipMalloc(&tmp, 3 * np4 * sizeof(float)));
+        sc.adopt(tmp);
         dr = (float *)tmp;
         dg = dr + np4;
         db = dg + np4;
         hipError_t e = hipMemcpyAsync(dr, r->data, n * 4, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(dg, g->data, n * 4, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(db, b->data, n * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(tmp);
-            return ab_set_error(ctx, AB_ERR_HIP, "H2D: %s", hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "H2D: %s", hipGetErrorString(e));
     }
     const int vec = (((uintptr_t)dr | (uintptr_t)dg | (uintptr_t)db) & 15) == 0;
     hipLaunchKernelGGL(scnr_kernel, dim3(ab_stream_grid(ctx, vec ? (n >> 2) : n)), dim3(kBlock), 0, ctx->stream, dr, dg, db, n,
@@ -297,7 +289,6 @@ int ab_apply_scnr_inplace(ab_ctx *ctx, ab_plane_mut *r, ab_plane_mut *g, ab_plan
         if (e == hipSuccess) e = hipMemcpyAsync(b->data, db, n * 4, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     }
-    if (tmp) (void)hipFree(tmp);
     if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "SCNR: %s", hipGetErrorString(e));
     return AB_OK;
 } AB_CATCH(ctx)
@@ -315,29 +306,14 @@ int ab_blend_channels(ab_ctx *ctx, const ab_plane *channels, size_t n_channels, 
     size_t nw = 0;
     for (size_t w = 0; w < n_weights; ++w) nw += weights[w].channel_idx < n_channels;
     AB_CHECK(ctx, nw <= (size_t)kMaxBlendWeights, "at most %d blend weights", kMaxBlendWeights);
-    std::vector<StagedPlane> st(n_channels);
+    Scope sc(ctx);
     const float *ch[kMaxBlendChannels];
-    int rc = AB_OK;
-    size_t staged = 0;
-    for (; staged < n_channels; ++staged) {
-        rc = ab_stage_in(ctx, &channels[staged], &st[staged]);
-        if (rc != AB_OK) break;
-        ch[staged] = st[staged].dptr;
-    }
-    StagedOut so[3];
+    for (size_t i = 0; i < n_channels; ++i) AB_TRY(sc.stage_in(&channels[i], &ch[i]));
     ab_plane_mut *outs[3] = {r, g, b};
-    int opened = 0;
-    for (; rc == AB_OK && opened < 3; ++opened) rc = ab_stage_out_begin(ctx, outs[opened], &so[opened]);
-    if (rc != AB_OK && opened > 0) --opened;
-    if (rc == AB_OK) rc = ab_blend_device(ctx, ch, n_channels, weights, n_weights, n, so[0].dptr, so[1].dptr, so[2].dptr);
-    for (int i = 0; i < opened; ++i) {
-        if (rc == AB_OK)
-            rc = ab_stage_out_finish(ctx, &so[i]);
-        else
-            ab_stage_out_abort(ctx, &so[i]);
-    }
-    for (size_t i = 0; i < staged; ++i) ab_stage_release(ctx, &st[i]);
-    return rc;
+    float *o[3];
+    for (int c = 0; c < 3; ++c) AB_TRY(sc.stage_out(outs[c], &o[c]));
+    AB_TRY(ab_blend_device(ctx, ch, n_channels, weights, n_weights, n, o[0], o[1], o[2]));
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 int ab_spline_lut_from_points(const double *points_xy, size_t n_in, float *lut4096) try {
@@ -425,31 +401,18 @@ int ab_luminance(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, const ab_pla
                       out->rows == r->rows && out->cols == r->cols,
              "luminance: R, G, B and the output must share dims");
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedPlane sr, sg, sb;
-    AB_TRY(ab_stage_in(ctx, r, &sr));
-    int rc = ab_stage_in(ctx, g, &sg);
-    if (rc == AB_OK) {
-        rc = ab_stage_in(ctx, b, &sb);
-        if (rc == AB_OK) {
-            StagedOut so;
-            rc = ab_stage_out_begin(ctx, out, &so);
-            if (rc == AB_OK) {
-                const int64_t n = r->rows * r->cols;
-                hipLaunchKernelGGL(luminance_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, sr.dptr, sg.dptr,
-                                   sb.dptr, n, so.dptr);
-                hipError_t e = hipGetLastError();
-                if (e != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "luminance: %s", hipGetErrorString(e));
-                if (rc == AB_OK)
-                    rc = ab_stage_out_finish(ctx, &so);
-                else
-                    ab_stage_out_abort(ctx, &so);
-            }
-            ab_stage_release(ctx, &sb);
-        }
-        ab_stage_release(ctx, &sg);
-    }
-    ab_stage_release(ctx, &sr);
-    return rc;
+    Scope sc(ctx);
+    const float *dr = nullptr, *dg = nullptr, *db = nullptr;
+    float *o = nullptr;
+    AB_TRY(sc.stage_in(r, &dr));
+    AB_TRY(sc.stage_in(g, &dg));
+    AB_TRY(sc.stage_in(b, &db));
+    AB_TRY(sc.stage_out(out, &o));
+    const int64_t n = r->rows * r->cols;
+    hipLaunchKernelGGL(luminance_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, dr, dg, db, n, o);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "luminance: %s", hipGetErrorString(e));
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 int ab_calibrate_image(ab_ctx *ctx, const ab_plane *raw, const ab_plane *bias, const ab_plane *dark, const ab_plane *flat,
@@ -460,23 +423,14 @@ int ab_calibrate_image(ab_ctx *ctx, const ab_plane *raw, const ab_plane *bias, c
     for (int i = 0; i < 3; ++i)
         if (opt[i]) AB_CHECK(ctx, opt[i]->rows == raw->rows && opt[i]->cols == raw->cols, "master frame dims differ from the raw frame");
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedPlane so_[3];
+    Scope sc(ctx);  // the masters outlive unary_map's own scope
     const float *d[3] = {nullptr, nullptr, nullptr};
-    int staged = 0, rc = AB_OK;
-    for (; staged < 3; ++staged) {
-        if (!opt[staged]) continue;
-        rc = ab_stage_in(ctx, opt[staged], &so_[staged]);
-        if (rc != AB_OK) break;
-        d[staged] = so_[staged].dptr;
-    }
-    if (rc == AB_OK)
-        rc = unary_map(ctx, raw, out, [&](const float *in, int64_t n, float *o) {
-            hipLaunchKernelGGL(calibrate_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in, d[0], d[1], d[2],
-                               dark_exposure_ratio, n, o);
-        });
-    for (int i = 0; i < staged; ++i)
-        if (opt[i]) ab_stage_release(ctx, &so_[i]);
-    return rc;
+    for (int i = 0; i < 3; ++i)
+        if (opt[i]) AB_TRY(sc.stage_in(opt[i], &d[i]));
+    return unary_map(ctx, raw, out, [&](const float *in, int64_t n, float *o) {
+        hipLaunchKernelGGL(calibrate_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in, d[0], d[1], d[2],
+                           dark_exposure_ratio, n, o);
+    });
 } AB_CATCH(ctx)
 
 }  // extern "C"

@@ -15,7 +15,7 @@
 //   frames  normalise -> per-frame min / max -> bytes in two launches for all frames; the asinh is evaluated in f64 (the result is
 //           DEFINED as the f32 rounding of the f64 asinh, include/astroburst_hip.h) and recomputed instead of stored.
 // No float atomics anywhere: the min / max go through per-block partials.
-#include "ab_common.hpp"
+#include "entry_host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -27,7 +27,6 @@ constexpr int kMedPix = 64;      // pixels of a median workgroup = lanes of a wa
 constexpr int kMedBins = 256;    // 8-bit digits
 constexpr int kMedMaxWaves = 16;
 constexpr int kMedAhead = 4;     // loads in flight per wave in a histogram pass
-constexpr int kBlock = 256;
 constexpr int kMaxPartials = 64;  // min / max partials per exported frame
 
 __device__ __forceinline__ bool cube_valid(float v, int rule) {
@@ -155,26 +154,6 @@ __global__ __launch_bounds__(kBlock) void cube_normalize_kernel(const float *__r
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) out[i] = cube_normalize(in[i], t);
 }
 
-__device__ __forceinline__ void block_minmax(float &mn, float &mx) {
-    __shared__ float smn[kBlock / 64], smx[kBlock / 64];
-    for (int off = 32; off > 0; off >>= 1) {
-        mn = fminf(mn, __shfl_xor(mn, off));
-        mx = fmaxf(mx, __shfl_xor(mx, off));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        smn[threadIdx.x / 64] = mn;
-        smx[threadIdx.x / 64] = mx;
-    }
-    __syncthreads();
-    mn = smn[0];
-    mx = smx[0];
-    for (int w = 1; w < kBlock / 64; ++w) {
-        mn = fminf(mn, smn[w]);
-        mx = fmaxf(mx, smx[w]);
-    }
-    __syncthreads();
-}
-
 // grid (parts, min(frames, 65535)): partial[(frame * parts + blockIdx.x) * 2 + {0, 1}] = min, max of the block's share of the frame
 __global__ __launch_bounds__(kBlock) void cube_frame_minmax_kernel(const float *__restrict__ cube, int64_t plane, int64_t step, int64_t frames,
                                                                    const NormTx t, float *__restrict__ partial) {
@@ -286,25 +265,23 @@ int collapse(ab_ctx *ctx, const ab_cube *cube, int32_t rule, ab_plane_mut *out, 
     AB_TRY(ab_cancel_point(ctx));
     const float *d = nullptr;
     AB_TRY(cube_stage(ctx, cube, &d));
-    StagedOut so;
-    AB_TRY(ab_stage_out_begin(ctx, out, &so));
+    Scope sc(ctx);
+    float *o = nullptr;
+    AB_TRY(sc.stage_out(out, &o));
     const int64_t plane = cube->rows * cube->cols;
     const int64_t groups = (plane + 63) / 64;
     if (!median) {
-        hipLaunchKernelGGL(cube_mean_kernel, dim3((unsigned)groups), dim3(64), 0, ctx->stream, d, cube->depth, plane, (int)rule, so.dptr);
+        hipLaunchKernelGGL(cube_mean_kernel, dim3((unsigned)groups), dim3(64), 0, ctx->stream, d, cube->depth, plane, (int)rule, o);
     } else {
         // waves per workgroup: as many as keep the chip covered when the plane is small, never more than the column can feed
         const int64_t cus = ctx->cu_count > 0 ? ctx->cu_count : 256;
         int waves = groups >= 4 * cus ? 4 : (groups >= 2 * cus ? 8 : kMedMaxWaves);
         while (waves > 1 && (int64_t)waves * kMedAhead > cube->depth) waves /= 2;
-        hipLaunchKernelGGL(cube_median_kernel, dim3((unsigned)groups), dim3(kMedPix * waves), 0, ctx->stream, d, cube->depth, plane, (int)rule, so.dptr);
+        hipLaunchKernelGGL(cube_median_kernel, dim3((unsigned)groups), dim3(kMedPix * waves), 0, ctx->stream, d, cube->depth, plane, (int)rule, o);
     }
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        ab_stage_out_abort(ctx, &so);
-        return ab_set_error(ctx, AB_ERR_HIP, "cube collapse launch failed: %s", hipGetErrorString(e));
-    }
-    return ab_stage_out_finish(ctx, &so);
+    if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "cube collapse launch failed: %s", hipGetErrorString(e));
+    return sc.finish_outs();
 }
 
 }  // namespace
@@ -389,27 +366,16 @@ int ab_cube_normalize_frame(ab_ctx *ctx, const ab_plane *img, const ab_cube_stat
     AB_TRY(stats_tx(ctx, stats, &t));
     AB_HIP(ctx, hipSetDevice(ctx->device));
     AB_TRY(ab_cancel_point(ctx));
-    StagedPlane in;
-    StagedOut so;
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    int rc = ab_stage_out_begin(ctx, out, &so);
-    if (rc != AB_OK) {
-        ab_stage_release(ctx, &in);
-        return rc;
-    }
+    Scope sc(ctx);
+    const float *in = nullptr;
+    float *o = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    AB_TRY(sc.stage_out(out, &o));
     const int64_t n = img->rows * img->cols;
-    const int64_t cap = (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 16;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, cap));
-    hipLaunchKernelGGL(cube_normalize_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, in.dptr, n, t, so.dptr);
+    hipLaunchKernelGGL(cube_normalize_kernel, dim3(ab_stream_grid(ctx, n, kBlock, 16)), dim3(kBlock), 0, ctx->stream, in, n, t, o);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        ab_stage_out_abort(ctx, &so);
-        rc = ab_set_error(ctx, AB_ERR_HIP, "cube_normalize_kernel launch failed: %s", hipGetErrorString(e));
-    } else {
-        rc = ab_stage_out_finish(ctx, &so);
-    }
-    ab_stage_release(ctx, &in);
-    return rc;
+    if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "cube_normalize_kernel launch failed: %s", hipGetErrorString(e));
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 int ab_cube_export_frames(ab_ctx *ctx, const ab_cube *cube, const ab_cube_stats *stats, int64_t frame_step, uint8_t *out_u8, int32_t out_on_device,

@@ -27,7 +27,7 @@
 // non-finite estimate sample, or writes a non-finite ratio, raises a flag in RlState; the update then treats the whole correction as
 // NaN (estimate -> max(NaN, 0) = 0, then the deringing clamp), as the reference does.  A non-finite PSF tap does the same for every
 // iteration.  Finite inputs large enough to overflow the reference's FFT (|x| >= ~1e30) are outside the contract.
-#include "ab_common.hpp"
+#include "entry_host.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -43,7 +43,6 @@ constexpr int kTileW = 2 * kTx;        // 64 output columns (two adjacent per la
 constexpr int kTileH = kRows * kTy;    // 32 output rows
 constexpr int kTap = 8;                // taps per LDS window; the PSF's columns are zero-padded to a multiple of it
 constexpr int kMaxTiledPsf = 63;
-constexpr int kBlock = 256;
 constexpr int kFinishBlock = 256;
 
 struct RlState {
@@ -397,17 +396,14 @@ int ab_richardson_lucy(ab_ctx *ctx, const ab_plane *img, const ab_plane *psf, co
         AB_CHECK(ctx, !ranges_overlap(img->data, bytes, out->data, bytes), "output must not overlap the image");
     }
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedPlane in, kp;
-    StagedOut so;
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    int rc = ab_stage_in(ctx, psf, &kp);
-    if (rc == AB_OK) rc = ab_stage_out_begin(ctx, out, &so);
-    if (rc == AB_OK) rc = rl_device(ctx, in.dptr, in.rows, in.cols, kp.dptr, (int)kp.rows, (int)kp.cols, *cfg, so.dptr, res);
-    if (rc == AB_OK) rc = ab_stage_out_finish(ctx, &so);
-    else ab_stage_out_abort(ctx, &so);
-    ab_stage_release(ctx, &kp);
-    ab_stage_release(ctx, &in);
-    return rc;
+    Scope sc(ctx);
+    const float *in = nullptr, *kp = nullptr;
+    float *o = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    AB_TRY(sc.stage_in(psf, &kp));
+    AB_TRY(sc.stage_out(out, &o));
+    AB_TRY(rl_device(ctx, in, img->rows, img->cols, kp, (int)psf->rows, (int)psf->cols, *cfg, o, res));
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 }  // extern "C"

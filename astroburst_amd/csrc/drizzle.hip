@@ -38,7 +38,7 @@
 //   `dev >= -sigma_low * sigma && dev <= sigma_high * sigma` with dev = v - median monotone in v keeps a contiguous range [a, b).
 // The survivors' f64 sum runs in ascending order of value (the pin oracle/orc_combine.c documents for what select_nth_unstable
 // leaves unspecified).  rejected_pixels: a u64 partial per workgroup, summed in a fixed order by dz_finish_kernel.
-#include "ab_common.hpp"
+#include "entry_host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -67,7 +67,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kFinishBlock = 1024;
 constexpr int kTileW = 64, kTileH = 4;  // the LDS path's workgroup: 64 x 4 output pixels, a wave per output row
 constexpr int kLdsCap = 64;             // lists of up to 64 samples (32 frames) stay in LDS: 256 * 64 * 4 = 64 KiB per workgroup
@@ -550,49 +549,25 @@ int dz_run(ab_ctx *ctx, const ab_plane *planes, size_t n, const double *dx_dy_in
     for (size_t i = 0; i < n; ++i) AB_CHECK(ctx, planes[i].data || planes[i].rows * planes[i].cols == 0, "frame %zu has no data", i);
     AB_TRY(ab_progress(ctx, "drizzle", 0, 1));  // (a cancel requested before the call)
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<StagedPlane> st(n);
     std::vector<const float *> dp(n);
     std::vector<int64_t> ld(n);
     std::vector<double> off(2 * n, 0.0);
-    int rc = AB_OK;
-    size_t staged = 0;
-    for (; staged < n; ++staged) {
-        rc = ab_stage_in(ctx, &planes[staged], &st[staged]);
-        if (rc != AB_OK) break;
-        dp[staged] = st[staged].dptr;
-        ld[staged] = st[staged].cols;  // the crop to the minimum dims (drizzle.rs:258-272) is only a row stride
+    Scope sc(ctx);
+    for (size_t i = 0; i < n; ++i) {
+        AB_TRY(sc.stage_in(&planes[i], &dp[i]));
+        ld[i] = planes[i].cols;  // the crop to the minimum dims (drizzle.rs:258-272) is only a row stride
     }
-    if (rc == AB_OK) {
-        if (dx_dy_in) std::copy(dx_dy_in, dx_dy_in + 2 * n, off.begin());
-        else if (cfg->align && D.in_rows > 0 && D.in_cols > 0) rc = dz_offsets(ctx, dp.data(), ld.data(), n, D, *cfg, off.data());
-    }
-    if (rc == AB_OK && !dx_dy_in)
+    if (dx_dy_in) std::copy(dx_dy_in, dx_dy_in + 2 * n, off.begin());
+    else if (cfg->align && D.in_rows > 0 && D.in_cols > 0) AB_TRY(dz_offsets(ctx, dp.data(), ld.data(), n, D, *cfg, off.data()));
+    if (!dx_dy_in)
         for (size_t i = 0; i < 2 * n; ++i)
-            if (!std::isfinite(off[i])) rc = ab_set_error(ctx, AB_ERR_INVALID, "the alignment returned a non-finite offset for frame %zu", i / 2);
-    StagedOut so_i, so_w;
-    bool open_i = false, open_w = false;
-    if (rc == AB_OK) {
-        rc = ab_stage_out_begin(ctx, out_image, &so_i);
-        open_i = rc == AB_OK;
-    }
-    if (rc == AB_OK && want_weight) {
-        rc = ab_stage_out_begin(ctx, out_weight, &so_w);
-        open_w = rc == AB_OK;
-    }
+            AB_CHECK(ctx, std::isfinite(off[i]), "the alignment returned a non-finite offset for frame %zu", i / 2);
+    float *image = nullptr, *weight = nullptr;
+    AB_TRY(sc.stage_out(out_image, &image));
+    if (want_weight) AB_TRY(sc.stage_out(out_weight, &weight));
     uint64_t rejected = 0;
-    if (rc == AB_OK) rc = dz_device(ctx, dp.data(), ld.data(), n, off.data(), D, *cfg, so_i.dptr, open_w ? so_w.dptr : nullptr, &rejected);
-    if (rc == AB_OK) {
-        rc = ab_stage_out_finish(ctx, &so_i);
-        open_i = false;
-    }
-    if (rc == AB_OK && open_w) {
-        rc = ab_stage_out_finish(ctx, &so_w);
-        open_w = false;
-    }
-    if (open_i) ab_stage_out_abort(ctx, &so_i);
-    if (open_w) ab_stage_out_abort(ctx, &so_w);
-    for (size_t i = 0; i < staged; ++i) ab_stage_release(ctx, &st[i]);
-    if (rc != AB_OK) return rc;
+    AB_TRY(dz_device(ctx, dp.data(), ld.data(), n, off.data(), D, *cfg, image, weight, &rejected));
+    AB_TRY(sc.finish_outs());
     if (dx_dy_out) std::copy(off.begin(), off.end(), dx_dy_out);
     res->frame_count = n;
     res->output_scale = D.scale;

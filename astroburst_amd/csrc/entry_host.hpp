@@ -1,8 +1,11 @@
-// Host plumbing of the display-side entry points: what is refused before anything touches the device, and what is released when an
-// entry point returns, on an error exit included.  Included by view.hip, tone.hip, rgb_export.hip, render.hip, compose_rgb.hip,
-// masked_stretch.hip, wizard_color.hip, wizard_stretch.hip, wizard_background.hip and compose_step.hip; crop.hip takes fits31 and the scope only (it
-// words its messages by plane number), spcc.hip the scope.  preview.hip does not include it: its own Span (a sweep's four-pixel
-// groups) is another thing.
+// Host plumbing of the entry points that take host or device planes: what is released when an entry point returns, on an error exit
+// or an exception included, and what the display-side ones refuse before anything touches the device.  Included, checks and all, by
+// view.hip, tone.hip, rgb_export.hip, render.hip, compose_rgb.hip, masked_stretch.hip, wizard_color.hip, wizard_stretch.hip,
+// wizard_background.hip and compose_step.hip; crop.hip takes fits31 and the scope only (it words its messages by plane number).  The
+// scope only, with checks worded by themselves: spcc.hip, color.hip, extras.hip, stf.hip, fits.hip, resample.hip, background.hip,
+// subframe.hip, phase_corr.hip, psf.hip, deconv.hip, wavelet.hip, spectrum.hip, synth.hip, drizzle.hip; preview.hip and cube.hip take
+// block_minmax too (preview.hip's four-pixel groups of a sweep are its Groups, not a Span).  Not included by the benchmark's path
+// and the multi-rank code (stats, detect, affine, batch_pipeline, stack_*, sharded, comm), whose plumbing is workspaces and child contexts.
 //   checks      fits31, plane_check, same_dims_check, out_planes_check, preview_of
 //   overlap     overlap_check over Spans.  Two forms of a span, kept apart because the entry points answer differently today:
 //               span_of -- the wizard's steps (wizard_*.hip): host memory counts too, and outputs may not overlap each other;
@@ -11,7 +14,7 @@
 //               at a time, so no output / output pair is tested that was not tested before.
 //   scope       Scope: staged inputs, staged outputs and the call's device planes, released in that order's reverse on return
 //   placement   head16, head_bytes: the pixels before the four-pixel groups
-//   device      nn_index (the preview's nearest-neighbour pick), quantise (its byte)
+//   device      nn_index (the preview's nearest-neighbour pick), quantise (its byte), block_minmax (wave shuffle, then kBlock / 64 LDS words)
 // The streaming grid's size is ab_common.hpp's ab_stream_grid.  A new entry-point file includes this header; it does not copy it.
 #pragma once
 #include "ab_common.hpp"
@@ -88,12 +91,14 @@ Span device_span(const void *p, size_t len, int32_t on_device) { return Span{(ui
 Span device_span(const ab_plane &p) { return device_span(p.data, (size_t)p.rows * (size_t)p.cols * sizeof(float), p.on_device); }
 
 // Releases / aborts everything registered with it when the entry point returns.  The deques never move an element, so a pointer to a
-// staged plane or output stays good for the length of the call, however many follow it.
+// staged plane or output stays good for the length of the call, however many follow it.  A loop that stages one plane per iteration
+// opens a Scope per iteration, inside the call's own; such an inner Scope stages and adopts but must not alloc(): slot numbering starts
+// at zero in each Scope, so its first plane would be the outer one's.
 struct Scope {
     ab_ctx *ctx;
     std::deque<StagedPlane> ins;
     std::deque<StagedOut> outs;
-    std::vector<void *> dev;  // the planes past the eight scope slots
+    std::vector<void *> dev;  // the planes past the eight scope slots, and what adopt() took
     int next_slot = 0;
     explicit Scope(ab_ctx *c) : ctx(c) {}
     ~Scope() {
@@ -136,6 +141,8 @@ struct Scope {
         dev.push_back(*p);
         return AB_OK;
     }
+    // a per-call hipMalloc of the entry point's own, freed with the rest once the stream has drained
+    void adopt(void *p) { dev.push_back(p); }
 };
 
 // the pixels before the first 16-byte group of a float plane
@@ -154,6 +161,27 @@ __device__ __forceinline__ uint32_t quantise(float s) {
     const float c = s < 0.0f ? 0.0f : (s > 1.0f ? 1.0f : s);
     const float x = c * 255.0f;
     return x == x ? (uint32_t)x : 0u;
+}
+
+// wave reduce -> LDS -> every lane holds the block's min / max
+__device__ __forceinline__ void block_minmax(float &mn, float &mx) {
+    __shared__ float smn[kBlock / 64], smx[kBlock / 64];
+    for (int off = 32; off > 0; off >>= 1) {
+        mn = fminf(mn, __shfl_xor(mn, off));
+        mx = fmaxf(mx, __shfl_xor(mx, off));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        smn[threadIdx.x / 64] = mn;
+        smx[threadIdx.x / 64] = mx;
+    }
+    __syncthreads();
+    mn = smn[0];
+    mx = smx[0];
+    for (int w = 1; w < kBlock / 64; ++w) {
+        mn = fminf(mn, smn[w]);
+        mx = fmaxf(mx, smx[w]);
+    }
+    __syncthreads();
 }
 
 }  // namespace

@@ -6,15 +6,13 @@
 // All maps are streaming f32 kernels in the reference's operation order (bit-exact); the one reduction
 // (the master flat's mean, calibration.rs:228-236) is a two-level f64 sum, so the flat's f32 scale factor
 // can differ from the reference's sequential sum in the last ulp on rare inputs (tests bound it at 1 ulp).
-#include "ab_common.hpp"
 #include "compose_device.hpp"
+#include "entry_host.hpp"
 
 #include <algorithm>
 #include <cmath>
 
 namespace {
-
-constexpr int kBlock = 256;
 
 #define AB_GRID_LOOP(i, n) \
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride_ = (int64_t)gridDim.x * kBlock; i < (n); i += stride_)
@@ -83,6 +81,33 @@ __global__ __launch_bounds__(kBlock) void flat_normalise_kernel(float *__restric
     }
 }
 
+// create_master_dark / _flat (calibration.rs:158-255): every frame less the masters, then the median of those.  A host frame's device
+// copy lives for its own iteration only.
+int combine_preprocessed(ab_ctx *ctx, const ab_plane *frames, size_t n_frames, const ab_plane *bias, const ab_plane *dark, ab_plane_mut *out) {
+    const int64_t rows = frames[0].rows, cols = frames[0].cols, n = rows * cols;
+    Scope sc(ctx);
+    const float *db = nullptr, *dd = nullptr;
+    if (bias) AB_TRY(sc.stage_in(bias, &db));
+    if (dark) AB_TRY(sc.stage_in(dark, &dd));
+    float *pre = nullptr;
+    if (hipMalloc((void **)&pre, std::max<size_t>((size_t)n, 1) * n_frames * sizeof(float)) != hipSuccess)
+        return ab_set_error(ctx, AB_ERR_HIP, "out of device memory for %zu preprocessed frames", n_frames);
+    sc.adopt(pre);
+    std::vector<ab_plane> planes(n_frames);
+    for (size_t f = 0; f < n_frames; ++f) {
+        Scope frame(ctx);  // (stages only: an inner scope's alloc() would start at slot 0 again)
+        const float *df = nullptr;
+        AB_TRY(frame.stage_in(&frames[f], &df));
+        float *dst = pre + f * (size_t)n;
+        if (n > 0) {
+            hipLaunchKernelGGL(preprocess_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, df, db, dd, n, dst);
+            if (hipGetLastError() != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "preprocess launch failed");
+        }
+        planes[f] = ab_plane{dst, rows, cols, 1};
+    }
+    return ab_median_combine(ctx, planes.data(), n_frames, out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -101,20 +126,22 @@ int ab_apply_lrgb(ab_ctx *ctx, const ab_plane *l, ab_plane_mut *r, ab_plane_mut 
     AB_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t n = l->rows * l->cols;
     if (n == 0) return AB_OK;
-    StagedPlane sl;
-    AB_TRY(ab_stage_in(ctx, l, &sl));
+    Scope sc(ctx);
+    const float *dl = nullptr;
+    AB_TRY(sc.stage_in(l, &dl));
     float *d[3] = {r->data, g->data, b->data};
     void *tmp = nullptr;
     hipError_t e = hipSuccess;
     if (!r->on_device) {
         e = hipMalloc(&tmp, 3 * (size_t)n * sizeof(float));
+        if (e == hipSuccess) sc.adopt(tmp);
         for (int c = 0; c < 3 && e == hipSuccess; ++c) {
             d[c] = (float *)tmp + (size_t)c * n;
             e = hipMemcpyAsync(d[c], ch[c]->data, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
         }
     }
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(lrgb_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, sl.dptr, d[0], d[1], d[2], n, lightness_weight,
+        hipLaunchKernelGGL(lrgb_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, dl, d[0], d[1], d[2], n, lightness_weight,
                            chrominance_weight);
         e = hipGetLastError();
     }
@@ -122,9 +149,7 @@ int ab_apply_lrgb(ab_ctx *ctx, const ab_plane *l, ab_plane_mut *r, ab_plane_mut 
         for (int c = 0; c < 3 && e == hipSuccess; ++c)
             e = hipMemcpyAsync(ch[c]->data, d[c], (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        (void)hipFree(tmp);
     }
-    ab_stage_release(ctx, &sl);
     if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "apply_lrgb: %s", hipGetErrorString(e));
     return AB_OK;
 } AB_CATCH(ctx)
@@ -136,27 +161,18 @@ int ab_synthesize_luminance(ab_ctx *ctx, const ab_plane *r, const ab_plane *g, c
                       out->cols == r->cols,
              "luminance planes must share dims");
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedPlane in[3];
+    Scope sc(ctx);
     const ab_plane *src[3] = {r, g, b};
-    int staged = 0, rc = AB_OK;
-    for (; staged < 3 && rc == AB_OK; ++staged) rc = ab_stage_in(ctx, src[staged], &in[staged]);
-    if (rc != AB_OK) --staged;
-    StagedOut so;
-    if (rc == AB_OK) rc = ab_stage_out_begin(ctx, out, &so);
-    if (rc == AB_OK) {
-        const int64_t n = r->rows * r->cols;
-        if (n > 0) {
-            hipLaunchKernelGGL(lum_plain_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in[0].dptr, in[1].dptr, in[2].dptr, n,
-                               so.dptr);
-            if (hipGetLastError() != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "luminance launch failed");
-        }
-        if (rc == AB_OK)
-            rc = ab_stage_out_finish(ctx, &so);
-        else
-            ab_stage_out_abort(ctx, &so);
+    const float *in[3];
+    float *o = nullptr;
+    for (int c = 0; c < 3; ++c) AB_TRY(sc.stage_in(src[c], &in[c]));
+    AB_TRY(sc.stage_out(out, &o));
+    const int64_t n = r->rows * r->cols;
+    if (n > 0) {
+        hipLaunchKernelGGL(lum_plain_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in[0], in[1], in[2], n, o);
+        if (hipGetLastError() != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "luminance launch failed");
     }
-    for (int i = 0; i < staged; ++i) ab_stage_release(ctx, &in[i]);
-    return rc;
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 int ab_compute_linked_stf(const ab_image_stats *sr, const ab_image_stats *sg, const ab_image_stats *sb, const ab_auto_stf_config *cfg,
@@ -180,34 +196,26 @@ int ab_calibrate_channel(ab_ctx *ctx, const ab_plane *orig, float factor, const 
     AB_CHECK(ctx, orig && orig_stats && out && out_stats, "null argument");
     AB_CHECK(ctx, out->rows == orig->rows && out->cols == orig->cols, "output must have the channel's dims");
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, orig, &in));
-    StagedOut so;
-    int rc = ab_stage_out_begin(ctx, out, &so);
-    if (rc == AB_OK) {
-        const int64_t n = in.rows * in.cols;
-        memset(out_stats, 0, sizeof *out_stats);
-        if (n > 0) {
-            hipLaunchKernelGGL(scale_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in.dptr, n, factor, so.dptr);
-            if (hipGetLastError() != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "scale launch failed");
-            if (rc == AB_OK) {
-                if (n <= 4000000) {  // PAR_THRESHOLD, color.rs:19,28-32
-                    rc = ab_stats_device(ctx, so.dptr, n, 0, 0.0, 0.0, out_stats);
-                } else {  // :41-47
-                    const double f = (double)factor;
-                    const double kmin = factor >= 0.0f ? orig_stats->min * f : orig_stats->max * f;
-                    const double kmax = factor >= 0.0f ? orig_stats->max * f : orig_stats->min * f;
-                    rc = ab_stats_device(ctx, so.dptr, n, 1, kmin, kmax, out_stats);
-                }
-            }
+    Scope sc(ctx);
+    const float *in = nullptr;
+    float *o = nullptr;
+    AB_TRY(sc.stage_in(orig, &in));
+    AB_TRY(sc.stage_out(out, &o));
+    const int64_t n = orig->rows * orig->cols;
+    memset(out_stats, 0, sizeof *out_stats);
+    if (n > 0) {
+        hipLaunchKernelGGL(scale_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, in, n, factor, o);
+        if (hipGetLastError() != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "scale launch failed");
+        if (n <= 4000000) {  // PAR_THRESHOLD, color.rs:19,28-32
+            AB_TRY(ab_stats_device(ctx, o, n, 0, 0.0, 0.0, out_stats));
+        } else {  // :41-47
+            const double f = (double)factor;
+            const double kmin = factor >= 0.0f ? orig_stats->min * f : orig_stats->max * f;
+            const double kmax = factor >= 0.0f ? orig_stats->max * f : orig_stats->min * f;
+            AB_TRY(ab_stats_device(ctx, o, n, 1, kmin, kmax, out_stats));
         }
-        if (rc == AB_OK)
-            rc = ab_stage_out_finish(ctx, &so);
-        else
-            ab_stage_out_abort(ctx, &so);
     }
-    ab_stage_release(ctx, &in);
-    return rc;
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 int ab_create_master(ab_ctx *ctx, int32_t kind, const ab_plane *frames, size_t n_frames, const ab_plane *master_bias,
@@ -226,50 +234,27 @@ int ab_create_master(ab_ctx *ctx, int32_t kind, const ab_plane *frames, size_t n
                       out->rows == rows && out->cols == cols,
              "master frames and output must have the frames' dims");
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    if (!bias && !dark) {
+    if (!bias && !dark)
         AB_TRY(ab_median_combine(ctx, frames, n_frames, out));
-    } else {
-        StagedPlane sb, sd;
-        if (bias) AB_TRY(ab_stage_in(ctx, bias, &sb));
-        int rc = dark ? ab_stage_in(ctx, dark, &sd) : AB_OK;
-        float *pre = nullptr;
-        if (rc == AB_OK && hipMalloc((void **)&pre, std::max<size_t>((size_t)n, 1) * n_frames * sizeof(float)) != hipSuccess)
-            rc = ab_set_error(ctx, AB_ERR_HIP, "out of device memory for %zu preprocessed frames", n_frames);
-        std::vector<ab_plane> planes(n_frames);
-        for (size_t f = 0; f < n_frames && rc == AB_OK; ++f) {
-            StagedPlane sf;
-            rc = ab_stage_in(ctx, &frames[f], &sf);
-            if (rc != AB_OK) break;
-            float *dst = pre + f * (size_t)n;
-            if (n > 0) {
-                hipLaunchKernelGGL(preprocess_kernel, dim3(ab_stream_grid(ctx, n)), dim3(kBlock), 0, ctx->stream, sf.dptr, bias ? sb.dptr : nullptr,
-                                   dark ? sd.dptr : nullptr, n, dst);
-                if (hipGetLastError() != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "preprocess launch failed");
-            }
-            if (sf.owned) (void)hipStreamSynchronize(ctx->stream);
-            ab_stage_release(ctx, &sf);
-            planes[f] = ab_plane{dst, rows, cols, 1};
-        }
-        if (rc == AB_OK) rc = ab_median_combine(ctx, planes.data(), n_frames, out);
-        (void)hipStreamSynchronize(ctx->stream);
-        if (pre) (void)hipFree(pre);
-        if (bias) ab_stage_release(ctx, &sb);
-        if (dark) ab_stage_release(ctx, &sd);
-        if (rc != AB_OK) return rc;
-    }
+    else
+        AB_TRY(combine_preprocessed(ctx, frames, n_frames, bias, dark, out));
     if (kind != 2 || n == 0) return AB_OK;
     // master flat normalisation (:228-247) on the combined plane
+    Scope sc(ctx);
     float *d = out->data;
     void *tmp = nullptr;
     if (!out->on_device) {
         AB_HIP(ctx, hipMalloc(&tmp, (size_t)n * sizeof(float)));
+        sc.adopt(tmp);
         d = (float *)tmp;
     }
     const int grid = ab_stream_grid(ctx, n);
     double *psum = nullptr;
     unsigned long long *pcnt = nullptr;
     hipError_t e = hipMalloc((void **)&psum, grid * sizeof(double));
+    if (e == hipSuccess) sc.adopt(psum);
     if (e == hipSuccess) e = hipMalloc((void **)&pcnt, grid * sizeof(unsigned long long));
+    if (e == hipSuccess) sc.adopt(pcnt);
     if (e == hipSuccess && tmp) e = hipMemcpyAsync(d, out->data, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
     std::vector<double> hs(grid);
     std::vector<unsigned long long> hc(grid);
@@ -295,9 +280,6 @@ int ab_create_master(ab_ctx *ctx, int32_t kind, const ab_plane *frames, size_t n
         e = hipMemcpyAsync(out->data, d, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     }
-    if (psum) (void)hipFree(psum);
-    if (pcnt) (void)hipFree(pcnt);
-    if (tmp) (void)hipFree(tmp);
     if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "master flat normalisation: %s", hipGetErrorString(e));
     return AB_OK;
 } AB_CATCH(ctx)

@@ -8,14 +8,13 @@
 // removes the decoded copy altogether.  Arithmetic: `v as f64 * bscale + bzero` as two separately rounded f64
 // operations, then `as f32`, and the identity fast path -- bit-identical to the reference.
 // Header parsing, mmap and file IO stay with the caller.
-#include "ab_common.hpp"
+#include "entry_host.hpp"
 
 #include <algorithm>
 #include <cmath>
 
 namespace {
 
-constexpr int kBlock = 256;
 
 #define AB_GRID_LOOP(i, n) \
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride_ = (int64_t)gridDim.x * kBlock; i < (n); i += stride_)
@@ -137,54 +136,42 @@ int ab_fits_decode_pixels(ab_ctx *ctx, const void *data, size_t nbytes, int32_t 
     AB_CHECK(ctx, out->rows * out->cols == n, "output plane has %lld pixels, the data unit decodes to %lld", (long long)(out->rows * out->cols),
              (long long)n);
     AB_HIP(ctx, hipSetDevice(ctx->device));
+    Scope sc(ctx);
     const uint8_t *raw = (const uint8_t *)data;
-    void *tmp = nullptr;
     if (!data_on_device && n > 0) {
+        void *tmp = nullptr;
         AB_HIP(ctx, hipMalloc(&tmp, (size_t)n * bpp));
+        sc.adopt(tmp);
         const hipError_t e = hipMemcpyAsync(tmp, data, (size_t)n * bpp, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(tmp);
-            return ab_set_error(ctx, AB_ERR_HIP, "H2D of the data unit failed: %s", hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "H2D of the data unit failed: %s", hipGetErrorString(e));
         raw = (const uint8_t *)tmp;
     }
     AB_CHECK(ctx, ((uintptr_t)raw % (size_t)bpp) == 0, "raw data must be aligned to its element size");
-    StagedOut so;
-    int rc = ab_stage_out_begin(ctx, out, &so);
-    if (rc == AB_OK) {
-        rc = ab_fits_decode_device(ctx, raw, n, bitpix, bscale, bzero, so.dptr);
-        if (rc == AB_OK)
-            rc = ab_stage_out_finish(ctx, &so);
-        else
-            ab_stage_out_abort(ctx, &so);
-    }
-    if (tmp) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(tmp);
-    }
-    return rc;
+    float *o = nullptr;
+    AB_TRY(sc.stage_out(out, &o));
+    AB_TRY(ab_fits_decode_device(ctx, raw, n, bitpix, bscale, bzero, o));
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 int ab_fits_compute_bzero_bscale(ab_ctx *ctx, const ab_plane *img, double *bzero, double *bscale) try {
     if (!ctx) return AB_ERR_INVALID;
     AB_CHECK(ctx, img && bzero && bscale, "null argument");
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    const int64_t n = in.rows * in.cols;
+    const int64_t n = img->rows * img->cols;
     const int grid = ab_stream_grid(ctx, n);
-    void *d = nullptr;
-    int rc = ab_scratch(ctx, (size_t)grid * 2 * sizeof(double), &d);
     std::vector<double> h((size_t)grid * 2);
-    if (rc == AB_OK) {
-        hipLaunchKernelGGL(finite_minmax_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, in.dptr, n, (double *)d);
+    {
+        Scope sc(ctx);
+        const float *in = nullptr;
+        AB_TRY(sc.stage_in(img, &in));
+        void *d = nullptr;
+        AB_TRY(ab_scratch(ctx, (size_t)grid * 2 * sizeof(double), &d));
+        hipLaunchKernelGGL(finite_minmax_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, in, n, (double *)d);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "min/max scan failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "min/max scan failed: %s", hipGetErrorString(e));
     }
-    ab_stage_release(ctx, &in);
-    if (rc != AB_OK) return rc;
     double dmin = INFINITY, dmax = -INFINITY;
     for (int i = 0; i < grid; ++i) {
         dmin = std::fmin(dmin, h[2 * i]);
@@ -205,36 +192,33 @@ int ab_fits_encode_pixels(ab_ctx *ctx, const ab_plane *img, int32_t bitpix, doub
     AB_CHECK(ctx, img && out, "null argument");
     AB_CHECK(ctx, bitpix == -32 || bitpix == 16 || bitpix == -64, "the writer supports BITPIX -32, 16 and -64 (got %d)", (int)bitpix);
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    const int64_t n = in.rows * in.cols;
+    Scope sc(ctx);
+    const float *in = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    const int64_t n = img->rows * img->cols;
     const size_t bytes = (size_t)n * (size_t)bytes_per_pixel(bitpix);
     uint8_t *dst = (uint8_t *)out;
     void *tmp = nullptr;
     hipError_t e = hipSuccess;
     if (!out_on_device) {
         e = hipMalloc(&tmp, bytes);
+        if (e == hipSuccess) sc.adopt(tmp);
         dst = (uint8_t *)tmp;
     }
     if (e == hipSuccess) {
         const dim3 grid(ab_stream_grid(ctx, n)), block(kBlock);
         if (bitpix == -32)
-            hipLaunchKernelGGL(fits_encode_kernel<-32>, grid, block, 0, ctx->stream, in.dptr, n, bzero, bscale, dst);
+            hipLaunchKernelGGL(fits_encode_kernel<-32>, grid, block, 0, ctx->stream, in, n, bzero, bscale, dst);
         else if (bitpix == 16)
-            hipLaunchKernelGGL(fits_encode_kernel<16>, grid, block, 0, ctx->stream, in.dptr, n, bzero, bscale, dst);
+            hipLaunchKernelGGL(fits_encode_kernel<16>, grid, block, 0, ctx->stream, in, n, bzero, bscale, dst);
         else
-            hipLaunchKernelGGL(fits_encode_kernel<-64>, grid, block, 0, ctx->stream, in.dptr, n, bzero, bscale, dst);
+            hipLaunchKernelGGL(fits_encode_kernel<-64>, grid, block, 0, ctx->stream, in, n, bzero, bscale, dst);
         e = hipGetLastError();
     }
     if (e == hipSuccess && tmp) {
         e = hipMemcpyAsync(out, tmp, bytes, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     }
-    if (tmp) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(tmp);
-    }
-    ab_stage_release(ctx, &in);
     if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "FITS encode failed: %s", hipGetErrorString(e));
     return AB_OK;
 } AB_CATCH(ctx)

@@ -14,7 +14,7 @@
 // its tests pin the shift to +-1 px); the CPU oracle uses the same butterflies as this kernel, so
 // the correlation surface is bit-identical between the two and the estimated shift agrees to ~1e-12.
 // find_peak's tie-break (schedule dependent in the reference) is the lowest index.
-#include "ab_common.hpp"
+#include "entry_host.hpp"
 
 #include <cfloat>
 #include <cmath>
@@ -24,7 +24,6 @@ namespace {
 constexpr int kCoarseMaxDim = 512;   // phase_correlation.rs:10
 constexpr int kRefineCropSize = 512; // :11
 constexpr double kEpsilon = 1e-15;   // :13
-constexpr int kBlock = 256;
 constexpr size_t kPcBatch = 16;  // pairs per round (4 MiB of spectrum + 2 MiB of surface + 1 MiB of downsampled plane each)
 
 struct MinMaxPartial {
@@ -642,16 +641,12 @@ extern "C" {
 int ab_phase_correlate(ab_ctx *ctx, const ab_plane *reference, const ab_plane *target, ab_phase_correlation_result *out) try {
     if (!ctx) return AB_ERR_INVALID;
     AB_CHECK(ctx, reference && target && out, "null argument");
-    StagedPlane r, t;
-    AB_TRY(ab_stage_in(ctx, reference, &r));
-    int rc = ab_stage_in(ctx, target, &t);
-    if (rc == AB_OK) {
-        rc = ab_phase_correlate_device(ctx, r.dptr, r.rows, r.cols, r.cols, t.dptr, t.rows, t.cols, t.cols, &out->dx, &out->dy,
-                                       &out->confidence);
-        ab_stage_release(ctx, &t);
-    }
-    ab_stage_release(ctx, &r);
-    return rc;
+    Scope sc(ctx);
+    const float *r = nullptr, *t = nullptr;
+    AB_TRY(sc.stage_in(reference, &r));
+    AB_TRY(sc.stage_in(target, &t));
+    return ab_phase_correlate_device(ctx, r, reference->rows, reference->cols, reference->cols, t, target->rows, target->cols, target->cols, &out->dx,
+                                     &out->dy, &out->confidence);
 } AB_CATCH(ctx)
 
 // test hook: correlate_single's full correlation surface (dims <= 512) for bit-level parity
@@ -661,18 +656,14 @@ int ab_correlate_single(ab_ctx *ctx, const ab_plane *a, const ab_plane *b, ab_ph
     AB_CHECK(ctx, a->rows == b->rows && a->cols == b->cols && a->rows <= kCoarseMaxDim && a->cols <= kCoarseMaxDim,
              "correlate_single takes two equal planes of at most 512 x 512");
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedPlane sa, sb;
-    AB_TRY(ab_stage_in(ctx, a, &sa));
-    int rc = ab_stage_in(ctx, b, &sb);
-    if (rc == AB_OK) {
-        PcBatchScratch s;
-        rc = pc_batch_carve(ctx, &s, 1);
-        const View va{sa.dptr, (int)sa.rows, (int)sa.cols, sa.cols}, vb{sb.dptr, (int)sb.rows, (int)sb.cols, sb.cols};
-        if (rc == AB_OK) rc = correlate_batch(ctx, va, &vb, 1, s, 0, &out->dx, &out->dy, &out->confidence, surface_host);
-        ab_stage_release(ctx, &sb);
-    }
-    ab_stage_release(ctx, &sa);
-    return rc;
+    Scope sc(ctx);
+    const float *da = nullptr, *db = nullptr;
+    AB_TRY(sc.stage_in(a, &da));
+    AB_TRY(sc.stage_in(b, &db));
+    PcBatchScratch s;
+    AB_TRY(pc_batch_carve(ctx, &s, 1));
+    const View va{da, (int)a->rows, (int)a->cols, a->cols}, vb{db, (int)b->rows, (int)b->cols, b->cols};
+    return correlate_batch(ctx, va, &vb, 1, s, 0, &out->dx, &out->dy, &out->confidence, surface_host);
 } AB_CATCH(ctx)
 
 }  // extern "C"

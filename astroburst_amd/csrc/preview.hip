@@ -15,7 +15,7 @@
 // Every kernel is a grid-stride sweep of four-pixel groups: one 16-byte load where the source allows it, one packed store (four
 // bytes, four big-endian u16, four floats) aligned by the DESTINATION; the at most six pixels around the groups and the AVX2
 // route's remainder are done one per lane by the first lanes of the grid.  A plane at any float-aligned address is served.
-#include "ab_common.hpp"
+#include "entry_host.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -23,7 +23,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kOpAvx2 = AB_ASINH_ROUTE_AVX2, kOpScalar = AB_ASINH_ROUTE_SCALAR, kOpIdent = 2;
 
 struct MapTx {
@@ -31,7 +30,7 @@ struct MapTx {
 };
 
 // where the four-pixel groups of a sweep lie
-struct Span {
+struct Groups {
     int64_t head;   // pixels [0, head) precede the first group
     int64_t quads;  // groups: pixels [head, head + 4 * quads)
     int64_t body;   // pixels [0, body) take the route's formula; [body, n) the scalar one (body == n except on the AVX2 route)
@@ -104,7 +103,7 @@ __device__ __forceinline__ float value_of(float v, const MapTx t) {
 
 // quad(i, a, b, c, d): the values of pixels i .. i + 3 of a group; one(i, a): a pixel outside the groups
 template <int OP, class Quad, class One>
-__device__ __forceinline__ void sweep(const float *src, const Span s, const MapTx t, Quad quad, One one) {
+__device__ __forceinline__ void sweep(const float *src, const Groups s, const MapTx t, Quad quad, One one) {
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < s.quads; q += stride) {
         const int64_t i = s.head + 4 * q;
@@ -129,36 +128,15 @@ __device__ __forceinline__ void sweep(const float *src, const Span s, const MapT
 
 // (out may be exactly src: a lane reads its pixels before it writes them and no other lane touches them)
 template <int OP>
-__global__ __launch_bounds__(kBlock) void preview_map_kernel(const float *src, const Span s, const MapTx t, float *out) {
+__global__ __launch_bounds__(kBlock) void preview_map_kernel(const float *src, const Groups s, const MapTx t, float *out) {
     sweep<OP>(
         src, s, t, [&](int64_t i, float a, float b, float c, float d) { *reinterpret_cast<float4 *>(out + i) = make_float4(a, b, c, d); },
         [&](int64_t i, float a) { out[i] = a; });
 }
 
-// wave reduce -> LDS -> every lane holds the block's min / max
-__device__ __forceinline__ void block_minmax(float &mn, float &mx) {
-    __shared__ float smn[kBlock / 64], smx[kBlock / 64];
-    for (int off = 32; off > 0; off >>= 1) {
-        mn = fminf(mn, __shfl_xor(mn, off));
-        mx = fmaxf(mx, __shfl_xor(mx, off));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        smn[threadIdx.x / 64] = mn;
-        smx[threadIdx.x / 64] = mx;
-    }
-    __syncthreads();
-    mn = smn[0];
-    mx = smx[0];
-    for (int w = 1; w < kBlock / 64; ++w) {
-        mn = fminf(mn, smn[w]);
-        mx = fmaxf(mx, smx[w]);
-    }
-    __syncthreads();
-}
-
 // find_minmax_simd's scalar statement (simd.rs:263-271) of the values: part[block] = (min, max) of its finite ones
 template <int OP>
-__global__ __launch_bounds__(kBlock) void preview_minmax_kernel(const float *__restrict__ src, const Span s, const MapTx t, float2 *__restrict__ part) {
+__global__ __launch_bounds__(kBlock) void preview_minmax_kernel(const float *__restrict__ src, const Groups s, const MapTx t, float2 *__restrict__ part) {
     float mn = FLT_MAX, mx = -FLT_MAX;  // f32::MAX, f32::MIN
     auto take = [&](float v) {
         if (__builtin_isfinite(v)) {
@@ -199,7 +177,7 @@ __device__ __forceinline__ uint32_t quantise(float v, float mn, float inv) {
 __device__ __forceinline__ uint32_t be16(uint32_t q) { return (q >> 8) | ((q & 255u) << 8); }
 
 template <int OP, int BITS, bool UNIT>
-__global__ __launch_bounds__(kBlock) void preview_bytes_kernel(const float *__restrict__ src, const Span s, const MapTx t,
+__global__ __launch_bounds__(kBlock) void preview_bytes_kernel(const float *__restrict__ src, const Groups s, const MapTx t,
                                                                const float2 *__restrict__ part, int parts, uint8_t *__restrict__ out,
                                                                float2 *__restrict__ range_out) {
     float mn = 0.0f, inv = 0.0f;
@@ -240,8 +218,8 @@ __global__ __launch_bounds__(kBlock) void preview_bytes_kernel(const float *__re
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 // the groups of a sweep over n pixels of `src` under `op`; `align_addr` / `bytes_per_pixel`: the address whose four-pixel stores
 // (or, for a sweep that only reads, loads) must be aligned
-Span make_span(const float *src, uintptr_t align_addr, int bytes_per_pixel, int64_t n, int op) {
-    Span s;
+Groups make_span(const float *src, uintptr_t align_addr, int bytes_per_pixel, int64_t n, int op) {
+    Groups s;
     s.n = n;
     s.body = op == kOpAvx2 ? 8 * (n / 8) : n;
     const uintptr_t group = (uintptr_t)(4 * bytes_per_pixel);
@@ -256,7 +234,7 @@ Span make_span(const float *src, uintptr_t align_addr, int bytes_per_pixel, int6
 }
 
 // workgroups for a sweep: enough for its groups (or, when it has none, for its pixels), at most per_cu per compute unit
-int grid_for(const ab_ctx *ctx, const Span &s, int per_cu) {
+int grid_for(const ab_ctx *ctx, const Groups &s, int per_cu) {
     const int64_t lanes = std::max<int64_t>(s.quads, s.n - 4 * s.quads);
     return ab_stream_grid(ctx, lanes, kBlock, per_cu);
 }
@@ -332,7 +310,7 @@ int stats_device(ab_ctx *ctx, const float *d, int64_t n, ab_asinh_stats *out) {
 }
 
 int map_launch(ab_ctx *ctx, const float *d, int64_t n, const MapTx t, int route, float *out) {
-    const Span s = make_span(d, (uintptr_t)out, (int)sizeof(float), n, route);
+    const Groups s = make_span(d, (uintptr_t)out, (int)sizeof(float), n, route);
     const int grid = grid_for(ctx, s, 8);
     if (route == kOpAvx2) {
         hipLaunchKernelGGL(preview_map_kernel<kOpAvx2>, dim3(grid), dim3(kBlock), 0, ctx->stream, d, s, t, out);
@@ -356,12 +334,12 @@ int preview_device(ab_ctx *ctx, const float *d, int64_t n, int route, float *out
 }
 
 template <int OP>
-void launch_minmax(ab_ctx *ctx, int grid, const float *d, const Span s, const MapTx t, float2 *part) {
+void launch_minmax(ab_ctx *ctx, int grid, const float *d, const Groups s, const MapTx t, float2 *part) {
     hipLaunchKernelGGL(preview_minmax_kernel<OP>, dim3(grid), dim3(kBlock), 0, ctx->stream, d, s, t, part);
 }
 
 template <int OP, bool UNIT>
-void launch_bytes(ab_ctx *ctx, int grid, int bits, const float *d, const Span s, const MapTx t, const float2 *part, int parts, uint8_t *out,
+void launch_bytes(ab_ctx *ctx, int grid, int bits, const float *d, const Groups s, const MapTx t, const float2 *part, int parts, uint8_t *out,
                   float2 *range) {
     if (bits == 8) {
         hipLaunchKernelGGL((preview_bytes_kernel<OP, 8, UNIT>), dim3(grid), dim3(kBlock), 0, ctx->stream, d, s, t, part, parts, out, range);
@@ -385,7 +363,7 @@ int bytes_device(ab_ctx *ctx, const float *d, int64_t n, int op, const MapTx t, 
         return AB_OK;
     }
     // scratch: the final (min, max) | the partials | (host output) the bytes
-    const Span rs = make_span(d, (uintptr_t)d, (int)sizeof(float), n, op);
+    const Groups rs = make_span(d, (uintptr_t)d, (int)sizeof(float), n, op);
     const int parts = grid_for(ctx, rs, 4);
     const size_t head = 256 + (((size_t)parts * sizeof(float2) + 255) & ~(size_t)255);
     char *scratch = nullptr;
@@ -402,7 +380,7 @@ int bytes_device(ab_ctx *ctx, const float *d, int64_t n, int op, const MapTx t, 
         }
         AB_HIP(ctx, hipGetLastError());
     }
-    const Span ws = make_span(d, (uintptr_t)bytes_dev, bits / 8, n, op);
+    const Groups ws = make_span(d, (uintptr_t)bytes_dev, bits / 8, n, op);
     const int grid = grid_for(ctx, ws, 8);
     if (unit) {
         launch_bytes<kOpIdent, true>(ctx, grid, bits, d, ws, t, part, 0, bytes_dev, range);
@@ -431,18 +409,18 @@ int render_plain(ab_ctx *ctx, const ab_plane *img, int32_t bits, bool unit, void
     AB_CHECK(ctx, out, "null output");
     AB_HIP(ctx, hipSetDevice(ctx->device));
     AB_TRY(ab_cancel_point(ctx));
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, img, &in));
+    Scope sc(ctx);
+    const float *in = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
     float range[2] = {0.0f, 0.0f};
     const bool want = !unit && (min_out || max_out);
-    const int rc = bytes_device(ctx, in.dptr, img->rows * img->cols, kOpIdent, MapTx{0.0f, 0.0f, 0.0f, 0.0f}, (int)bits, unit, false, out, out_on_device,
-                                want ? range : nullptr);
-    ab_stage_release(ctx, &in);
-    if (rc == AB_OK && want) {
+    AB_TRY(bytes_device(ctx, in, img->rows * img->cols, kOpIdent, MapTx{0.0f, 0.0f, 0.0f, 0.0f}, (int)bits, unit, false, out, out_on_device,
+                        want ? range : nullptr));
+    if (want) {
         if (min_out) *min_out = range[0];
         if (max_out) *max_out = range[1];
     }
-    return rc;
+    return AB_OK;
 }
 
 }  // namespace
@@ -455,11 +433,10 @@ int ab_asinh_preview_stats(ab_ctx *ctx, const ab_plane *img, ab_asinh_stats *out
     AB_CHECK(ctx, out, "null statistics");
     AB_HIP(ctx, hipSetDevice(ctx->device));
     AB_TRY(ab_cancel_point(ctx));
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    const int rc = stats_device(ctx, in.dptr, img->rows * img->cols, out);
-    ab_stage_release(ctx, &in);
-    return rc;
+    Scope sc(ctx);
+    const float *in = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    return stats_device(ctx, in, img->rows * img->cols, out);
 } AB_CATCH(ctx)
 
 int ab_asinh_normalize_with_stats(ab_ctx *ctx, const ab_plane *img, const ab_asinh_stats *stats, int32_t route, ab_plane_mut *out) try {
@@ -471,28 +448,19 @@ int ab_asinh_normalize_with_stats(ab_ctx *ctx, const ab_plane *img, const ab_asi
     AB_TRY(stats_tx(ctx, stats, &t));
     AB_HIP(ctx, hipSetDevice(ctx->device));
     AB_TRY(ab_cancel_point(ctx));
-    StagedPlane in;
-    StagedOut so;
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    int rc = ab_stage_out_begin(ctx, out, &so);
-    if (rc != AB_OK) {
-        ab_stage_release(ctx, &in);
-        return rc;
-    }
+    Scope sc(ctx);
+    const float *in = nullptr;
+    float *o = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    AB_TRY(sc.stage_out(out, &o));
     const int64_t n = img->rows * img->cols;
     if (stats->valid_count == 0) {  // asinh_normalize_simd returns data.clone() (simd.rs:165-167)
-        const hipError_t e = so.dptr != in.dptr ? hipMemcpyAsync(so.dptr, in.dptr, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream) : hipSuccess;
-        rc = e == hipSuccess ? AB_OK : ab_set_error(ctx, AB_ERR_HIP, "the copy of the image failed: %s", hipGetErrorString(e));
+        const hipError_t e = o != in ? hipMemcpyAsync(o, in, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream) : hipSuccess;
+        if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "the copy of the image failed: %s", hipGetErrorString(e));
     } else {
-        rc = map_launch(ctx, in.dptr, n, t, (int)route, so.dptr);
+        AB_TRY(map_launch(ctx, in, n, t, (int)route, o));
     }
-    if (rc != AB_OK) {
-        ab_stage_out_abort(ctx, &so);
-    } else {
-        rc = ab_stage_out_finish(ctx, &so);
-    }
-    ab_stage_release(ctx, &in);
-    return rc;
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 int ab_robust_asinh_preview(ab_ctx *ctx, const ab_plane *img, int32_t route, ab_plane_mut *out, ab_asinh_stats *stats_out) try {
@@ -502,24 +470,16 @@ int ab_robust_asinh_preview(ab_ctx *ctx, const ab_plane *img, int32_t route, ab_
     AB_TRY(out_plane_check(ctx, img, out));
     AB_HIP(ctx, hipSetDevice(ctx->device));
     AB_TRY(ab_cancel_point(ctx));
-    StagedPlane in;
-    StagedOut so;
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    int rc = ab_stage_out_begin(ctx, out, &so);
-    if (rc != AB_OK) {
-        ab_stage_release(ctx, &in);
-        return rc;
-    }
+    Scope sc(ctx);
+    const float *in = nullptr;
+    float *o = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    AB_TRY(sc.stage_out(out, &o));
     ab_asinh_stats st;
-    rc = preview_device(ctx, in.dptr, img->rows * img->cols, (int)route, so.dptr, &st);
-    if (rc != AB_OK) {
-        ab_stage_out_abort(ctx, &so);
-    } else {
-        rc = ab_stage_out_finish(ctx, &so);
-    }
-    ab_stage_release(ctx, &in);
-    if (rc == AB_OK && stats_out) *stats_out = st;
-    return rc;
+    AB_TRY(preview_device(ctx, in, img->rows * img->cols, (int)route, o, &st));
+    AB_TRY(sc.finish_outs());
+    if (stats_out) *stats_out = st;
+    return AB_OK;
 } AB_CATCH(ctx)
 
 int ab_render_asinh_preview(ab_ctx *ctx, const ab_plane *img, int32_t route, uint8_t *out_u8, int32_t out_on_device, ab_asinh_stats *stats_out) try {
@@ -529,18 +489,18 @@ int ab_render_asinh_preview(ab_ctx *ctx, const ab_plane *img, int32_t route, uin
     AB_CHECK(ctx, out_u8, "null output");
     AB_HIP(ctx, hipSetDevice(ctx->device));
     AB_TRY(ab_cancel_point(ctx));
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, img, &in));
+    Scope sc(ctx);
+    const float *in = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
     const int64_t n = img->rows * img->cols;
     ab_asinh_stats st;
-    int rc = stats_device(ctx, in.dptr, n, &st);
+    AB_TRY(stats_device(ctx, in, n, &st));
     MapTx t{0.0f, 0.0f, 0.0f, 0.0f};
-    if (rc == AB_OK && st.valid_count > 0) rc = stats_tx(ctx, &st, &t);
+    if (st.valid_count > 0) AB_TRY(stats_tx(ctx, &st, &t));
     // (no valid pixel: the preview is the image itself, and render_grayscale sends every invalid pixel to 0)
-    if (rc == AB_OK) rc = bytes_device(ctx, in.dptr, n, (int)route, t, 8, false, st.valid_count == 0, out_u8, out_on_device, nullptr);
-    ab_stage_release(ctx, &in);
-    if (rc == AB_OK && stats_out) *stats_out = st;
-    return rc;
+    AB_TRY(bytes_device(ctx, in, n, (int)route, t, 8, false, st.valid_count == 0, out_u8, out_on_device, nullptr));
+    if (stats_out) *stats_out = st;
+    return AB_OK;
 } AB_CATCH(ctx)
 
 int ab_render_grayscale(ab_ctx *ctx, const ab_plane *img, int32_t bits, void *out, int32_t out_on_device, float *min_out, float *max_out) try {

@@ -15,14 +15,13 @@
 // EXACTNESS: a sum the reference forms sequentially is formed sequentially here, by one lane, over values the other lanes staged (and
 // sorted) in LDS -- raster order over a window, ascending order over a sorted slice.  Products and quotients are per-element and
 // unfused (-ffp-contract=off); f64 sqrt and division are IEEE.  Only stddev (pass 1) is summed in another order than the reference's.
-#include "ab_common.hpp"
+#include "entry_host.hpp"
 
 #include <algorithm>
 #include <cmath>
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kStatBlocks = 1024;  // fixed: the reduction tree must not depend on the device
 constexpr int kTileW = 64, kTileH = 32, kHalo = 5;
 constexpr int kSortCap = 15360;  // floats of LDS per workgroup: the 2 f .. 3 f annulus at f = 30 holds pi * 4500 = 14 137 lattice points
@@ -783,11 +782,10 @@ int ab_estimate_psf(ab_ctx *ctx, const ab_plane *img, const ab_psf_estimation_co
     *res = ab_psf_result{};
     res->kernel_size = (size_t)size;
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    const int rc = estimate_device(ctx, in.dptr, in.rows, in.cols, *cfg, kernel_out, stars_out, stars_cap, res);
-    ab_stage_release(ctx, &in);
-    return rc;
+    Scope sc(ctx);
+    const float *in = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    return estimate_device(ctx, in, img->rows, img->cols, *cfg, kernel_out, stars_out, stars_cap, res);
 } AB_CATCH(ctx)
 
 }  // extern "C"

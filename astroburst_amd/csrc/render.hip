@@ -399,12 +399,13 @@ int ab_ipc_encode_with_header(ab_ctx *ctx, const ab_plane *img, int64_t max_dim,
     if (!ctx) return AB_ERR_INVALID;
     AB_CHECK(ctx, img && out, "null argument");
     AB_CHECK(ctx, max_dim >= 0, "max_dim must be >= 0 (0 = full resolution)");
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    int64_t ph = in.rows, pw = in.cols;
+    Scope sc(ctx);
+    const float *in = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    int64_t ph = img->rows, pw = img->cols;
     double yr = 1.0, xr = 1.0;
-    const int full = max_dim == 0 || (in.rows <= max_dim && in.cols <= max_dim);
-    if (!full) preview_dims(in.rows, in.cols, max_dim, &ph, &pw, &yr, &xr);
+    const int full = max_dim == 0 || (img->rows <= max_dim && img->cols <= max_dim);
+    if (!full) preview_dims(img->rows, img->cols, max_dim, &ph, &pw, &yr, &xr);
     const size_t bytes = 16 + (size_t)(ph * pw) * 4;
     BytesOut bo;
     int rc = bytes_begin(ctx, out, out_on_device, bytes, &bo);
@@ -415,7 +416,7 @@ int ab_ipc_encode_with_header(ab_ctx *ctx, const ab_plane *img, int64_t max_dim,
         rc = ab_scratch(ctx, grid * sizeof(float2), &d);
         std::vector<float2> part(grid);
         if (rc == AB_OK) {
-            hipLaunchKernelGGL(ipc_encode_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, in.dptr, in.rows, in.cols, ph, pw, yr, xr, full,
+            hipLaunchKernelGGL(ipc_encode_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, in, img->rows, img->cols, ph, pw, yr, xr, full,
                                (float *)(bo.dptr + 16), (float2 *)d);
             if (hipGetLastError() != hipSuccess || hipMemcpyAsync(part.data(), d, grid * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
                 hipStreamSynchronize(ctx->stream) != hipSuccess)
@@ -437,7 +438,6 @@ int ab_ipc_encode_with_header(ab_ctx *ctx, const ab_plane *img, int64_t max_dim,
         }
     }
     rc = bytes_finish(ctx, &bo, rc);
-    ab_stage_release(ctx, &in);
     if (rc == AB_OK && out_len) *out_len = bytes;
     return rc;
 } AB_CATCH(ctx)
@@ -462,32 +462,24 @@ int ab_tile_downsample_2x(ab_ctx *ctx, const ab_plane *img, ab_plane_mut *out) t
     if (!ctx) return AB_ERR_INVALID;
     AB_CHECK(ctx, img && out, "null argument");
     AB_CHECK(ctx, out->rows == (img->rows + 1) / 2 && out->cols == (img->cols + 1) / 2, "downsample_2x writes ((rows + 1) / 2) x ((cols + 1) / 2)");
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    StagedOut so;
-    int rc = ab_stage_out_begin(ctx, out, &so);
-    if (rc == AB_OK) {
-        hipLaunchKernelGGL(downsample2x_kernel, dim3(ab_div_up(out->cols, kBlock), (unsigned)out->rows), dim3(kBlock), 0, ctx->stream, in.dptr,
-                           (int)in.rows, (int)in.cols, (int)out->rows, (int)out->cols, so.dptr);
-        if (hipGetLastError() != hipSuccess) {
-            ab_stage_out_abort(ctx, &so);
-            rc = ab_set_error(ctx, AB_ERR_HIP, "downsample launch failed");
-        } else {
-            rc = ab_stage_out_finish(ctx, &so);
-        }
-    }
-    ab_stage_release(ctx, &in);
-    return rc;
+    Scope sc(ctx);
+    const float *in = nullptr;
+    float *o = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    AB_TRY(sc.stage_out(out, &o));
+    hipLaunchKernelGGL(downsample2x_kernel, dim3(ab_div_up(out->cols, kBlock), (unsigned)out->rows), dim3(kBlock), 0, ctx->stream, in, (int)img->rows,
+                       (int)img->cols, (int)out->rows, (int)out->cols, o);
+    if (hipGetLastError() != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "downsample launch failed");
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 int ab_tile_percentile_bounds(ab_ctx *ctx, const ab_plane *img, double low_pct, double high_pct, float *lo, float *hi) try {
     if (!ctx) return AB_ERR_INVALID;
     AB_CHECK(ctx, img && lo && hi, "null argument");
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    const int rc = percentile_bounds(ctx, in.dptr, in.rows * in.cols, low_pct, high_pct, lo, hi);
-    ab_stage_release(ctx, &in);
-    return rc;
+    Scope sc(ctx);
+    const float *in = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    return percentile_bounds(ctx, in, img->rows * img->cols, low_pct, high_pct, lo, hi);
 } AB_CATCH(ctx)
 
 int ab_generate_tile_pyramid(ab_ctx *ctx, const ab_plane *normalized, int64_t tile_size, uint8_t *tiles, int32_t tiles_on_device,
@@ -500,10 +492,11 @@ int ab_generate_tile_pyramid(ab_ctx *ctx, const ab_plane *normalized, int64_t ti
     int nl = 0;
     const size_t total = layout(normalized->rows, normalized->cols, tile_size, 1, levels, &nl);
     *num_levels_out = nl;
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, normalized, &in));
+    Scope sc(ctx);
+    const float *in = nullptr;
+    AB_TRY(sc.stage_in(normalized, &in));
     float gmin = 0.0f, gmax = 0.0f;
-    int rc = percentile_bounds(ctx, in.dptr, in.rows * in.cols, 0.001, 0.999, &gmin, &gmax);  // tiles.rs:190
+    int rc = percentile_bounds(ctx, in, normalized->rows * normalized->cols, 0.001, 0.999, &gmin, &gmax);  // tiles.rs:190
     BytesOut bo;
     if (rc == AB_OK) {
         rc = bytes_begin(ctx, tiles, tiles_on_device, total, &bo);
@@ -511,12 +504,11 @@ int ab_generate_tile_pyramid(ab_ctx *ctx, const ab_plane *normalized, int64_t ti
         if (rc == AB_OK) {
             Stf3 none;
             none.on = 0;
-            const float *base[1] = {in.dptr};
+            const float *base[1] = {in};
             rc = pyramid<1>(ctx, base, levels, nl, tile_size, gmin, gmax, none, bo.dptr);
         }
         rc = bytes_finish(ctx, &bo, rc);
     }
-    ab_stage_release(ctx, &in);
     if (global_min) *global_min = gmin;
     if (global_max) *global_max = gmax;
     return rc;

@@ -11,7 +11,7 @@
 // each source line about once (4*P read + 4*P written per frame).  Coordinates, weights and the
 // accumulation are f64 in the reference's evaluation order, so results are bit-identical to the
 // CPU restatement; only the final store is f32.
-#include "ab_common.hpp"
+#include "entry_host.hpp"
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -472,25 +472,29 @@ int ab_warp_rows_device(ab_ctx *ctx, const float *src, int64_t src_rows, int64_t
     return AB_OK;
 }
 
+namespace {
+
+// the whole-plane entry points: stage the source and the output, run, download a host output
+template <typename F>
+int staged_map(ab_ctx *ctx, const ab_plane *src, ab_plane_mut *out, F run) {
+    Scope sc(ctx);
+    const float *in = nullptr;
+    float *o = nullptr;
+    AB_TRY(sc.stage_in(src, &in));
+    AB_TRY(sc.stage_out(out, &o));
+    AB_TRY(run(in, o));
+    return sc.finish_outs();
+}
+
+}  // namespace
+
 extern "C" {
 
 int ab_shift_image_subpixel(ab_ctx *ctx, const ab_plane *src, double dy, double dx, ab_plane_mut *out) try {
     if (!ctx) return AB_ERR_INVALID;
     AB_CHECK(ctx, src && out, "null plane");
     AB_CHECK(ctx, src->rows == out->rows && src->cols == out->cols, "shift_image_subpixel keeps the image dims");
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, src, &in));
-    StagedOut so;
-    int rc = ab_stage_out_begin(ctx, out, &so);
-    if (rc == AB_OK) {
-        rc = ab_shift_device(ctx, in.dptr, in.rows, in.cols, in.cols, dy, dx, so.dptr);
-        if (rc == AB_OK)
-            rc = ab_stage_out_finish(ctx, &so);
-        else
-            ab_stage_out_abort(ctx, &so);
-    }
-    ab_stage_release(ctx, &in);
-    return rc;
+    return staged_map(ctx, src, out, [&](const float *in, float *o) { return ab_shift_device(ctx, in, src->rows, src->cols, src->cols, dy, dx, o); });
 } AB_CATCH(ctx)
 
 // rows [row0, row0 + out_band->rows) of warp_image(src, transform, out_rows, out_band->cols) (device planes)
@@ -589,38 +593,16 @@ int ab_warp_image_rows_from_band(ab_ctx *ctx, const ab_plane *src_band, int64_t 
 int ab_warp_image(ab_ctx *ctx, const ab_plane *src, const double transform[6], ab_plane_mut *out) try {
     if (!ctx) return AB_ERR_INVALID;
     AB_CHECK(ctx, src && out && transform, "null plane or transform");
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, src, &in));
-    StagedOut so;
-    int rc = ab_stage_out_begin(ctx, out, &so);
-    if (rc == AB_OK) {
-        rc = ab_warp_device(ctx, in.dptr, in.rows, in.cols, transform, out->rows, out->cols, so.dptr);
-        if (rc == AB_OK)
-            rc = ab_stage_out_finish(ctx, &so);
-        else
-            ab_stage_out_abort(ctx, &so);
-    }
-    ab_stage_release(ctx, &in);
-    return rc;
+    return staged_map(ctx, src, out, [&](const float *in, float *o) {
+        return ab_warp_device(ctx, in, src->rows, src->cols, transform, out->rows, out->cols, o);
+    });
 } AB_CATCH(ctx)
 
 int ab_resample_image(ab_ctx *ctx, const ab_plane *src, ab_plane_mut *out) try {
     if (!ctx) return AB_ERR_INVALID;
     AB_CHECK(ctx, src && out, "null plane");
     if (out->rows == 0 || out->cols == 0) return ab_set_error(ctx, AB_ERR_INVALID, "Target dimensions must be > 0");  // :32-34
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, src, &in));
-    StagedOut so;
-    int rc = ab_stage_out_begin(ctx, out, &so);
-    if (rc == AB_OK) {
-        rc = ab_resample_device(ctx, in.dptr, in.rows, in.cols, out->rows, out->cols, so.dptr);
-        if (rc == AB_OK)
-            rc = ab_stage_out_finish(ctx, &so);
-        else
-            ab_stage_out_abort(ctx, &so);
-    }
-    ab_stage_release(ctx, &in);
-    return rc;
+    return staged_map(ctx, src, out, [&](const float *in, float *o) { return ab_resample_device(ctx, in, src->rows, src->cols, out->rows, out->cols, o); });
 } AB_CATCH(ctx)
 
 }  // extern "C"

@@ -21,7 +21,7 @@
 // an in-place DIF is bit-reversed: the store reads LDS at brev(k).  Every twiddle is W_n^p = exp(-2 pi i p / n) evaluated in f64
 // and rounded once to f32, from a table per line length cached in the context; no sincosf in a kernel.
 // No atomics anywhere: two calls are bit-identical.
-#include "ab_common.hpp"
+#include "entry_host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256) void spectrum_log_kernel(const float2 *__restr
 constexpr int kRedBlock = 256;
 constexpr int kRedBlocks = 1024;
 
-__device__ __forceinline__ void block_minmax(float &mn, float &mx) {
+__device__ __forceinline__ void tree_minmax(float &mn, float &mx) {
     __shared__ float smn[kRedBlock], smx[kRedBlock];
     smn[threadIdx.x] = mn;
     smx[threadIdx.x] = mx;
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(kRedBlock) void u8_minmax_kernel(const float *__res
         mn = fminf(mn, v[i]);
         mx = fmaxf(mx, v[i]);
     }
-    block_minmax(mn, mx);
+    tree_minmax(mn, mx);
     if (threadIdx.x == 0) partial[2 * blockIdx.x] = mn, partial[2 * blockIdx.x + 1] = mx;
 }
 
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(kRedBlock) void u8_minmax_final_kernel(const float 
         mn = fminf(mn, partial[2 * i]);
         mx = fmaxf(mx, partial[2 * i + 1]);
     }
-    block_minmax(mn, mx);
+    tree_minmax(mn, mx);
     if (threadIdx.x == 0) result[0] = mn, result[1] = mx, result[2] = v[dc_at];
 }
 
@@ -428,10 +428,11 @@ int ab_fft2_forward_f32(ab_ctx *ctx, const ab_plane *image, const float *win_y, 
              (long long)image->rows, (long long)image->cols, (long long)fft_rows, (long long)fft_cols);
     AB_CHECK(ctx, (win_y == nullptr) == (win_x == nullptr), "win_y and win_x must both be given or both be NULL");
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, image, &in));
+    Scope sc(ctx);
+    const float *in = nullptr;
+    AB_TRY(sc.stage_in(image, &in));
     float2 *bt = nullptr, *spare = nullptr;
-    int rc = fft2_device(ctx, in.dptr, (int)in.rows, (int)in.cols, win_y, win_x, (int)fft_rows, (int)fft_cols, &bt, &spare);
+    int rc = fft2_device(ctx, in, (int)image->rows, (int)image->cols, win_y, win_x, (int)fft_rows, (int)fft_cols, &bt, &spare);
     if (rc == AB_OK) rc = launch_transpose(ctx, bt, out_on_device ? (float2 *)out : spare, (int)fft_cols, (int)fft_rows, (int)fft_cols);
     if (rc == AB_OK && !out_on_device) {
         const hipError_t e = hipMemcpyAsync(out, spare, (size_t)fft_rows * (size_t)fft_cols * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream);
@@ -441,7 +442,6 @@ int ab_fft2_forward_f32(ab_ctx *ctx, const ab_plane *image, const float *win_y, 
         const hipError_t e = hipStreamSynchronize(ctx->stream);  // (the result is complete, and the caller's windows are read, on return)
         if (e != hipSuccess && rc == AB_OK) rc = ab_set_error(ctx, AB_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
     }
-    ab_stage_release(ctx, &in);
     return rc;
 } AB_CATCH(ctx)
 
@@ -464,21 +464,18 @@ int ab_compute_power_spectrum(ab_ctx *ctx, const ab_plane *image, int32_t apply_
         hann_symmetric_f32(wy.size(), wy.data());
         hann_symmetric_f32(wx.size(), wx.data());
     }
-    StagedPlane in;
-    StagedOut so;
-    AB_TRY(ab_stage_in(ctx, image, &in));
-    int rc = ab_stage_out_begin(ctx, spectrum, &so);
-    if (rc != AB_OK) {
-        ab_stage_release(ctx, &in);
-        return rc;
-    }
+    Scope sc(ctx);
+    const float *in = nullptr;
+    float *o = nullptr;
+    AB_TRY(sc.stage_in(image, &in));
+    AB_TRY(sc.stage_out(spectrum, &o));
     float2 *bt = nullptr, *spare = nullptr;
-    rc = fft2_device(ctx, in.dptr, (int)in.rows, (int)in.cols, apply_window ? wy.data() : nullptr, apply_window ? wx.data() : nullptr, (int)size,
+    int rc = fft2_device(ctx, in, (int)image->rows, (int)image->cols, apply_window ? wy.data() : nullptr, apply_window ? wx.data() : nullptr, (int)size,
                      (int)size, &bt, &spare);
     if (rc == AB_OK) {
         const int s = (int)(size / disp);
         hipLaunchKernelGGL(spectrum_log_kernel, dim3(ab_div_up(disp, 32), ab_div_up(disp, 32)), dim3(32, 8), 0, ctx->stream, (const float2 *)bt,
-                           (int)size, s, so.dptr, (int)disp);
+                           (int)size, s, o, (int)disp);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "spectrum_log_kernel launch failed: %s", hipGetErrorString(e));
     }
@@ -486,9 +483,7 @@ int ab_compute_power_spectrum(ab_ctx *ctx, const ab_plane *image, int32_t apply_
         const hipError_t e = hipStreamSynchronize(ctx->stream);  // (the window tables are this call's: read before they go)
         if (e != hipSuccess && rc == AB_OK) rc = ab_set_error(ctx, AB_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
     }
-    if (rc == AB_OK) rc = ab_stage_out_finish(ctx, &so);
-    else ab_stage_out_abort(ctx, &so);
-    ab_stage_release(ctx, &in);
+    if (rc == AB_OK) rc = sc.finish_outs();
     if (rc == AB_OK) {
         result->display_rows = disp;
         result->display_cols = disp;
@@ -512,11 +507,12 @@ int ab_spectrum_to_u8(ab_ctx *ctx, const ab_plane *spectrum, uint8_t *out_u8, in
     AB_TRY(ab_scratch(ctx, head + (out_on_device ? 0 : (size_t)n), (void **)&scratch));
     float *partial = (float *)scratch, *triple = partial + 2 * kRedBlocks;
     uint8_t *bytes_dev = out_on_device ? out_u8 : (uint8_t *)(scratch + head);
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, spectrum, &in));
+    Scope sc(ctx);
+    const float *in = nullptr;
+    AB_TRY(sc.stage_in(spectrum, &in));
     const int64_t dc_at = (spectrum->rows / 2) * spectrum->cols + spectrum->cols / 2;  // (mod.rs:77)
-    hipLaunchKernelGGL(u8_minmax_kernel, dim3(blocks), dim3(kRedBlock), 0, ctx->stream, in.dptr, n, partial);
-    hipLaunchKernelGGL(u8_minmax_final_kernel, dim3(1), dim3(kRedBlock), 0, ctx->stream, (const float *)partial, blocks, in.dptr, dc_at, triple);
+    hipLaunchKernelGGL(u8_minmax_kernel, dim3(blocks), dim3(kRedBlock), 0, ctx->stream, in, n, partial);
+    hipLaunchKernelGGL(u8_minmax_final_kernel, dim3(1), dim3(kRedBlock), 0, ctx->stream, (const float *)partial, blocks, in, dc_at, triple);
     float host[3] = {0.0f, 0.0f, 0.0f};
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(host, triple, sizeof host, hipMemcpyDeviceToHost, ctx->stream);
@@ -524,13 +520,12 @@ int ab_spectrum_to_u8(ab_ctx *ctx, const ab_plane *spectrum, uint8_t *out_u8, in
     if (e == hipSuccess) {
         const float range = std::fmax(host[1] - host[0], 1e-10f);  // (mod.rs:75-76), in f32
         const float inv = 255.0f / range;
-        hipLaunchKernelGGL(u8_scale_kernel, dim3((unsigned)((n + kRedBlock - 1) / kRedBlock)), dim3(kRedBlock), 0, ctx->stream, in.dptr, n, host[0], inv,
+        hipLaunchKernelGGL(u8_scale_kernel, dim3((unsigned)((n + kRedBlock - 1) / kRedBlock)), dim3(kRedBlock), 0, ctx->stream, in, n, host[0], inv,
                            bytes_dev);
         e = hipGetLastError();
     }
     if (e == hipSuccess && !out_on_device) e = hipMemcpyAsync(out_u8, bytes_dev, (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    ab_stage_release(ctx, &in);
     if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "ab_spectrum_to_u8 failed: %s", hipGetErrorString(e));
     if (min_val) *min_val = host[0];
     if (max_val) *max_val = host[1];

@@ -8,7 +8,7 @@
 // (any 4-byte aligned f32 plane and any u8 pointer are accepted: the scalar loop takes what the wide accesses cannot).
 // The per-pixel arithmetic is f64 in the reference's evaluation order, so the u8 output is
 // bit-exact against the CPU restatement.
-#include "ab_common.hpp"
+#include "entry_host.hpp"
 #include "stf_device.hpp"
 
 #include <cmath>
@@ -138,29 +138,20 @@ int ab_apply_stf_u8(ab_ctx *ctx, const ab_plane *img, const ab_stf_params *p, co
                     int32_t out_on_device) try {
     if (!ctx) return AB_ERR_INVALID;
     AB_CHECK(ctx, img && p && st && out, "null argument");
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    const int64_t n = in.rows * in.cols;
-    int rc = AB_OK;
-    if (out_on_device) {
-        rc = ab_stf_u8_device(ctx, in.dptr, n, p, st, out);
-    } else {
-        void *d = nullptr;
-        hipError_t e = hipMalloc(&d, (size_t)n);
-        if (e != hipSuccess) {
-            rc = ab_set_error(ctx, AB_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e));
-        } else {
-            rc = ab_stf_u8_device(ctx, in.dptr, n, p, st, (uint8_t *)d);
-            if (rc == AB_OK) {
-                e = hipMemcpyAsync(out, d, (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-                if (e != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "D2H: %s", hipGetErrorString(e));
-            }
-            (void)hipFree(d);
-        }
-    }
-    ab_stage_release(ctx, &in);
-    return rc;
+    Scope sc(ctx);
+    const float *in = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    const int64_t n = img->rows * img->cols;
+    if (out_on_device) return ab_stf_u8_device(ctx, in, n, p, st, out);
+    void *d = nullptr;
+    hipError_t e = hipMalloc(&d, (size_t)n);
+    if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e));
+    sc.adopt(d);
+    AB_TRY(ab_stf_u8_device(ctx, in, n, p, st, (uint8_t *)d));
+    e = hipMemcpyAsync(out, d, (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "D2H: %s", hipGetErrorString(e));
+    return AB_OK;
 } AB_CATCH(ctx)
 
 int ab_apply_stf_f32(ab_ctx *ctx, const ab_plane *img, const ab_stf_params *p, const ab_image_stats *st,
@@ -168,19 +159,13 @@ int ab_apply_stf_f32(ab_ctx *ctx, const ab_plane *img, const ab_stf_params *p, c
     if (!ctx) return AB_ERR_INVALID;
     AB_CHECK(ctx, img && p && st && out, "null argument");
     AB_CHECK(ctx, img->rows == out->rows && img->cols == out->cols, "apply_stf_f32 keeps the image dims");
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    StagedOut so;
-    int rc = ab_stage_out_begin(ctx, out, &so);
-    if (rc == AB_OK) {
-        rc = ab_stf_f32_device(ctx, in.dptr, in.rows * in.cols, p, st, so.dptr);
-        if (rc == AB_OK)
-            rc = ab_stage_out_finish(ctx, &so);
-        else
-            ab_stage_out_abort(ctx, &so);
-    }
-    ab_stage_release(ctx, &in);
-    return rc;
+    Scope sc(ctx);
+    const float *in = nullptr;
+    float *o = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    AB_TRY(sc.stage_out(out, &o));
+    AB_TRY(ab_stf_f32_device(ctx, in, img->rows * img->cols, p, st, o));
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 int ab_bench_copy(ab_ctx *ctx, const float *src_dev, float *dst_dev, size_t n_floats) try {

@@ -1,6 +1,6 @@
 // Subframe scoring: core/analysis/subframe.rs.  The pixel work is detect_stars(image, 4.0) -- the
 // detect.hip kernels, one frame per worker stream -- and the rest is a handful of f64 scalars per frame on the host.
-#include "ab_common.hpp"
+#include "entry_host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -36,13 +36,14 @@ double compute_weight(double fwhm, double ecc, double snr, double noise, const a
 }
 
 int analyze_one(ab_ctx *ctx, const ab_plane *img, const ab_subframe_weight_config &c, ab_subframe_metrics *out, const double *bg = nullptr) {  // :51-121
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, img, &in));
     std::vector<ab_detected_star> stars;
     double bm = 0.0, bs = 1.0;
-    const int rc = ab_detect_stars_device(ctx, in.dptr, in.rows, in.cols, kDetectionSigma, &stars, &bm, &bs, ab_pixel_xf(), (size_t)-1, false, bg);
-    ab_stage_release(ctx, &in);
-    if (rc != AB_OK) return rc;
+    {
+        Scope sc(ctx);
+        const float *in = nullptr;
+        AB_TRY(sc.stage_in(img, &in));
+        AB_TRY(ab_detect_stars_device(ctx, in, img->rows, img->cols, kDetectionSigma, &stars, &bm, &bs, ab_pixel_xf(), (size_t)-1, false, bg));
+    }
     *out = ab_subframe_metrics{};
     out->star_count = stars.size();
     out->background_median = bm;

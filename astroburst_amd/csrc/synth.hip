@@ -15,12 +15,12 @@
 #include <algorithm>
 #include <cmath>
 
-#include "ab_common.hpp"
+#include "entry_host.hpp"
+
 #include "chacha12.hpp"
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kTile = 16;  // pass B: 16 x 16 pixels per workgroup
 constexpr double kTwoPi = 2.0 * 3.14159265358979323846;
 
@@ -529,14 +529,11 @@ int generate_impl(ab_ctx *ctx, const ab_synth_config &cfg, ab_plane_mut *frames_
             AB_TRY(launch_apply_flat(ctx, img_dev, flat_dev, npx));
             src = img_dev;
         }
-        StagedOut so;
-        AB_TRY(ab_stage_out_begin(ctx, &frames_out[i], &so));
-        const int rc = launch_noise(ctx, src, npx, noise_seed(i), np, so.dptr, flags_dev + i);
-        if (rc != AB_OK) {
-            ab_stage_out_abort(ctx, &so);
-            return rc;
-        }
-        AB_TRY(ab_stage_out_finish(ctx, &so));
+        Scope frame(ctx);  // (stages only: an inner scope's alloc() would start at slot 0 again)
+        float *o = nullptr;
+        AB_TRY(frame.stage_out(&frames_out[i], &o));
+        AB_TRY(launch_noise(ctx, src, npx, noise_seed(i), np, o, flags_dev + i));
+        AB_TRY(frame.finish_outs());
         AB_TRY(ab_progress(ctx, "synth", (uint64_t)i + 1, (uint64_t)n));
     }
     // the frames' routes, read once
@@ -631,14 +628,11 @@ int ab_synth_render_stars(ab_ctx *ctx, const ab_synth_star *stars, size_t n, con
     AB_CHECK(ctx, psf && out && (stars || n == 0), "null argument");
     AB_CHECK(ctx, out->data && out->rows > 0 && out->cols > 0, "the output plane is empty");
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedOut so;
-    AB_TRY(ab_stage_out_begin(ctx, out, &so));
-    const int rc = render_device(ctx, stars, n, *psf, out->rows, out->cols, so.dptr);
-    if (rc != AB_OK) {
-        ab_stage_out_abort(ctx, &so);
-        return rc;
-    }
-    return ab_stage_out_finish(ctx, &so);
+    Scope sc(ctx);
+    float *o = nullptr;
+    AB_TRY(sc.stage_out(out, &o));
+    AB_TRY(render_device(ctx, stars, n, *psf, out->rows, out->cols, o));
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 int ab_synth_flat_field(ab_ctx *ctx, uint64_t seed, double vignette_strength, ab_plane_mut *out) try {
@@ -646,14 +640,11 @@ int ab_synth_flat_field(ab_ctx *ctx, uint64_t seed, double vignette_strength, ab
     AB_CHECK(ctx, out, "null argument");
     AB_CHECK(ctx, out->data && out->rows > 0 && out->cols > 0, "the output plane is empty");
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedOut so;
-    AB_TRY(ab_stage_out_begin(ctx, out, &so));
-    const int rc = launch_flat(ctx, out->rows, out->cols, seed, vignette_strength, so.dptr);
-    if (rc != AB_OK) {
-        ab_stage_out_abort(ctx, &so);
-        return rc;
-    }
-    return ab_stage_out_finish(ctx, &so);
+    Scope sc(ctx);
+    float *o = nullptr;
+    AB_TRY(sc.stage_out(out, &o));
+    AB_TRY(launch_flat(ctx, out->rows, out->cols, seed, vignette_strength, o));
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 int ab_synth_apply_flat_field(ab_ctx *ctx, ab_plane_mut *img_inout, const ab_plane *flat) try {
@@ -663,22 +654,19 @@ int ab_synth_apply_flat_field(ab_ctx *ctx, ab_plane_mut *img_inout, const ab_pla
     AB_CHECK(ctx, img_inout->rows == flat->rows && img_inout->cols == flat->cols, "the image and the flat must have equal dims");
     AB_HIP(ctx, hipSetDevice(ctx->device));
     const ab_plane view{img_inout->data, img_inout->rows, img_inout->cols, img_inout->on_device};
-    StagedPlane img, fl;
-    AB_TRY(ab_stage_in(ctx, &view, &img));
-    int rc = ab_stage_in(ctx, flat, &fl);
-    if (rc == AB_OK) {
-        const int64_t n = img.rows * img.cols;
-        float *img_dev = const_cast<float *>(img.dptr);  // (the caller's own mutable plane, or the staged copy of it)
-        rc = launch_apply_flat(ctx, img_dev, fl.dptr, n);
-        if (rc == AB_OK && img.owned) {
-            hipError_t e = hipMemcpyAsync(img_inout->data, img_dev, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "D2H copy failed: %s", hipGetErrorString(e));
-        }
-        ab_stage_release(ctx, &fl);
+    Scope sc(ctx);
+    const float *img = nullptr, *fl = nullptr;
+    AB_TRY(sc.stage_in(&view, &img));
+    AB_TRY(sc.stage_in(flat, &fl));
+    const int64_t n = view.rows * view.cols;
+    float *img_dev = const_cast<float *>(img);  // (the caller's own mutable plane, or the staged copy of it)
+    AB_TRY(launch_apply_flat(ctx, img_dev, fl, n));
+    if (!view.on_device) {
+        hipError_t e = hipMemcpyAsync(img_inout->data, img_dev, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "D2H copy failed: %s", hipGetErrorString(e));
     }
-    ab_stage_release(ctx, &img);
-    return rc;
+    return AB_OK;
 } AB_CATCH(ctx)
 
 int ab_synth_apply_noise(ab_ctx *ctx, const ab_plane *img, const ab_synth_noise_params *params, ab_plane_mut *out, ab_synth_result *res) try {
@@ -694,41 +682,32 @@ int ab_synth_apply_noise(ab_ctx *ctx, const ab_plane *img, const ab_synth_noise_
     unsigned int *flag_dev = nullptr;
     AB_TRY(ab_workspace(ctx, AB_WS_SCOPE3, sizeof(unsigned int), (void **)&flag_dev));
     AB_HIP(ctx, hipMemsetAsync(flag_dev, 0, sizeof(unsigned int), ctx->stream));
-    StagedPlane in;
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    StagedOut so;
-    int rc = ab_stage_out_begin(ctx, out, &so);
-    if (rc == AB_OK) {
-        rc = launch_noise(ctx, in.dptr, n, params->seed, np, so.dptr, flag_dev);
-        if (rc == AB_OK)
-            rc = ab_stage_out_finish(ctx, &so);
-        else
-            ab_stage_out_abort(ctx, &so);
-    }
+    Scope sc(ctx);
+    const float *in = nullptr;
+    float *o = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    AB_TRY(sc.stage_out(out, &o));
+    AB_TRY(launch_noise(ctx, in, n, params->seed, np, o, flag_dev));
+    AB_TRY(sc.finish_outs());
     unsigned int flag = 0;
-    if (rc == AB_OK) {
-        hipError_t e = hipMemcpyAsync(&flag, flag_dev, sizeof flag, hipMemcpyDeviceToHost, ctx->stream);
+    hipError_t e = hipMemcpyAsync(&flag, flag_dev, sizeof flag, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "reading the route flag failed: %s", hipGetErrorString(e));
+    if (!flag) return AB_OK;
+    // the general route: the reference's serial walk on the host
+    std::vector<float> host_in, host_out((size_t)n);
+    const float *src = img->data;
+    if (img->on_device) {
+        host_in.resize((size_t)n);
+        e = hipMemcpyAsync(host_in.data(), in, bytes, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "reading the route flag failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return ab_set_error(ctx, AB_ERR_HIP, "D2H copy failed: %s", hipGetErrorString(e));
+        src = host_in.data();
     }
-    if (rc == AB_OK && flag) {  // the general route: the reference's serial walk on the host
-        std::vector<float> host_in, host_out((size_t)n);
-        const float *src = img->data;
-        if (img->on_device) {
-            host_in.resize((size_t)n);
-            hipError_t e = hipMemcpyAsync(host_in.data(), in.dptr, bytes, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) rc = ab_set_error(ctx, AB_ERR_HIP, "D2H copy failed: %s", hipGetErrorString(e));
-            src = host_in.data();
-        }
-        if (rc == AB_OK) {
-            host_apply_noise(src, n, params->seed, np, host_out.data());
-            rc = store_plane(ctx, out, host_out.data(), bytes);
-            if (rc == AB_OK && res) res->frames_on_host = 1;
-        }
-    }
-    ab_stage_release(ctx, &in);
-    return rc;
+    host_apply_noise(src, n, params->seed, np, host_out.data());
+    AB_TRY(store_plane(ctx, out, host_out.data(), bytes));
+    if (res) res->frames_on_host = 1;
+    return AB_OK;
 } AB_CATCH(ctx)
 
 int ab_synth_generate(ab_ctx *ctx, const ab_synth_config *cfg, ab_plane_mut *noisy_out, ab_plane_mut *truth_out, ab_synth_star *stars_out, size_t cap,

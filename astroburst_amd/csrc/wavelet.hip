@@ -21,7 +21,7 @@
 //                                from c_S, applies the finite-and-non-negative gate and writes the output: thresholding never
 //                                makes a pass of its own (a recomputed c_j - c_{j+1} has the bits of a stored one)
 // No atomics touch a pixel: two calls are bit-identical.
-#include "ab_common.hpp"
+#include "entry_host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -37,7 +37,6 @@ constexpr int kFusedStepLimit = 32;       // (64 + 4 * 32) * 256 B = 48 KiB of L
 // The hand-over between the two forms.  0: every scale takes the two-pass form.  The fused kernel has not been measured against it
 // yet, so the release library never selects it; it stays reachable through the developer switch below.
 constexpr int kFusedMaxStepDefault = 0;
-constexpr int kBlock = 256;
 
 // B3_KERNEL_1D (wavelet.rs:35)
 #define AB_B3_TAPS {1.0f / 16.0f, 4.0f / 16.0f, 6.0f / 16.0f, 4.0f / 16.0f, 1.0f / 16.0f}
@@ -381,15 +380,13 @@ int ab_wavelet_denoise(ab_ctx *ctx, const ab_plane *img, const ab_wavelet_config
     const size_t bytes = (size_t)img->rows * (size_t)img->cols * sizeof(float);
     AB_CHECK(ctx, !ranges_overlap(img->data, bytes, out->data, bytes), "output must not overlap the image");
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    StagedPlane in;
-    StagedOut so;
-    AB_TRY(ab_stage_in(ctx, img, &in));
-    int rc = ab_stage_out_begin(ctx, out, &so);
-    if (rc == AB_OK) rc = wavelet_device(ctx, in.dptr, in.rows, in.cols, *cfg, so.dptr, res);
-    if (rc == AB_OK) rc = ab_stage_out_finish(ctx, &so);
-    else ab_stage_out_abort(ctx, &so);
-    ab_stage_release(ctx, &in);
-    return rc;
+    Scope sc(ctx);
+    const float *in = nullptr;
+    float *o = nullptr;
+    AB_TRY(sc.stage_in(img, &in));
+    AB_TRY(sc.stage_out(out, &o));
+    AB_TRY(wavelet_device(ctx, in, img->rows, img->cols, *cfg, o, res));
+    return sc.finish_outs();
 } AB_CATCH(ctx)
 
 }  // extern "C"
