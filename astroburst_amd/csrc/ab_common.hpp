@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/astroburst_hip.h"
+#include "bg_pipe_plan.hpp"
 
 #define AB_REJ_SLOTS 2048
 #define AB_STACK_LIST_SLOTS 2048  // lists of the pixels a stacking fast pass hands over, by wave index (no hot atomic address)
@@ -41,7 +42,7 @@ enum {
     AB_WS_SUBSAMPLE,          // the <= ~100 000-pixel subsample normalize_for_detection takes its percentiles from
     AB_WS_REGISTER_GROUP,     // the target-side matcher workspaces of a group of frames (affine.hip)
     AB_WS_PHASE_TABLES,       // two sets of Hann windows + FFT twiddles of the phase correlation, kept between calls (phase_corr.hip)
-    AB_WS_PIPE_TABLES,        // plane pointers + transforms of a background pipeline (detect.hip: ab_bg_pipeline_begin, ab_bg_pipeline_begin_fed)
+    AB_WS_PIPE_TABLES,        // a background pipeline's plane pointers | transforms, both rounded up to 16 bytes (detect.hip: pipe_setup, the one layout of both forms)
     AB_WS_PIPE_SUBSAMPLE,     // its subsamples (one per plane: the chunks' percentile launches overlap)
     AB_WS_SCOPE0,             // eight slots for the planes an entry point needs for the length of one call (masked stretch: luminance,
     AB_WS_SCOPE1,             // mask, disc table, coverage counter, chain state; SPCC: luminance, apertures, fluxes): grow-only like every
@@ -141,7 +142,9 @@ struct ab_ctx {
     int shard_chunks_timed = 0;
     bool stack_keep_counters = false;  // ab_stack_device: do not clear the rejection counters / restart the stack events (chunks 2 .. K of one stack)
     // the background-tile pipeline of a registration batch (detect.hip: ab_bg_pipeline_*): its own stream, one event per chunk
-    // of frames, its own pinned result buffer (the context's general one may be reallocated by the reference's detection)
+    // of frames, its own pinned result buffer (the context's general one may be reallocated by the reference's detection):
+    // aux_pinned = tile results | plane pointers | transforms | the fed form's percentile records (detect.hip: pipe_setup).
+    // The event lists are grow-only (ab_events_reserve)
     hipStream_t aux_stream = nullptr;
     hipStream_t warp_stream = nullptr;  // the warps of a registration batch (affine.hip): off the workers' own streams
     std::vector<hipEvent_t> aux_events;
@@ -286,6 +289,8 @@ int ab_catch(ab_ctx *ctx, const char *fn);
 extern thread_local std::string *ab_tls_error_sink;  // see ab_set_error
 int ab_scratch(ab_ctx *ctx, size_t bytes, void **out);
 int ab_pinned(ab_ctx *ctx, size_t bytes, void **out);
+// at least n untimed events in one of the context's grow-only lists (they live until the context dies)
+int ab_events_reserve(ab_ctx *ctx, std::vector<hipEvent_t> *events, size_t n);
 // persistent workspace `slot` of at least `bytes` (contents are undefined after a growth)
 int ab_workspace(ab_ctx *ctx, int slot, size_t bytes, void **out);
 // the same for a caller whose contract names AB_ERR_NOMEM: exhausted device memory is that status, not AB_ERR_HIP
@@ -394,14 +399,15 @@ int ab_detect_stars_device(ab_ctx *ctx, const float *img, int64_t rows, int64_t 
                            const double *bg_known = nullptr /* {bg_median, bg_sigma} of estimate_background, if the caller has them */);
 // estimate_background of a batch of equally sized planes as a pipeline: the tile kernel of `chunk` planes at a time on the
 // context's auxiliary stream, an event after each chunk; ab_bg_pipeline_get blocks until plane i's chunk has run and reduces
-// its tiles (any thread)
+// its tiles (any thread).  Both begin functions share one plan, one set-up and one enqueue per chunk (detect.hip: PipePlan); the
+// chunk arithmetic is bg_pipe_plan.hpp's.  A caller declares an ab_bg_pipeline_guard right after the pipeline and drains nothing itself.
 struct ab_bg_pipeline {
-    bool on = false;
+    bool on = false;       // every chunk is enqueued, or a feeder thread enqueues them: ab_bg_pipeline_get answers
+    bool started = false;  // commands that belong to the caller's frames may be in the pipeline's streams (also after a begin that failed part-way)
     const void *tiles = nullptr;  // pinned TileOut[n][ntiles]
-    const hipEvent_t *events = nullptr;
-    int ntiles = 0, chunk = 1;
-    int first = 0;  // planes of the FIRST launch when it is smaller than the others (0: `chunk` like every launch): chunk of plane i = i < first ? 0 : 1 + (i - first) / chunk
-    size_t n = 0;
+    const hipEvent_t *events = nullptr;  // one per chunk
+    int ntiles = 0;
+    PipeChunks chunks;  // the n planes' launches: plane i's event is events[chunks.chunk_of(i)]
     const ab_pixel_xf *xf_host = nullptr;  // fed pipeline: plane i's transform, valid once ab_bg_pipeline_get(i) has returned
     struct ab_bg_feed_impl *feed = nullptr;  // the feeder thread of a pipeline whose planes are still landing (detect.hip)
     // the candidate lists of plane i's tiles (DEVICE; valid once ab_bg_pipeline_get(i) has returned): entries at cand_ent + (i * ntiles
@@ -429,14 +435,23 @@ static inline ab_frame_cand ab_bg_pipeline_cand(const ab_bg_pipeline *p, size_t 
     }
     return c;
 }
-void ab_bg_pipeline_end(ab_bg_pipeline *p);  // joins the feeder, if any (before the streams are drained / the planes released)
-// the pipeline fed chunk by chunk: the percentiles run per chunk on the device (no host join before the first tile launch); with
-// `landed` events (nullable; a null entry = the plane is complete already) a feeder thread enqueues a chunk when its planes have landed
+// The one way out of a batch: stops and joins the feeder, if any, then drains the percentile and the auxiliary stream if the pipeline
+// was switched on or a begin failed part-way (their launches read the caller's frames).  Leaves *p switched off.
+void ab_bg_pipeline_end(ab_ctx *ctx, ab_bg_pipeline *p);
+struct ab_bg_pipeline_guard {  // ... on whatever path leaves the scope
+    ab_ctx *ctx;
+    ab_bg_pipeline *p;
+    ~ab_bg_pipeline_guard() { ab_bg_pipeline_end(ctx, p); }
+};
+// The two begin functions.  Either may leave *p switched off with AB_OK (planes too small for tiles): the frames then estimate their own.
 // want_cand: whole 256-px tiles also leave their candidate lists (ab_bg_pipeline_cand) for the labelling pass of a registration batch
-int ab_bg_pipeline_begin_fed(ab_ctx *ctx, const float *const *planes, size_t n, int64_t rows, int64_t cols, int chunk, const hipEvent_t *landed,
-                             ab_bg_pipeline *p, bool want_cand = false);
+// the pipeline of planes whose transforms the caller has (`xf`): every chunk is enqueued before the call returns
 int ab_bg_pipeline_begin(ab_ctx *ctx, const float *const *planes, size_t n, int64_t rows, int64_t cols, const ab_pixel_xf *xf, int chunk,
                          ab_bg_pipeline *p, bool want_cand = false);
+// the pipeline fed chunk by chunk: the percentiles run per chunk on the device (no host join before the first tile launch); with
+// `landed` events (nullable; a null entry = the plane is complete already) a feeder thread enqueues a chunk when its planes have landed
+int ab_bg_pipeline_begin_fed(ab_ctx *ctx, const float *const *planes, size_t n, int64_t rows, int64_t cols, int chunk, const hipEvent_t *landed,
+                             ab_bg_pipeline *p, bool want_cand = false);
 int ab_bg_pipeline_get(ab_ctx *ctx, const ab_bg_pipeline *p, size_t i, double *bg /* [2] */);
 // the percentile normalisation's parameters (xf->on = 0 where the reference returns image.clone())
 int ab_normalize_params_device(ab_ctx *ctx, const float *img, int64_t len, ab_pixel_xf *xf);

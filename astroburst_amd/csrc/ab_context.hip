@@ -384,6 +384,15 @@ int ab_pinned(ab_ctx *ctx, size_t bytes, void **out) {
     return AB_OK;
 }
 
+int ab_events_reserve(ab_ctx *ctx, std::vector<hipEvent_t> *events, size_t n) {
+    while (events->size() < n) {
+        hipEvent_t e;
+        AB_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        events->push_back(e);
+    }
+    return AB_OK;
+}
+
 int ab_stage_in(ab_ctx *ctx, const ab_plane *p, StagedPlane *out) {
     AB_CHECK(ctx, p && p->data && p->rows > 0 && p->cols > 0, "plane is null or has a zero dimension");
     out->rows = p->rows;

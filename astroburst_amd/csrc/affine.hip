@@ -1158,21 +1158,13 @@ int ab_register_frames_device(ab_ctx *ctx, const float *ref, const float *const 
     MatchWs w;
     AB_TRY(match_ws(ctx, &w));
     RefTable rt;
-    // normalize_for_detection's percentiles of every frame of the batch (targets, then the reference) up front: two launches, 64
+    // normalize_for_detection's percentiles of every frame of the batch (the reference, then the targets) up front: two launches, 64
     // percentile workgroups side by side (see ab_normalize_params_many_device)
-    std::vector<ab_pixel_xf> xfs;
+    std::vector<ab_pixel_xf> xfs;  // [f] = target f's, [n] = the reference's
     ab_bg_pipeline pipe;  // plane 0 = the reference, plane 1 + f = target f
-    // whatever path leaves this function, tile launches still in flight on the auxiliary stream (they read the caller's frames)
-    // are drained first
-    struct AuxDrain {
-        ab_ctx *c;
-        ab_bg_pipeline *p;
-        ~AuxDrain() {
-            ab_bg_pipeline_end(p);
-            if (p->on && c->pct_stream) (void)hipStreamSynchronize(c->pct_stream);
-            if (p->on && c->aux_stream) (void)hipStreamSynchronize(c->aux_stream);
-        }
-    } aux_drain{ctx, &pipe};
+    // whatever path leaves this function -- an error and a cancel included -- the feeder is joined and the tile launches still in
+    // flight (they read the caller's frames) are drained first
+    const ab_bg_pipeline_guard pipe_guard{ctx, &pipe};
     const bool have_xf = n >= 4 || landed != nullptr;
     // Round 4: frames that are still on the PCIe link (`landed`) go through the FED pipeline (ab_bg_pipeline_begin_fed): a chunk's
     // percentiles run on the device right before its tiles and wait for the chunk's upload events, so nothing is joined on the host
@@ -1182,11 +1174,14 @@ int ab_register_frames_device(ab_ctx *ctx, const float *ref, const float *const 
     static const bool force_fed = ab_dev_env("AB_PIPE_FED") != nullptr;
     static const bool want_cand = ab_dev_env("AB_NO_CAND_LISTS") == nullptr;  // (developer A/B: the labelling reads the frames as in round 5)
     const bool fed = have_xf && (landed != nullptr || force_fed);
-    if (fed) {
-        static const int chunk = ab_dev_env("AB_TILE_CHUNK") ? std::max(atoi(ab_dev_env("AB_TILE_CHUNK")), 1) : 16;
-        static const int fed_chunk = ab_dev_env("AB_FEED_CHUNK") ? std::max(atoi(ab_dev_env("AB_FEED_CHUNK")), 1) : 4;  // frames per launch while frames are still arriving
-        std::vector<const float *> order;  // reference first
-        std::vector<hipEvent_t> ev;
+    // Frames per tile launch (AB_TILE_CHUNK).  Device-resident frames: 0 = no pipeline, every frame's tiles in its own chain; measured
+    // 0 / 2 / 4 / 8 / 16 -> 17.6 / 17.5 / 17.2 / 17.0 / 17.4 ms for the stage, and in round 6 9.73 / 9.74 / 9.68 ms per step with 16 against
+    // 9.82 / 9.80 / 9.90 with 8 (profiles/r06_priority_ab.txt).  Fed frames: at least 1, and AB_FEED_CHUNK while frames are still arriving
+    static const int tile_chunk = ab_dev_env("AB_TILE_CHUNK") ? atoi(ab_dev_env("AB_TILE_CHUNK")) : 16;
+    static const int fed_chunk = ab_dev_env("AB_FEED_CHUNK") ? std::max(atoi(ab_dev_env("AB_FEED_CHUNK")), 1) : 4;
+    std::vector<const float *> order;  // the planes in the pipeline's order: the reference first
+    std::vector<hipEvent_t> ev;        // ... and the event behind each (null: the plane is complete)
+    if (have_xf) {
         order.push_back(ref);
         ev.push_back(nullptr);
         for (size_t i = 0; i < n; ++i) {
@@ -1194,31 +1189,24 @@ int ab_register_frames_device(ab_ctx *ctx, const float *ref, const float *const 
             ev.push_back(landed ? landed[i] : nullptr);
         }
         xfs.resize(n + 1);
+    }
+    if (fed) {
         AB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller's frames are complete before any other stream reads them
-        AB_TRY(ab_bg_pipeline_begin_fed(ctx, order.data(), n + 1, rows, cols, landed ? fed_chunk : chunk, landed ? ev.data() : nullptr, &pipe, want_cand));
+        AB_TRY(ab_bg_pipeline_begin_fed(ctx, order.data(), n + 1, rows, cols, landed ? fed_chunk : std::max(tile_chunk, 1), landed ? ev.data() : nullptr, &pipe,
+                                        want_cand));
         if (!pipe.on && landed)  // (planes too small for tiles, AB_TILE_LEGACY: the frames are waited for and the batch takes the path below)
             for (size_t i = 0; i < n; ++i)
                 if (landed[i]) AB_HIP(ctx, hipEventSynchronize(landed[i]));
     }
     if (have_xf && !pipe.on) {
-        std::vector<const float *> planes(targets, targets + n);
-        planes.push_back(ref);
-        xfs.resize(n + 1);
-        AB_TRY(ab_normalize_params_many_device(ctx, planes.data(), n + 1, rows * cols, xfs.data()));
+        std::vector<ab_pixel_xf> oxf(n + 1);  // the transforms in the pipeline's order
+        AB_TRY(ab_normalize_params_many_device(ctx, order.data(), n + 1, rows * cols, oxf.data()));
+        std::rotate_copy(oxf.begin(), oxf.begin() + 1, oxf.end(), xfs.begin());
         ab_upload_trace("percentiles joined, planes", (long)(n + 1));
         // ... and their background tiles: the tile kernel runs on its own stream, a few frames per launch, the reference first,
         // while the workers already label the frames whose tiles are done (register_one blocks on its frame's chunk)
-        static const int chunk = ab_dev_env("AB_TILE_CHUNK") ? atoi(ab_dev_env("AB_TILE_CHUNK")) : 16;  // (round 6: 16 frames per launch, 9.73 / 9.74 / 9.68 ms per step against 9.82 / 9.80 / 9.90 with 8: profiles/r06_priority_ab.txt)  // frames per launch (0: every frame's tiles in its own chain); measured 0 / 2 / 4 / 8 / 16 -> 17.6 / 17.5 / 17.2 / 17.0 / 17.4 ms for the stage
-        if (chunk > 0) {
-            std::vector<const float *> order;  // reference first
-            std::vector<ab_pixel_xf> oxf;
-            order.push_back(ref);
-            oxf.push_back(xfs[n]);
-            for (size_t i = 0; i < n; ++i) {
-                order.push_back(targets[i]);
-                oxf.push_back(xfs[i]);
-            }
-            AB_TRY(ab_bg_pipeline_begin(ctx, order.data(), n + 1, rows, cols, oxf.data(), chunk, &pipe, want_cand));
+        if (tile_chunk > 0) {
+            AB_TRY(ab_bg_pipeline_begin(ctx, order.data(), n + 1, rows, cols, oxf.data(), tile_chunk, &pipe, want_cand));
             ab_upload_trace("tile launches enqueued, planes", (long)(n + 1));
         }
     }
@@ -1235,22 +1223,23 @@ int ab_register_frames_device(ab_ctx *ctx, const float *ref, const float *const 
         return AB_OK;
     };
     hipStream_t warp_stream = nullptr;
-    // the warp of a frame (f64 VALU) overlaps the other workers' latency-bound detection passes
+    // the warp of a frame (f64 VALU, pair.rs:59-61) overlaps the other workers' latency-bound detection passes.  It needs nothing from
+    // the GPU but the frame: it goes to the batch's warp stream, so that the worker's next frame does not queue up behind it on
+    // the worker's own stream
+    auto warp_on_batch_stream = [&](ab_ctx *wc, size_t f) -> int {
+        if (!aligned) return AB_OK;
+        hipStream_t keep = wc->stream;
+        if (warp_stream) wc->stream = warp_stream;
+        const int rc = warp_out(wc, f);
+        wc->stream = keep;
+        return rc;
+    };
     auto one = [&](ab_ctx *wc, size_t f) -> int {
         double bg[2];
         if (pipe.on) AB_TRY(ab_bg_pipeline_get(wc, &pipe, f + 1, bg));
         if (pipe.xf_host) xfs[f] = pipe.xf_host[f + 1];  // (each worker writes its own frames' entries)
         AB_TRY(register_one(wc, w, rt, ref, targets[f], rows, cols, num_threads, &out[f], have_xf ? &xfs[f] : nullptr, pipe.on ? bg : nullptr));
-        if (aligned) {  // pair.rs:59-61
-            // the warp needs nothing from the GPU but the frame: it goes to the batch's warp stream, so that this worker's
-            // next frame does not queue up behind it on the worker's own stream
-            hipStream_t keep = wc->stream;
-            if (warp_stream) wc->stream = warp_stream;
-            const int rc = warp_out(wc, f);
-            wc->stream = keep;
-            if (rc != AB_OK) return rc;
-        }
-        return AB_OK;
+        return warp_on_batch_stream(wc, f);
     };
     // Round 4: the targets go through detection and matching in GROUPS of kGroup (AB_REGISTER_GROUP, default 4; 1 = frame by frame as
     // in rounds 2 / 3): the stage was bound by the number of launches the four hardware queues serialise, not by their work.
@@ -1273,18 +1262,11 @@ int ab_register_frames_device(ab_ctx *ctx, const float *ref, const float *const 
             cands[k] = ab_bg_pipeline_cand(&pipe, frames[k] + 1);  // (complete: the plane's chunk has run)
             if (pipe.xf_host) xfs[frames[k]] = pipe.xf_host[frames[k] + 1];  // (each worker writes its own frames' entries)
         }
-        const std::function<int(size_t)> warp_frame = [&](size_t f) -> int {
-            if (!aligned) return AB_OK;  // pair.rs:59-61
-            hipStream_t keep = wc->stream;
-            if (warp_stream) wc->stream = warp_stream;
-            const int rc = warp_out(wc, f);
-            wc->stream = keep;
-            return rc;
-        };
+        const std::function<int(size_t)> warp_frame = [&](size_t f) -> int { return warp_on_batch_stream(wc, f); };
         return register_group(wc, w, rt, ref, targets, frames, G, rows, cols, num_threads, out, xfs.data(), bgs, warp_frame, cands);
     };
     const size_t n_jobs = grouped ? n_groups : n;
-    const std::function<int(ab_ctx *, size_t)> job = grouped ? std::function<int(ab_ctx *, size_t)>(one_group) : std::function<int(ab_ctx *, size_t)>(one);
+    const std::function<int(ab_ctx *, size_t)> job = [&](ab_ctx *wc, size_t j) -> int { return grouped ? one_group(wc, j) : one(wc, j); };
     const bool inline_run = std::min<size_t>(n_jobs, (size_t)std::max(ctx->register_workers, 1)) <= 1;
     static const bool own_warp_stream = ab_dev_env("AB_NO_WARP_STREAM") == nullptr;
     // The warps run at LOW stream priority (round 6): they need nothing but a fitted transform and 4.35 ms of f64 issue slots, while
@@ -1293,16 +1275,15 @@ int ab_register_frames_device(ab_ctx *ctx, const float *ref, const float *const 
     // tile stream made it worse (10.82 / 10.78 / 10.92), both together no better than low warps alone.
     if (!inline_run && aligned && own_warp_stream) {
         if (!ctx->warp_stream) {
-        const hipError_t stream_rc = ab_stream_create_masked(ctx, &ctx->warp_stream, AB_DEV_NAME("AB_WARP_CU_MASK"), AB_DEV_NAME("AB_WARP_PRIO"), 1);  // (outside AB_HIP: its message would carry the developer variables' names)
-        AB_HIP(ctx, stream_rc);
-    }
+            const hipError_t stream_rc = ab_stream_create_masked(ctx, &ctx->warp_stream, AB_DEV_NAME("AB_WARP_CU_MASK"), AB_DEV_NAME("AB_WARP_PRIO"), 1);  // (outside AB_HIP: its message would carry the developer variables' names)
+            AB_HIP(ctx, stream_rc);
+        }
         warp_stream = ctx->warp_stream;
     }
     if (inline_run) {  // the reference first, on ctx
         int rc = prepare_reference();
         rt.publish(rc, rc == AB_OK && rt.stars.size() >= kMinMatchesRigid);
         if (rc == AB_OK) rc = ab_parallel_frames(ctx, n_jobs, "registration", job);
-        if (pipe.on) (void)hipStreamSynchronize(ctx->aux_stream);  // (an error or a cancel may leave tile launches in flight: they read the caller's frames)
         return rc;
     }
     AB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller's frames are complete before any other stream reads them
@@ -1318,7 +1299,6 @@ int ab_register_frames_device(ab_ctx *ctx, const float *ref, const float *const 
     if (warp_stream) (void)hipStreamSynchronize(warp_stream);
     ab_upload_trace("warp stream drained", 0);
     if (!landed) ab_upload_trace("registration returns", (long)n);  // the aligned frames are complete when this call returns
-    if (pipe.on) (void)hipStreamSynchronize(ctx->aux_stream);  // (an error or a cancel may leave tile launches in flight: they read the caller's frames)
     return prep_rc != AB_OK ? prep_rc : rc;
 }
 
@@ -1416,11 +1396,7 @@ int ab_align_pairs_affine(ab_ctx *ctx, const ab_plane *reference, const ab_plane
         const hipError_t stream_rc = ab_stream_create_masked(ctx, &ctx->upload_stream, nullptr, AB_DEV_NAME("AB_UPLOAD_PRIO"), 1);  // (outside AB_HIP: its message would carry the developer variables' names)
         AB_HIP(ctx, stream_rc);
     }
-    while (ctx->upload_events.size() < slots) {
-        hipEvent_t e;
-        AB_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ctx->upload_events.push_back(e);
-    }
+    AB_TRY(ab_events_reserve(ctx, &ctx->upload_events, slots));
     // whatever leaves this function, the copies (they read the caller's memory) have drained first
     struct UploadDrain {
         ab_ctx *c;

@@ -2179,10 +2179,9 @@ static int launch_tile_kernels(ab_ctx *ctx, hipStream_t stream, int which, const
 static int tile_stats_host(ab_ctx *ctx, const float *img, int64_t rows, int64_t cols, int64_t ld, int64_t tile_size, ab_pixel_xf xf,
                            std::vector<TileOut> *out, int *ntx_out) {
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    const int step = (int)std::max<int64_t>(tile_size, 16);
-    AB_CHECK(ctx, step <= 256, "background tiles larger than 256 px are not supported (tile_size %lld)", (long long)tile_size);
-    const int nty = (int)((rows + step - 1) / step), ntx = (int)((cols + step - 1) / step);
-    const int ntiles = nty * ntx;
+    AB_CHECK(ctx, tile_size <= 256, "background tiles larger than 256 px are not supported (tile_size %lld)", (long long)tile_size);
+    const TileGrid grid = ab_tile_grid_of(rows, cols, tile_size);
+    const int step = grid.step, ntx = grid.ntx, ntiles = grid.ntiles;
     // small results go straight into the context's pinned host buffer (device-visible): no copy command, no bounce
     // through the runtime's staging pages for a pageable destination, just the stream sync
     void *pin = nullptr;
@@ -2253,134 +2252,58 @@ static inline TileCand cand_at(const TileCand &c, size_t plane, int ntiles) {
 // the other frames' small kernels aside and shared their in-order queues.  (One launch for all 64 frames followed by a
 // synchronisation was slower than the per-frame form -- 5.9 ms during which nothing else runs: 19.0 against 18.0 ms for the
 // stage; the pipeline measures 17.1.)
-int ab_bg_pipeline_begin(ab_ctx *ctx, const float *const *planes, size_t n, int64_t rows, int64_t cols, const ab_pixel_xf *xf, int chunk,
-                         ab_bg_pipeline *p, bool want_cand) {
-    *p = ab_bg_pipeline();
-    static const bool legacy = ab_dev_env("AB_TILE_LEGACY") != nullptr;
-    if (legacy || n == 0 || rows < 3 || cols < 3 || chunk < 1) return AB_OK;
-    AB_HIP(ctx, hipSetDevice(ctx->device));
-    const int64_t m = std::min(rows, cols);
-    const int64_t tile_size = std::min<int64_t>(std::max<int64_t>(m / 8, 32), 256);  // detect_stars' choice (:100)
-    const int step = (int)std::max<int64_t>(tile_size, 16);
-    const int nty = (int)((rows + step - 1) / step), ntx = (int)((cols + step - 1) / step), ntiles = nty * ntx;
-    if (!ctx->aux_stream) {
-        const hipError_t stream_rc = ab_stream_create_masked(ctx, &ctx->aux_stream, AB_DEV_NAME("AB_TILE_CU_MASK"), AB_DEV_NAME("AB_TILE_PRIO"), 0);  // (outside AB_HIP: its message would carry the developer variables' names)
-        AB_HIP(ctx, stream_rc);
-    }
-    // the first launch holds the reference and the first group's targets only (AB_TILE_FIRST, default 5; 0 = `chunk` like the rest):
-    // nothing else can run until a group's tiles are done, and eight frames' tiles are ~300 us of an otherwise idle chip
-    static const int first_env = ab_dev_env("AB_TILE_FIRST") ? atoi(ab_dev_env("AB_TILE_FIRST")) : 5;
-    const size_t first = (first_env > 0 && first_env < chunk && (size_t)first_env < n) ? (size_t)first_env : 0;
-    const size_t nchunks = first ? 1 + (n - first + (size_t)chunk - 1) / (size_t)chunk : (n + (size_t)chunk - 1) / (size_t)chunk;
-    while (ctx->aux_events.size() < nchunks) {
-        hipEvent_t e;
-        AB_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ctx->aux_events.push_back(e);
-    }
-    // the tile results, and behind them the staging copy of the plane-pointer and transform tables: the callers' tables are locals
-    // in pageable memory, and an asynchronous copy out of those is only safe while the runtime happens to stage it synchronously
-    const size_t ptr_bytes = n * sizeof(const float *), xf_bytes = n * sizeof(ab_pixel_xf);
-    const size_t tiles_bytes = (n * (size_t)ntiles * sizeof(TileOut) + 63) & ~(size_t)63;
-    const size_t need = tiles_bytes + ((ptr_bytes + 15) & ~(size_t)15) + xf_bytes;
-    if (need > ctx->aux_pinned_bytes) {
-        if (ctx->aux_pinned) {
-            AB_HIP(ctx, hipStreamSynchronize(ctx->aux_stream));
-            AB_HIP(ctx, hipHostFree(ctx->aux_pinned));
-            ctx->aux_pinned = nullptr;
-            ctx->aux_pinned_bytes = 0;
-        }
-        AB_HIP(ctx, hipHostMalloc(&ctx->aux_pinned, need, hipHostMallocDefault));
-        ctx->aux_pinned_bytes = need;
-    }
-    char *dv = nullptr;  // device copies of the plane pointers and transforms
-    AB_TRY(ab_workspace(ctx, AB_WS_PIPE_TABLES, ptr_bytes + xf_bytes + 64, (void **)&dv));
-    const float **dplanes = (const float **)dv;
-    ab_pixel_xf *dxf = (ab_pixel_xf *)(dv + ((ptr_bytes + 15) & ~(size_t)15));
-    TileCand cand;
-    if (want_cand) AB_TRY(pipeline_cand_lists(ctx, n, ntiles, step, &cand));
-    char *stage = (char *)ctx->aux_pinned + tiles_bytes;
-    memcpy(stage, planes, ptr_bytes);
-    memcpy(stage + ((ptr_bytes + 15) & ~(size_t)15), xf, xf_bytes);
-    // from the first enqueue on, a failure drains the auxiliary stream before it returns: the launches read the caller's frames
-    auto enqueue = [&]() -> int {
-        AB_HIP(ctx, hipMemcpyAsync(dplanes, stage, ptr_bytes, hipMemcpyHostToDevice, ctx->aux_stream));
-        AB_HIP(ctx, hipMemcpyAsync(dxf, stage + ((ptr_bytes + 15) & ~(size_t)15), xf_bytes, hipMemcpyHostToDevice, ctx->aux_stream));
-        if (cand.ent) AB_HIP(ctx, hipMemsetAsync(cand.cut, 0xff, n * (size_t)ntiles * sizeof(float), ctx->aux_stream));  // NaN: "no list" until a tile says otherwise
-        for (size_t c = 0; c < nchunks; ++c) {
-            const size_t begin = first ? (c == 0 ? 0 : first + (c - 1) * (size_t)chunk) : c * (size_t)chunk;
-            const size_t cnt = (first && c == 0) ? first : std::min<size_t>((size_t)chunk, n - begin);
-            AB_TRY(launch_tile_kernels(ctx, ctx->aux_stream, 1, nullptr, rows, cols, cols, step, ntx, ntiles, (int)cnt, ab_pixel_xf(),
-                                       (TileOut *)ctx->aux_pinned + begin * (size_t)ntiles, (const float *const *)(dplanes + begin),
-                                       (const ab_pixel_xf *)(dxf + begin), cand_at(cand, begin, ntiles)));
-            AB_HIP(ctx, hipEventRecord(ctx->aux_events[c], ctx->aux_stream));
-        }
-        AB_HIP(ctx, hipGetLastError());
-        return AB_OK;
-    };
-    const int rc = enqueue();
-    if (rc != AB_OK) {
-        (void)hipStreamSynchronize(ctx->aux_stream);
-        return rc;
-    }
-    p->on = true;
-    p->tiles = ctx->aux_pinned;
-    p->events = ctx->aux_events.data();
-    p->ntiles = ntiles;
-    p->chunk = chunk;
-    p->first = (int)first;
-    p->n = n;
-    p->cand_ent = cand.ent;
-    p->cand_cnt = cand.cnt;
-    p->cand_cut = cand.cut;
-    p->cand_step = cand.ent ? step : 0;
-    return AB_OK;
-}
-
-// The same pipeline FED chunk by chunk (round 4): nothing is known about a plane on the host before its chunk has run.  The
-// percentiles of normalize_for_detection (subsample + radix select, one workgroup per plane) run per chunk on a third stream and
-// leave each plane's transform in a device table (read by the tile kernel) and in a pinned mirror (read by the workers after
+//
+// Two forms, ONE plan (PipePlan), one set-up (pipe_setup), one enqueue per chunk, one guard (ab_bg_pipeline_end):
+// RESIDENT (ab_bg_pipeline_begin): the caller has every plane's transform; the set-up uploads them and every chunk is enqueued
+// before the call returns, the first one short (bg_pipe_plan.hpp: PipeChunks).
+// FED (ab_bg_pipeline_begin_fed, round 4): nothing is known about a plane on the host before its chunk has run.  The percentiles of
+// normalize_for_detection (subsample + radix select, one workgroup per plane) run per chunk on a third stream and leave each
+// plane's transform in a device table (read by the tile kernel) and in a pinned mirror (read by the workers after
 // ab_bg_pipeline_get); a chunk's tile launch waits for its percentiles by event.
-// `landed` (nullable): one event per plane that is still being written when this returns (an upload from the host in flight).
+// `landed` (nullable): one event per plane that is still being written when the call returns (an upload from the host in flight).
 // A chunk is then enqueued by a FEEDER THREAD once its planes' events have completed on the host.  (Enqueueing every chunk up
 // front behind hipStreamWaitEvent was measured first: the runtime multiplexes all streams onto four hardware queues, a wait
 // packet at the head of a queue holds back every stream that shares it, and a third of the workers' kernels ran only after the
 // LAST frame had landed -- 10 ms of registration behind a 76 ms upload instead of ~2.)
-struct FedPlan {  // everything a chunk's launches need, by value (the feeder outlives ab_bg_pipeline_begin_fed)
+struct PipePlan {  // everything a chunk's launches need, BY VALUE: a feeder thread owns its plan and outlives the begin call that made it
     ab_ctx *ctx = nullptr;
+    bool fed = false;  // a chunk's transforms come from its own percentile launches (false: from the caller, uploaded by the set-up)
     std::vector<const float *> planes;
-    std::vector<hipEvent_t> landed;
-    size_t n = 0, nchunks = 0;
-    int chunk = 1, step = 0, ntx = 0, ntiles = 0;
-    int64_t rows = 0, cols = 0, len = 0, sstep = 1, ns = 0;
+    std::vector<hipEvent_t> landed;  // empty, or one (nullable) event per plane
+    PipeChunks chunks;
+    TileGrid grid = {};
+    int64_t rows = 0, cols = 0, len = 0, sstep = 1, ns = 0;  // (sstep, ns: the fed form's subsample of a plane's len pixels)
     float *sub = nullptr;
-    const float **dplanes = nullptr;
-    ab_pixel_xf *dxf = nullptr, *hxf = nullptr;
+    const float **dplanes = nullptr;  // device: plane pointers | transforms (AB_WS_PIPE_TABLES)
+    ab_pixel_xf *dxf = nullptr, *hxf = nullptr;  // hxf, hpo: the fed form's pinned mirrors
     PercentileOut *hpo = nullptr;
     TileCand cand;  // the candidate lists of all n planes (pipeline_cand_lists; their cuts are preset to NaN)
     int enqueue(size_t c) const {
-        const size_t first = c * (size_t)chunk, cnt = std::min<size_t>((size_t)chunk, n - first);
-        PlaneList pl;
-        for (size_t i = 0; i < (size_t)kManyPlanes; ++i) pl.p[i] = planes[first + (i < cnt ? i : 0)];
-        float *csub = sub + first * (size_t)ns;
-        hipLaunchKernelGGL(subsample_many_kernel, dim3((unsigned)((ns + 255) / 256), (unsigned)cnt), dim3(256), 0, ctx->pct_stream, pl, len, sstep, csub, ns);
-        if (ns <= (int64_t)kPctPer * 1024)
-            hipLaunchKernelGGL(percentiles_many_reg_kernel, dim3((unsigned)cnt), dim3(1024), 0, ctx->pct_stream, (const float *)csub, (unsigned int)ns,
-                               hpo + first, dxf + first, hxf + first);
-        else
-            hipLaunchKernelGGL(percentiles_many_mem_kernel, dim3((unsigned)cnt), dim3(1024), 0, ctx->pct_stream, (const float *)csub, (unsigned int)ns,
-                               hpo + first, dxf + first, hxf + first);
-        AB_HIP(ctx, hipEventRecord(ctx->pct_events[c], ctx->pct_stream));
-        AB_HIP(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->pct_events[c], 0));
-        AB_TRY(launch_tile_kernels(ctx, ctx->aux_stream, 1, nullptr, rows, cols, cols, step, ntx, ntiles, (int)cnt, ab_pixel_xf(),
-                                   (TileOut *)ctx->aux_pinned + first * (size_t)ntiles, (const float *const *)(dplanes + first),
-                                   (const ab_pixel_xf *)(dxf + first), cand_at(cand, first, ntiles)));
+        const size_t begin = chunks.begin(c), cnt = chunks.count(c);
+        if (fed) {
+            PlaneList pl;
+            for (size_t i = 0; i < (size_t)kManyPlanes; ++i) pl.p[i] = planes[begin + (i < cnt ? i : 0)];
+            float *csub = sub + begin * (size_t)ns;
+            hipLaunchKernelGGL(subsample_many_kernel, dim3((unsigned)((ns + 255) / 256), (unsigned)cnt), dim3(256), 0, ctx->pct_stream, pl, len, sstep, csub, ns);
+            if (ns <= (int64_t)kPctPer * 1024)
+                hipLaunchKernelGGL(percentiles_many_reg_kernel, dim3((unsigned)cnt), dim3(1024), 0, ctx->pct_stream, (const float *)csub, (unsigned int)ns,
+                                   hpo + begin, dxf + begin, hxf + begin);
+            else
+                hipLaunchKernelGGL(percentiles_many_mem_kernel, dim3((unsigned)cnt), dim3(1024), 0, ctx->pct_stream, (const float *)csub, (unsigned int)ns,
+                                   hpo + begin, dxf + begin, hxf + begin);
+            AB_HIP(ctx, hipEventRecord(ctx->pct_events[c], ctx->pct_stream));
+            AB_HIP(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->pct_events[c], 0));
+        }
+        AB_TRY(launch_tile_kernels(ctx, ctx->aux_stream, 1, nullptr, rows, cols, cols, grid.step, grid.ntx, grid.ntiles, (int)cnt, ab_pixel_xf(),
+                                   (TileOut *)ctx->aux_pinned + begin * (size_t)grid.ntiles, (const float *const *)(dplanes + begin),
+                                   (const ab_pixel_xf *)(dxf + begin), cand_at(cand, begin, grid.ntiles)));
         AB_HIP(ctx, hipEventRecord(ctx->aux_events[c], ctx->aux_stream));
         AB_HIP(ctx, hipGetLastError());
         return AB_OK;
     }
 };
 struct ab_bg_feed_impl {
-    FedPlan plan;
+    PipePlan plan;
     std::mutex m;
     std::condition_variable cv;
     size_t enqueued = 0;  // chunks whose launches are in the streams
@@ -2399,12 +2322,12 @@ struct ab_bg_feed_impl {
     void run() {
         ab_tls_error_sink = &err;
         (void)hipSetDevice(plan.ctx->device);
-        for (size_t c = 0; c < plan.nchunks; ++c) {
+        for (size_t c = 0; c < plan.chunks.nchunks; ++c) {
             if (stop.load(std::memory_order_acquire)) return give_up();
             int r = AB_OK;
-            const size_t first = c * (size_t)plan.chunk, cnt = std::min<size_t>((size_t)plan.chunk, plan.n - first);
+            const size_t begin = plan.chunks.begin(c), cnt = plan.chunks.count(c);
             for (size_t i = 0; i < cnt && r == AB_OK; ++i)
-                if (plan.landed[first + i] && hipEventSynchronize(plan.landed[first + i]) != hipSuccess)
+                if (plan.landed[begin + i] && hipEventSynchronize(plan.landed[begin + i]) != hipSuccess)
                     r = ab_set_error(plan.ctx, AB_ERR_HIP, "waiting for an uploaded frame failed");
             ab_upload_trace("chunk landed", (long)c);
             if (stop.load(std::memory_order_acquire)) return give_up();
@@ -2423,52 +2346,51 @@ struct ab_bg_feed_impl {
     }
 };
 
-int ab_bg_pipeline_begin_fed(ab_ctx *ctx, const float *const *planes, size_t n, int64_t rows, int64_t cols, int chunk, const hipEvent_t *landed,
-                             ab_bg_pipeline *p, bool want_cand) {
-    *p = ab_bg_pipeline();
+// planes too small for tiles, no planes, no chunk, AB_TILE_LEGACY: no pipeline (the callers' frames estimate their own backgrounds)
+static bool pipe_wanted(size_t n, int64_t rows, int64_t cols, int chunk) {
     static const bool legacy = ab_dev_env("AB_TILE_LEGACY") != nullptr;
-    if (legacy || n == 0 || rows < 3 || cols < 3 || chunk < 1) return AB_OK;
-    if (chunk > kManyPlanes) chunk = kManyPlanes;
+    return !legacy && n > 0 && rows >= 3 && cols >= 3 && chunk >= 1;
+}
+
+// The set-up of both forms: the plan's geometry, the streams and events, the pinned and the device tables, the declined-tile list, the
+// candidate lists, the uploads, and what the workers read (*p, all but `on`).  xf: the planes' transforms (resident), nullptr = fed.
+// From the first upload on, commands that belong to the caller's frames are in the streams: p->started tells ab_bg_pipeline_end to
+// drain them however the batch ends, so no path here or in the begin functions drains on its own.
+static int pipe_setup(PipePlan *f, ab_ctx *ctx, const float *const *planes, size_t n, int64_t rows, int64_t cols, const PipeChunks &chunks,
+                      const ab_pixel_xf *xf, const hipEvent_t *landed, bool want_cand, ab_bg_pipeline *p) {
     AB_HIP(ctx, hipSetDevice(ctx->device));
-    FedPlan f;
-    f.ctx = ctx;
-    f.n = n;
-    f.chunk = chunk;
-    f.rows = rows;
-    f.cols = cols;
-    const int64_t m = std::min(rows, cols);
-    const int64_t tile_size = std::min<int64_t>(std::max<int64_t>(m / 8, 32), 256);  // detect_stars' choice (:100)
-    f.step = (int)std::max<int64_t>(tile_size, 16);
-    const int nty = (int)((rows + f.step - 1) / f.step);
-    f.ntx = (int)((cols + f.step - 1) / f.step);
-    f.ntiles = nty * f.ntx;
-    f.len = rows * cols;
-    f.sstep = std::max<int64_t>(f.len / 100000, 1);  // affine.rs:28-30
-    f.ns = (f.len + f.sstep - 1) / f.sstep;
+    f->ctx = ctx;
+    f->fed = xf == nullptr;
+    f->chunks = chunks;
+    f->grid = ab_tile_grid(rows, cols);
+    f->rows = rows;
+    f->cols = cols;
+    f->planes.assign(planes, planes + n);
+    if (landed) f->landed.assign(landed, landed + n);
+    const size_t ntiles = (size_t)f->grid.ntiles;
     if (!ctx->aux_stream) {
         const hipError_t stream_rc = ab_stream_create_masked(ctx, &ctx->aux_stream, AB_DEV_NAME("AB_TILE_CU_MASK"), AB_DEV_NAME("AB_TILE_PRIO"), 0);  // (outside AB_HIP: its message would carry the developer variables' names)
         AB_HIP(ctx, stream_rc);
     }
-    if (!ctx->pct_stream) AB_HIP(ctx, hipStreamCreateWithFlags(&ctx->pct_stream, hipStreamNonBlocking));
-    f.nchunks = (n + (size_t)chunk - 1) / (size_t)chunk;
-    while (ctx->aux_events.size() < f.nchunks) {
-        hipEvent_t e;
-        AB_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ctx->aux_events.push_back(e);
+    AB_TRY(ab_events_reserve(ctx, &ctx->aux_events, chunks.nchunks));
+    if (f->fed) {
+        f->len = rows * cols;
+        f->sstep = std::max<int64_t>(f->len / 100000, 1);  // affine.rs:28-30
+        f->ns = (f->len + f->sstep - 1) / f->sstep;
+        if (!ctx->pct_stream) AB_HIP(ctx, hipStreamCreateWithFlags(&ctx->pct_stream, hipStreamNonBlocking));
+        AB_TRY(ab_events_reserve(ctx, &ctx->pct_events, chunks.nchunks));
+        AB_TRY(ab_workspace(ctx, AB_WS_PIPE_SUBSAMPLE, n * (size_t)f->ns * sizeof(float), (void **)&f->sub));
     }
-    while (ctx->pct_events.size() < f.nchunks) {
-        hipEvent_t e;
-        AB_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ctx->pct_events.push_back(e);
-    }
-    // pinned: tile results | plane pointers (staging copy) | transforms (the mirror the workers read) | percentile records
+    // pinned: tile results | plane pointers (staging copy) | transforms (resident: staging copy; fed: the mirror the workers read) |
+    // fed: percentile records.  The callers' tables are locals in pageable memory, and an asynchronous copy out of those is only
+    // safe while the runtime happens to stage it synchronously: the uploads read the pinned copies.  Device: plane pointers | transforms
     const size_t ptr_bytes = (n * sizeof(const float *) + 15) & ~(size_t)15, xf_bytes = (n * sizeof(ab_pixel_xf) + 15) & ~(size_t)15;
-    const size_t tiles_bytes = (n * (size_t)f.ntiles * sizeof(TileOut) + 63) & ~(size_t)63;
-    const size_t need = tiles_bytes + ptr_bytes + xf_bytes + n * sizeof(PercentileOut);
+    const size_t tiles_bytes = (n * ntiles * sizeof(TileOut) + 63) & ~(size_t)63;
+    const size_t need = tiles_bytes + ptr_bytes + xf_bytes + (f->fed ? n * sizeof(PercentileOut) : 0);
     if (need > ctx->aux_pinned_bytes) {
-        if (ctx->aux_pinned) {
-            AB_HIP(ctx, hipStreamSynchronize(ctx->aux_stream));
-            AB_HIP(ctx, hipStreamSynchronize(ctx->pct_stream));
+        if (ctx->aux_pinned) {  // (whichever form used it last: every pipeline stream that exists is idle before the buffer goes)
+            for (hipStream_t st : {ctx->aux_stream, ctx->pct_stream})
+                if (st) AB_HIP(ctx, hipStreamSynchronize(st));
             AB_HIP(ctx, hipHostFree(ctx->aux_pinned));
             ctx->aux_pinned = nullptr;
             ctx->aux_pinned_bytes = 0;
@@ -2476,33 +2398,60 @@ int ab_bg_pipeline_begin_fed(ab_ctx *ctx, const float *const *planes, size_t n, 
         AB_HIP(ctx, hipHostMalloc(&ctx->aux_pinned, need, hipHostMallocDefault));
         ctx->aux_pinned_bytes = need;
     }
-    char *dv = nullptr;  // device: plane pointers | transforms
+    char *dv = nullptr;
     AB_TRY(ab_workspace(ctx, AB_WS_PIPE_TABLES, ptr_bytes + xf_bytes + 64, (void **)&dv));
-    AB_TRY(ab_workspace(ctx, AB_WS_PIPE_SUBSAMPLE, n * (size_t)f.ns * sizeof(float), (void **)&f.sub));
-    unsigned int *fail = nullptr;  // (sized once, here: the feeder's launches must not reallocate it)
-    AB_TRY(tile_fail_buffer(ctx, 1, (size_t)f.ntiles * (size_t)chunk, &fail));
-    f.dplanes = (const float **)dv;
-    f.dxf = (ab_pixel_xf *)(dv + ptr_bytes);
+    f->dplanes = (const float **)dv;
+    f->dxf = (ab_pixel_xf *)(dv + ptr_bytes);
+    // the declined-tile list is sized HERE, for the largest launch: a feeder's launches must not reallocate it
+    unsigned int *fail = nullptr;
+    AB_TRY(tile_fail_buffer(ctx, 1, ntiles * std::min(chunks.chunk, n), &fail));
+    if (want_cand) AB_TRY(pipeline_cand_lists(ctx, n, f->grid.ntiles, f->grid.step, &f->cand));
     char *stage = (char *)ctx->aux_pinned + tiles_bytes;
-    f.hxf = (ab_pixel_xf *)(stage + ptr_bytes);
-    f.hpo = (PercentileOut *)(stage + ptr_bytes + xf_bytes);
     memcpy(stage, planes, n * sizeof(const float *));
-    f.planes.assign(planes, planes + n);
-    if (landed) f.landed.assign(landed, landed + n);
-    AB_HIP(ctx, hipMemcpyAsync(f.dplanes, stage, n * sizeof(const float *), hipMemcpyHostToDevice, ctx->aux_stream));
-    if (want_cand) AB_TRY(pipeline_cand_lists(ctx, n, f.ntiles, f.step, &f.cand));
-    if (f.cand.ent) AB_HIP(ctx, hipMemsetAsync(f.cand.cut, 0xff, n * (size_t)f.ntiles * sizeof(float), ctx->aux_stream));  // NaN: "no list"
+    if (f->fed) {
+        f->hxf = (ab_pixel_xf *)(stage + ptr_bytes);
+        f->hpo = (PercentileOut *)(stage + ptr_bytes + xf_bytes);
+    } else {
+        memcpy(stage + ptr_bytes, xf, n * sizeof(ab_pixel_xf));
+    }
     p->tiles = ctx->aux_pinned;
     p->events = ctx->aux_events.data();
-    p->ntiles = f.ntiles;
-    p->chunk = chunk;
-    p->n = n;
-    p->xf_host = f.hxf;
-    p->cand_ent = f.cand.ent;
-    p->cand_cnt = f.cand.cnt;
-    p->cand_cut = f.cand.cut;
-    p->cand_step = f.cand.ent ? f.step : 0;
-    if (landed) {
+    p->ntiles = f->grid.ntiles;
+    p->chunks = chunks;
+    p->xf_host = f->hxf;
+    p->cand_ent = f->cand.ent;
+    p->cand_cnt = f->cand.cnt;
+    p->cand_cut = f->cand.cut;
+    p->cand_step = f->cand.ent ? f->grid.step : 0;
+    p->started = true;
+    AB_HIP(ctx, hipMemcpyAsync(f->dplanes, stage, n * sizeof(const float *), hipMemcpyHostToDevice, ctx->aux_stream));
+    if (!f->fed) AB_HIP(ctx, hipMemcpyAsync(f->dxf, stage + ptr_bytes, n * sizeof(ab_pixel_xf), hipMemcpyHostToDevice, ctx->aux_stream));
+    if (f->cand.ent) AB_HIP(ctx, hipMemsetAsync(f->cand.cut, 0xff, n * ntiles * sizeof(float), ctx->aux_stream));  // NaN: "no list" until a tile says otherwise
+    return AB_OK;
+}
+
+int ab_bg_pipeline_begin(ab_ctx *ctx, const float *const *planes, size_t n, int64_t rows, int64_t cols, const ab_pixel_xf *xf, int chunk,
+                         ab_bg_pipeline *p, bool want_cand) {
+    *p = ab_bg_pipeline();
+    if (!pipe_wanted(n, rows, cols, chunk)) return AB_OK;
+    // the first launch holds the reference and the first group's targets only (AB_TILE_FIRST, default 5; 0 = `chunk` like the rest):
+    // nothing else can run until a group's tiles are done, and eight frames' tiles are ~300 us of an otherwise idle chip
+    static const int first_env = ab_dev_env("AB_TILE_FIRST") ? atoi(ab_dev_env("AB_TILE_FIRST")) : 5;
+    PipePlan f;
+    AB_TRY(pipe_setup(&f, ctx, planes, n, rows, cols, ab_pipe_chunks(n, chunk, first_env), xf, nullptr, want_cand, p));
+    for (size_t c = 0; c < f.chunks.nchunks; ++c) AB_TRY(f.enqueue(c));
+    p->on = true;
+    return AB_OK;
+}
+
+int ab_bg_pipeline_begin_fed(ab_ctx *ctx, const float *const *planes, size_t n, int64_t rows, int64_t cols, int chunk, const hipEvent_t *landed,
+                             ab_bg_pipeline *p, bool want_cand) {
+    *p = ab_bg_pipeline();
+    if (!pipe_wanted(n, rows, cols, chunk)) return AB_OK;
+    if (chunk > kManyPlanes) chunk = kManyPlanes;  // (a chunk's percentile launch takes one PlaneList)
+    PipePlan f;
+    AB_TRY(pipe_setup(&f, ctx, planes, n, rows, cols, ab_pipe_chunks(n, chunk, 0), nullptr, landed, want_cand, p));
+    if (landed) {  // the feeder takes the plan with it
         ab_bg_feed_impl *feed = new ab_bg_feed_impl();
         feed->plan = std::move(f);
         p->feed = feed;
@@ -2510,33 +2459,30 @@ int ab_bg_pipeline_begin_fed(ab_ctx *ctx, const float *const *planes, size_t n, 
         feed->th = std::thread([feed] { feed->run(); });
         return AB_OK;
     }
-    // frames that are complete already: every chunk enqueued here.  From the first enqueue on, a failure drains both streams
-    // before it returns: the launches read the caller's frames
-    for (size_t c = 0; c < f.nchunks; ++c) {
-        const int rc = f.enqueue(c);
-        if (rc != AB_OK) {
-            (void)hipStreamSynchronize(ctx->pct_stream);
-            (void)hipStreamSynchronize(ctx->aux_stream);
-            return rc;
-        }
-    }
+    for (size_t c = 0; c < f.chunks.nchunks; ++c) AB_TRY(f.enqueue(c));  // frames that are complete already: every chunk enqueued here
     p->on = true;
     return AB_OK;
 }
 
-// joins the feeder (if any): call before the pipeline's streams are drained and before the planes go away
-void ab_bg_pipeline_end(ab_bg_pipeline *p) {
-    if (p && p->feed) {
+// The one way out of a batch, whatever path leaves it (ab_bg_pipeline_guard): the feeder is stopped and joined, then the pipeline's
+// streams are drained -- their launches read the caller's frames -- if the pipeline ran or a begin failed part-way.
+void ab_bg_pipeline_end(ab_ctx *ctx, ab_bg_pipeline *p) {
+    if (!p) return;
+    if (p->feed) {
         p->feed->stop.store(true, std::memory_order_release);  // (a finished feeder never looks; an abandoned batch stops at the next chunk)
         if (p->feed->th.joinable()) p->feed->th.join();
         delete p->feed;
-        p->feed = nullptr;
     }
+    if (p->started) {
+        if (p->xf_host && ctx->pct_stream) (void)hipStreamSynchronize(ctx->pct_stream);
+        if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
+    }
+    *p = ab_bg_pipeline();
 }
 
 int ab_bg_pipeline_get(ab_ctx *ctx, const ab_bg_pipeline *p, size_t i, double *bg) {
-    AB_CHECK(ctx, p && p->on && i < p->n, "background pipeline: no such plane");
-    const size_t c = p->first > 0 ? (i < (size_t)p->first ? 0 : 1 + (i - (size_t)p->first) / (size_t)p->chunk) : i / (size_t)p->chunk;
+    AB_CHECK(ctx, p && p->on && i < p->chunks.n, "background pipeline: no such plane");
+    const size_t c = p->chunks.chunk_of(i);
     if (p->feed) {  // the chunk's launches are in the streams only once its planes have landed
         std::unique_lock<std::mutex> g(p->feed->m);
         p->feed->cv.wait(g, [&] { return p->feed->enqueued > c || p->feed->rc != AB_OK; });
@@ -2552,25 +2498,7 @@ int ab_estimate_background_device(ab_ctx *ctx, const float *img, int64_t rows, i
                                   double *out_median, double *out_sigma, ab_pixel_xf xf = ab_pixel_xf()) {
     std::vector<TileOut> h;
     AB_TRY(tile_stats_host(ctx, img, rows, cols, ld, tile_size, xf, &h, nullptr));
-    std::vector<double> med, sig;
-    uint64_t declined = 0;
-    for (const auto &t : h) declined += t.pad != 0;
-    ab_count_fallback(ctx, AB_FB_TILES_DECLINED, declined);
-    for (const auto &t : h)
-        if (t.valid) {
-            med.push_back(t.median);
-            sig.push_back(t.sigma);
-        }
-    if (med.empty()) {  // :70-72
-        *out_median = 0.0;
-        *out_sigma = 1.0;
-        return AB_OK;
-    }
-    auto lt = [](double a, double b) { return f64_cmp(a, b) < 0; };
-    std::sort(med.begin(), med.end(), lt);
-    std::sort(sig.begin(), sig.end(), lt);
-    *out_median = med[med.size() / 2];
-    *out_sigma = std::fmax(sig[sig.size() / 2], 1e-10);
+    background_from_tiles(h.data(), (int)h.size(), out_median, out_sigma, ctx);
     return AB_OK;
 }
 
@@ -2930,8 +2858,7 @@ int ab_detect_stars_device(ab_ctx *ctx, const float *img, int64_t rows, int64_t 
         bg[0][1] = bg_known[1];
     } else {
         if (normalize_first) AB_TRY(ab_normalize_params_device(ctx, img, rows * cols, &xf));
-        const int64_t tile_size = std::min<int64_t>(std::max<int64_t>(std::min(rows, cols) / 8, 32), 256);  // :100
-        AB_TRY(ab_estimate_background_device(ctx, img, rows, cols, cols, tile_size, &bg[0][0], &bg[0][1], xf));
+        AB_TRY(ab_estimate_background_device(ctx, img, rows, cols, cols, ab_tile_grid(rows, cols).tile_size, &bg[0][0], &bg[0][1], xf));  // :100
         trace.mark("background");
     }
     AB_TRY(detect_group(ctx, &img, 1, rows, cols, sigma_threshold, &xf, bg, max_keep, stars, nullptr, /*full=*/true));

@@ -160,11 +160,7 @@ int ab_stack_sigma_clip_sharded(ab_ctx *ctx, ab_comm *comm, const ab_plane *loca
         psum = (double *)ws;
         pcnt = (uint32_t *)(ws + sum_bytes);
         if (!ctx->comm_stream) AB_HIP(ctx, hipStreamCreateWithFlags(&ctx->comm_stream, hipStreamNonBlocking));
-        while (ctx->shard_ev.size() < (size_t)(2 * kShardChunks)) {
-            hipEvent_t e;
-            AB_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            ctx->shard_ev.push_back(e);
-        }
+        AB_TRY(ab_events_reserve(ctx, &ctx->shard_ev, (size_t)(2 * kShardChunks)));
         while (ctx->shard_tm.size() < (size_t)(2 + 2 * kShardChunks)) {
             hipEvent_t e;
             AB_HIP(ctx, hipEventCreate(&e));
