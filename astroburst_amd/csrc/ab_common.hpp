@@ -35,7 +35,7 @@ enum {
     AB_WS_STACK_WIDE,         // plane pointer / stride tables of a > 64-frame stack
     AB_WS_BATCH_WIDE,         // tables of a > 64-frame batch stack
     AB_WS_STACK_INF,          // one plane of +inf: stands in for the frames a stack is short of a power of two
-    AB_WS_STACK_PAIR_LISTS,   // the pixels a two-lane fast pass hands to the oracle-arithmetic kernel (stack_pair.hip, stack_duo.hip)
+    AB_WS_STACK_PAIR_LISTS,   // the pixels a two-lane fast pass hands to the oracle-arithmetic kernel (stack_pair.hip, stack_lanes.hip)
     AB_WS_BATCH_PAD,          // one plane of FLT_MAX: the same for the batch stack (where +inf is a sample like any other)
     AB_WS_STATS,              // state block, 65 536-bin histograms and partials of the statistics chain (stats.hip)
     AB_WS_SHARD,              // (sum f64, count u32) partial planes of the frame-sharded stack (sharded.hip)
@@ -496,10 +496,10 @@ int ab_stack_wide_device(ab_ctx *ctx, const StackPlan &plan, const float *const 
 // stack_deep.hip: more than ctx->stack_deep_from frames (any count): one workgroup per pixel, samples in global scratch
 int ab_stack_deep_device(ab_ctx *ctx, const float *const *dplanes, const int64_t *ld, size_t n, int64_t rows, int64_t cols,
                          const ab_stack_config *cfg, float *out_dev, double *out_sum_dev, uint32_t *out_cnt_dev, bool median_only);
-// stack_pair.hip (+ stack_duo.hip, stack_quad.hip): 129 .. 1024 contiguous frames, two to eight lanes per pixel; dplanes is a HOST array
+// stack_pair.hip (+ stack_lanes.hip): 129 .. 1024 contiguous frames, two to eight lanes per pixel; dplanes is a HOST array
 int ab_stack_pair_device(ab_ctx *ctx, const StackPlan &plan, const float *const *dplanes, size_t n, int64_t rows, int64_t cols,
                          const ab_stack_config *cfg, float *out_dev, bool median_only);
-// stack_wide.hip: the pixels a 513 .. 1024-frame fast pass (stack_quad.hip, eight lanes per pixel) handed over -- 2048 lists of `cap`
+// stack_wide.hip: the pixels a 513 .. 1024-frame fast pass (stack_lanes.hip, eight lanes per pixel) handed over -- 2048 lists of `cap`
 // pixel indices each -- one wave per pixel, the oracle's arithmetic; leaves the lists empty.  table_dev: DEVICE array of >= n plane pointers
 int ab_stack_wide_list_device(ab_ctx *ctx, const float *const *table_dev, size_t n, int64_t rows, int64_t cols, const ab_stack_config *cfg, float *out_dev,
                               bool median_only, unsigned int *list_count, const int *list, unsigned int cap);

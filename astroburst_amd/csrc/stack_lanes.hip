@@ -1,28 +1,42 @@
-// The FAST pass of a 257 .. 512-frame kappa-sigma stack on gfx950: FOUR lanes per pixel, 128 samples each, two waves per SIMD.
+// The FAST pass of a 129 .. 1024-frame kappa-sigma stack (and median combine) on gfx950: L = 2, 4 or 8 lanes per pixel for 129 .. 256,
+// 257 .. 512 and 513 .. 1024 frames, 128 samples per lane, two waves per SIMD, the default engine's running sums.
 //
-// sigma_clip_combine (core/stacking/combine.rs:14-92).  stack_duo.hip's engine with the pair widened to a quad: with 256 samples per
-// lane (two lanes per pixel) the samples fill the unified register file, ONE wave fits a SIMD, and a lone wave issues an instruction
-// every 8 .. 9 cycles -- 36 ms for 512 x 4096^2.  Lanes 4k .. 4k + 3 share pixel k of the wave's 16:
+// sigma_clip_combine (core/stacking/combine.rs:14-92) for the frame counts of deep light stacks and master calibration stacks.
+// Why 128 samples per lane: 129 .. 256 samples in ONE lane's registers (VGPRs + AGPRs) fill the unified register file, one wave fits
+// a SIMD, and a lone wave issues an instruction every 8 .. 9 cycles with nothing to hide its loads behind -- 10.6 ms for 256 x 4096^2,
+// two lanes of 128 take 7.1.  Two lanes of H = 256 for 257 .. 512 frames were one wave per SIMD again: 36 ms for 512 x 4096^2 against 15
+// on four lanes of 128, so H = 256 is retired.  stack_pair.hip's oracle arithmetic over all pixels (two f64 chains of 512 additions per
+// iteration) took 58 ms there, and the wave-per-pixel kernel (stack_wide.hip: a bitonic sort through 64-lane shuffles) 43.7 ms for
+// 513 x 2048^2 where eight lanes take 9.7: both now see only the pixels this pass hands over.
+// Lanes L k .. L k + L - 1 share pixel k of the wave's 64 / L; q = the lane's place in its group:
 //   * gather: lane q takes frames q R .. (q + 1) R - 1 (R = the frame-count class, a multiple of 16; wires R .. 127 are +inf pads
-//     known at compile time, frames n .. 4R - 1 read a plane of +inf); every lane loads ITS plane's pointer from the table (a vector
-//     load of 8 bytes) and then its sample: two memory instructions and a 64-bit add per sample, nothing fetched twice;
-//   * sort: SortNet<128>::sort_fused_n<R> per lane; level 1 merges lanes (0, 1) and (2, 3) as stack_duo.hip does (cross step
-//     against the partner's reversed registers + an in-lane bitonic merge); level 2 merges the two sorted runs of 256: a cross
-//     step against lane q ^ 3's reversed registers, one half-cleaner stage between lanes q and q ^ 1, the in-lane merge again.
-//     An exchange keeps v_med3(x, partner, -inf / +inf): the minimum or the maximum by a per-lane constant, one instruction.
-//     Lane q then holds sorted ranks 128 q .. 128 q + 127;
-//   * median / MAD at a compile-time position (n / 2 is one number per launch): lanes 0 and 1 hold the windows' low ends V[p], the
-//     high ends V[p + M] come from lane q + 1 or q + 2 through DPP at a constant register index;
-//   * clipping, running moments, the list of pixels handed to stack_pair.hip's oracle-arithmetic kernel: as in stack_duo.hip, the
-//     low end in lane 0's first registers, the high end in the lane that holds rank n - 1.
-// Same contract as the <= 64-frame fast engine: 1e-5 relative, at most 1e-4 of the pixels may differ from the oracle at all.
-//
-// 513 .. 1024 frames: the same kernel with EIGHT lanes per pixel (L = 8; lanes 8k .. 8k + 7, pixel k of the wave's 8): a third
-// merge level (cross step against lane 7 - q's reversed registers = DPP row_half_mirror, half-cleaner stages between lanes q ^ 2
-// and q ^ 1, the in-lane merge), sums over three DPP steps, a window's far end `row_shl` 2 .. 5 lanes on, the median's lane through
-// ds_bpermute.  The wave-per-pixel kernel (stack_wide.hip: a bitonic sort through 64-lane shuffles) took 43.7 ms for 513 x 2048^2
-// where 512 frames take 5: its pixels now are only the ones this pass hands over.
+//     known at compile time -- no loads, and SortNet<128>::sort_fused_n<R> drops their operations; frames n .. L R - 1 read a plane
+//     of +inf).  L = 4, 8: every lane loads ITS plane's pointer from the table (a vector load of 8 bytes) and then its sample: two
+//     memory instructions and a 64-bit add per sample, nothing fetched twice.  L = 2: both lanes fetch frames f and R + f through
+//     the wave-uniform scalar table and keep their own -- the one piece written per lane count (measured: see the gather);
+//   * sort: R per lane, then log2 L merge levels.  Level 1 merges lanes (0, 1), (2, 3), ..: a cross step against the partner's
+//     reversed registers + an in-lane bitonic merge (stack_pair.hpp).  Level 2 (L >= 4) merges the two sorted runs of 256: a cross
+//     step against lane q ^ 3's reversed registers, one half-cleaner stage between lanes q and q ^ 1, the in-lane merge.  Level 3
+//     (L = 8): a cross step against lane 7 - q's reversed registers (DPP row_half_mirror), half-cleaner stages between lanes q ^ 2 and
+//     q ^ 1, the in-lane merge.  An exchange keeps v_med3(x, partner, -inf / +inf): the minimum or the maximum by a per-lane constant,
+//     one instruction.  Lane q then holds sorted ranks 128 q .. 128 q + 127;
+//   * median and MAD at a compile-time position: every pixel of this kernel holds all n samples finite (the others are handed over,
+//     see below), so M = n / 2 is one number per launch and a binary dispatch reaches the instance written for it -- the window
+//     formula MAD = min_p max(med - V[p], V[p + M] - med) with constant register indices: the lanes up to M >> 7 hold the windows'
+//     low ends, a high end comes from the same lane or from 1 .. 5 lanes on through DPP row_shl; sums over log2 L DPP steps, the
+//     median's lane through a quad_perm (L = 2, 4) or ds_bpermute (L = 8);
+//   * clipping: the default engine of stack_sigma_clip.hip (clip_fast) in multi-lane form.  Survivors are a rank interval; the low
+//     end lives in lane 0's first registers, the high end in the last real registers of the lane that holds rank n - 1 (a launch-
+//     uniform position) and, when that lane holds at most eight samples, the top of the lane below; each walk looks at eight samples;
+//     iteration >= 1 gets mean and sigma from running moments about the median, E = sum (x - med), Q = sum (x - med)^2 in f64 -- one
+//     pass over the lane's registers, the group's parts added through DPP -- minus what the walks shaved.  Same contract as the
+//     <= 64-frame fast engine: 1e-5 relative, at most 1e-4 of the pixels may differ from the oracle at all (measured: none);
+//   * whatever does not fit -- a pixel with a non-finite sample, more than eight rejected samples at one end in total, nothing
+//     surviving -- is appended to one of 2048 lists and redone with the oracle's arithmetic, bit for bit: stack_pair.hip's kernel in
+//     LIST mode up to 512 frames, stack_wide.hip's beyond.  AB_FB_STACK_GENERAL_PIXELS counts them under AB_TRACE.
+// ~5 700 instructions per wave of 32 pixels at L = 2.
 #include "stack_pair.hpp"
+#include "stack_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -33,90 +47,62 @@ namespace {
 
 constexpr int HQ = 128;  // samples per lane
 
-template <int CTRL>
-__device__ __forceinline__ float dppf(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
-}
-template <int CTRL>
-__device__ __forceinline__ int dppi(int x) {
-    return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xf, 0xf, false);
-}
-constexpr int kSwap1 = 0xB1;  // quad_perm [1,0,3,2]: lane q ^ 1
-constexpr int kSwap2 = 0x4E;  // quad_perm [2,3,0,1]: lane q ^ 2
-constexpr int kRev = 0x1B;    // quad_perm [3,2,1,0]: lane q ^ 3
-constexpr int kHalfMirror = 0x141;  // row_half_mirror: lane 7 - i of every 8
-// sums / ors / minima over the L = 4 or 8 lanes of a pixel: after the steps inside a quad every lane of it holds the quad's value,
-// and the half mirror pairs a lane with one of the other quad
+// sums / ors / minima over the L lanes of a pixel: after the steps inside a quad every lane of it holds the quad's value, and the
+// half mirror pairs a lane with one of the other quad
 template <int L>
 __device__ __forceinline__ int grp_sum(int x) {
     x += dppi<kSwap1>(x);
-    x += dppi<kSwap2>(x);
+    if constexpr (L >= 4) x += dppi<kSwap2>(x);
     if constexpr (L == 8) x += dppi<kHalfMirror>(x);
     return x;
 }
 template <int L>
 __device__ __forceinline__ int grp_or(int x) {
     x |= dppi<kSwap1>(x);
-    x |= dppi<kSwap2>(x);
+    if constexpr (L >= 4) x |= dppi<kSwap2>(x);
     if constexpr (L == 8) x |= dppi<kHalfMirror>(x);
     return x;
-}
-template <int CTRL>
-__device__ __forceinline__ double dppd(double x) {
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-    const unsigned int lo = (unsigned int)dppi<CTRL>((int)(unsigned int)u), hi = (unsigned int)dppi<CTRL>((int)(unsigned int)(u >> 32));
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
 // (every step adds the same two numbers in both lanes of a pair: all lanes of the group end with the same bits)
 template <int L>
 __device__ __forceinline__ double grp_sum(double x) {
     x += dppd<kSwap1>(x);
-    x += dppd<kSwap2>(x);
+    if constexpr (L >= 4) x += dppd<kSwap2>(x);
     if constexpr (L == 8) x += dppd<kHalfMirror>(x);
     return x;
 }
 template <int L>
 __device__ __forceinline__ float grp_min(float x) {
     x = fminf(x, dppf<kSwap1>(x));
-    x = fminf(x, dppf<kSwap2>(x));
+    if constexpr (L >= 4) x = fminf(x, dppf<kSwap2>(x));
     if constexpr (L == 8) x = fminf(x, dppf<kHalfMirror>(x));
     return x;
 }
 // lane k's register for every lane of the group
 template <int L, int KLANE>
 __device__ __forceinline__ float grp_bcast(float x, int lane) {
-    if constexpr (L == 4) {
+    if constexpr (L == 2) {
+        return dppf<KLANE * 0x05 + (2 + KLANE) * 0x50>(x);  // quad_perm [k,k,2+k,2+k]
+    } else if constexpr (L == 4) {
         return dppf<KLANE * 0x55>(x);  // quad_perm [k,k,k,k]
     } else {
         return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(((lane & ~7) | KLANE) << 2, __builtin_bit_cast(int, x)));
     }
 }
-
-// v[i] against the partner lane's v[127 - i]: a lane keeps the smaller (sel = -inf) or the larger (sel = +inf) of each pair
-template <int CTRL>
-__device__ __forceinline__ void cross_rev(float (&v)[HQ], float sel) {
-#pragma unroll
-    for (int i = 0; i < HQ / 2; ++i) {
-        const float t1 = dppf<CTRL>(v[HQ - 1 - i]), t2 = dppf<CTRL>(v[i]);
-        const float a = ab_v_med3(v[i], t1, sel), b = ab_v_med3(v[HQ - 1 - i], t2, sel);
-        v[i] = a;
-        v[HQ - 1 - i] = b;
-    }
-}
-// v[i] against the partner lane's v[i]: the half-cleaner stage of distance 128 of a bitonic merge over two lanes
-template <int CTRL>
-__device__ __forceinline__ void cross_same(float (&v)[HQ], float sel) {
-#pragma unroll
-    for (int i = 0; i < HQ; ++i) {
-        const float t = dppf<CTRL>(v[i]);
-        v[i] = ab_v_med3(v[i], t, sel);
-    }
+// the register of the lane SHL places on (DPP row_shl); 0: this lane's own
+template <int SHL>
+__device__ __forceinline__ float lane_on(float x) {
+    if constexpr (SHL == 0)
+        return x;
+    else
+        return dppf<0x100 + SHL>(x);
 }
 
 // median (combine.rs:38-40) and MAD (combine.rs:42-46) of a group of L lanes that holds n finite samples, n / 2 = M: rank r in lane
-// r >> 7, register r & 127.  MAD = min over p = 0 .. n - 1 - M of max(med - V[p], V[p + M] - med) (stack_duo.hip).  The window p
-// belongs to the lane that holds V[p] (lanes below M >> 7: every register; lane M >> 7: registers below M & 127); its high end is
-// register (i + M) & 127 of the lane (M >> 7) or (M >> 7) + 1 places on: DPP row_shl.
+// r >> 7, register r & 127.  MAD = the (M + 1)-th smallest deviation = min over the windows [p, p + M] of sorted samples that contain
+// the median of the larger end deviation, max(med - V[p], V[p + M] - med): p = 0 .. n - 1 - M (stack_sigma_clip.hip: med_mad_at).  The
+// window p belongs to the lane that holds V[p] (lanes below M >> 7: every register; lane M >> 7: registers below M & 127); its high end
+// is register (i + M) & 127 of the lane (M >> 7) or (M >> 7) + 1 places on.
 template <int L, int M>
 __device__ __forceinline__ void med_mad_at(const float (&v)[HQ], int q, int lane, bool n_is_odd, float &med_out, float &mad_out) {
     static_assert(M >= 32 * L && M <= 64 * L, "a group of L lanes holds 64 L + 1 .. 128 L samples");
@@ -127,7 +113,7 @@ __device__ __forceinline__ void med_mad_at(const float (&v)[HQ], int q, int lane
 #pragma unroll
     for (int i = 0; i < HQ; ++i) {
         const int s2 = (i + Mr) & 127;
-        const float hi_end = ((i + Mr) >> 7) ? dppf<0x100 + Mq + 1>(v[s2]) : dppf<0x100 + Mq>(v[s2]);  // row_shl: lane q + Mq (+ 1)
+        const float hi_end = ((i + Mr) >> 7) ? lane_on<Mq + 1>(v[s2]) : lane_on<Mq>(v[s2]);
         const float t = ab_v_max(med - v[i], hi_end - med);
         if (i < Mr)
             best_lo = ab_v_min(best_lo, t);
@@ -170,9 +156,11 @@ __device__ __forceinline__ float median_dispatch(const float (&v)[HQ], int lane,
     }
 }
 
-// One clipping pass over the two ends of the quad's rank interval (combine.rs:65-82; stack_duo.hip: clip_walk).  [la, lb]: this
-// lane's part of it in its own register indices.  The low end is lane 0's registers 0 .. 7; the high end lane qt's last real
-// registers (chunks ct and ct - 1; qt, ct launch-uniform) and, when that lane holds at most eight samples, lane qt - 1's top.
+// One clipping pass over the two ends of the group's rank interval (combine.rs:65-82).  [la, lb]: this lane's part of it in its own
+// register indices.  The low end is lane 0's registers 0 .. 7; the high end lane qt's last real registers (chunks ct and ct - 1; qt, ct
+// launch-uniform) and, when that lane holds at most eight samples, lane qt - 1's top registers as well.  A sorted end fails the test
+// as a prefix, so the counts of the lanes simply add.  `decided`: both ends saw a surviving sample within their eight -- otherwise
+// the pixel is not this kernel's.  UPDATE: the shaved samples are folded into e_rem / q_rem (moments about c0).
 template <int L, bool UPDATE>
 __device__ __forceinline__ void clip_walk(const float (&v)[HQ], int q, bool go, int la, int lb, int qt, int ct, float center, float lo, float hi, float c0,
                                           double c0d, int &cl_own, int &ch_own, bool &decided, double &e_rem, double &q_rem) {
@@ -222,7 +210,7 @@ __device__ __forceinline__ void clip_walk(const float (&v)[HQ], int q, bool go, 
         }
         fold(r, 4 * c);
     };
-    // (whether some pixel of the wave still looks for its first surviving sample at the high end: the quad's lanes share the flag)
+    // (whether some pixel of the wave still looks for its first surviving sample at the high end: the group's lanes share the flag)
     auto open_hi = [&]() { return __any(go && grp_or<L>(found_hi ? 1 : 0) == 0); };
 #pragma unroll
     for (int c = NC - 1; c >= 0; --c) {
@@ -243,15 +231,17 @@ __device__ __forceinline__ void clip_walk(const float (&v)[HQ], int q, bool go, 
 }
 
 template <int L, int R, bool MEDIAN = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void stack_quad_fast_kernel(const PairArgs a) {
-    static_assert((L == 4 || L == 8) && R <= HQ && R > HQ / 2 && R % 8 == 0, "frame-count class");
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void stack_lanes_fast_kernel(const PairArgs a) {
+    static_assert((L == 2 || L == 4 || L == 8) && R <= HQ && R > HQ / 2 && R % 8 == 0, "frame-count class");
     constexpr int PX = 64 / L;  // pixels per wave
     const int lane = threadIdx.x;
     const int q = lane & (L - 1);
     const int pix = lane / L;
-    // A wave reads 16 (8) pixels = 64 (32) bytes of every plane: a HALF (quarter) of a cache line, the rest being the next waves'.
-    // Workgroup ids go round the eight XCDs (id % 8), so consecutive ids would fetch every line into several XCDs' L2; ids id, id + 8,
-    // ... -- same XCD, dispatched together -- take neighbouring pixel groups instead (the grid is a multiple of 8).
+    // A wave reads 32 / 16 / 8 pixels = 128 / 64 / 32 bytes of every plane: with four or eight lanes per pixel a HALF or a quarter of a
+    // cache line, the rest being the next waves'.  Workgroup ids go round the eight XCDs (id % 8), so consecutive ids would fetch every
+    // line into several XCDs' L2; ids id, id + 8, ... -- same XCD, dispatched together -- take neighbouring pixel groups instead (the
+    // grid is a multiple of 8: stack_plan.hpp, ab_stack_lanes_grid).  A two-lane wave reads whole lines and needs no such order; it
+    // takes the same one, which costs it nothing (LABNOTES 36).
     const unsigned int per_xcd = gridDim.x >> 3;
     const unsigned int group = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
     int64_t g = (int64_t)group * PX + pix;
@@ -265,10 +255,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     const float *const *tab = a.p + q * R;
 #pragma unroll
     for (int f = 0; f < HQ; ++f) {
-        if (f < R)
-            v[f] = *(const float *)((const char *)tab[f] + boff);
-        else
+        if (f >= R) {
             v[f] = __builtin_inff();  // a pad of the class: never loaded, never moved by the network
+        } else if constexpr (L == 2) {
+            // BOTH lanes of a pair fetch their pixel from frame f and from frame R + f -- wave-uniform planes: the pointers come through
+            // scalar loads, every sample load is a scalar base + one shared 32-bit byte offset and reads one 128-byte line -- and each
+            // keeps its half's sample.  With a pointer load per lane in front of every sample load the median combine, which has
+            // little else to hide the two dependent round trips behind, took 4.42 ms against 3.86 for 200 x 4096^2 (LABNOTES 36)
+            const float xe = *(const float *)((const char *)a.p[f] + boff);
+            const float xo = *(const float *)((const char *)a.p[f + R] + boff);
+            v[f] = q ? xo : xe;
+        } else {
+            v[f] = *(const float *)((const char *)tab[f] + boff);
+        }
     }
     float nf = 0.0f;  // fma(x, 0, nf) stays 0 for finite x and turns NaN for inf / NaN
 #pragma unroll
@@ -297,11 +296,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     cross_rev<kSwap1>(v, sel1);  // lanes (0, 1), (2, 3), ...: runs of 256
     bitonic_merge<HQ>(v);
     dpp_fence<HQ>(v);
-    cross_rev<kRev>(v, sel2);  // quads: runs of 512
-    dpp_fence<HQ>(v);
-    cross_same<kSwap1>(v, sel1);
-    bitonic_merge<HQ>(v);
-    dpp_fence<HQ>(v);
+    if constexpr (L >= 4) {  // quads: runs of 512
+        cross_rev<kRev>(v, sel2);
+        dpp_fence<HQ>(v);
+        cross_same<kSwap1>(v, sel1);
+        bitonic_merge<HQ>(v);
+        dpp_fence<HQ>(v);
+    }
     if constexpr (L == 8) {  // the two quads: one run of 1024
         const float sel4 = (q & 4) ? inf : -inf;
         cross_rev<kHalfMirror>(v, sel4);
@@ -359,7 +360,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         apply(go, cl_own, ch_own, decided);
     }
 
-    // ---- one pass over the survivors: E = sum e_i, Q = sum e_i^2 with e_i = x_i - med (f64), the quad's parts added ----
+    // ---- one pass over the survivors: E = sum e_i, Q = sum e_i^2 with e_i = x_i - med (f64), the group's parts added ----
     double E, Q;
     {
         double E1 = 0.0, Q1 = 0.0;
@@ -413,29 +414,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 
 }  // namespace
 
-// the fast pass of a 257 .. 512-frame (L = 4 lanes per pixel) or 513 .. 1024-frame (L = 8) stack; the arguments' table holds L R pointers
-int ab_stack_quad_launch(ab_ctx *ctx, int L, int R, const PairArgs &args) {
-    const int64_t px = 64 / L;
-    const dim3 grid((unsigned)(((args.total + px - 1) / px + 7) / 8 * 8)), block(64);  // (a multiple of 8: see the kernel's pixel-group order)
-#define AB_QUAD_CASE(LV, RV)                                                                              \
-    if (L == LV && R == RV) {                                                                             \
-        if (args.median_only)                                                                             \
-            hipLaunchKernelGGL((stack_quad_fast_kernel<LV, RV, true>), grid, block, 0, ctx->stream, args); \
-        else                                                                                              \
-            hipLaunchKernelGGL((stack_quad_fast_kernel<LV, RV>), grid, block, 0, ctx->stream, args);       \
-        AB_HIP(ctx, hipGetLastError());                                                                   \
-        return AB_OK;                                                                                     \
+int ab_stack_lanes_launch(ab_ctx *ctx, int L, int R, const PairArgs &args) {
+    const dim3 grid((unsigned)ab_stack_lanes_grid(L, args.total).waves), block(64);
+#define AB_LANES_CASE(LV, RV)                                                                              \
+    if (L == LV && R == RV) {                                                                              \
+        if (args.median_only)                                                                              \
+            hipLaunchKernelGGL((stack_lanes_fast_kernel<LV, RV, true>), grid, block, 0, ctx->stream, args); \
+        else                                                                                               \
+            hipLaunchKernelGGL((stack_lanes_fast_kernel<LV, RV>), grid, block, 0, ctx->stream, args);       \
+        AB_HIP(ctx, hipGetLastError());                                                                    \
+        return AB_OK;                                                                                      \
     }
-#ifndef AB_QUAD_ONE_CLASS  // (tests/test_abi_cpu.py walks the listing of ONE instance of each lane count)
-    AB_QUAD_CASE(4, 80)
-    AB_QUAD_CASE(4, 96)
-    AB_QUAD_CASE(4, 128)
-    AB_QUAD_CASE(8, 80)
-    AB_QUAD_CASE(8, 96)
-    AB_QUAD_CASE(8, 128)
+#define AB_LANES_CLASS(RV) AB_LANES_CASE(2, RV) AB_LANES_CASE(4, RV) AB_LANES_CASE(8, RV)
+#ifndef AB_LANES_ONE_CLASS  // (tests/test_abi_cpu.py walks the listing of ONE class of each lane count: the others are the same code at other constants)
+    AB_LANES_CLASS(80)
+    AB_LANES_CLASS(96)
+    AB_LANES_CLASS(128)
 #endif
-    AB_QUAD_CASE(4, 112)
-    AB_QUAD_CASE(8, 112)
-#undef AB_QUAD_CASE
+    AB_LANES_CLASS(112)
+#undef AB_LANES_CLASS
+#undef AB_LANES_CASE
     return ab_set_error(ctx, AB_ERR_INVALID, "internal: no %d-lane kernel for class %d", L, R);
 }

@@ -279,7 +279,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(H == 128 ? 2
     const int pix = threadIdx.x >> 1;
     int r = 0;
     if (a.walk_lists) {
-        // LIST mode: the pixels stack_duo.hip's fast pass handed over, kListWaves one-wave workgroups per list
+        // LIST mode: the pixels stack_lanes.hip's fast pass handed over, kListWaves one-wave workgroups per list
         const unsigned int slot = blockIdx.x / kListWaves, sub = blockIdx.x % kListWaves;
         const unsigned int cnt = a.list_count[slot];
         const int *list = a.list + (size_t)slot * a.list_cap;
@@ -321,12 +321,12 @@ void launch_pair_kernel(ab_ctx *ctx, int H, bool median_only, dim3 grid, const P
 }  // namespace
 
 // dplanes: HOST array of n device pointers (128 < n <= 1024), contiguous planes of rows x cols; counters already cleared by the caller.
-// plan (stack_plan.hpp): kEnginePair -- this file's kernel over all pixels (AB_STACK_EXACT=1); kEngineDuo / kEngineQuad -- a fast multi-lane
+// plan (stack_plan.hpp): kEnginePair -- this file's kernel over all pixels (AB_STACK_EXACT=1); kEngineLanes -- stack_lanes.hip's fast
 // pass, then the oracle's arithmetic over the pixels it handed over (this file's kernel in list mode, stack_wide.hip's beyond 512 frames).
 int ab_stack_pair_device(ab_ctx *ctx, const StackPlan &plan, const float *const *dplanes, size_t n, int64_t rows, int64_t cols,
                          const ab_stack_config *cfg, float *out_dev, bool median_only) {
     AB_CHECK(ctx, n > 128 && n <= 1024, "the multi-lane stack takes 129 .. 1024 frames (got %zu)", n);
-    AB_CHECK(ctx, plan.engine == kEnginePair || plan.engine == kEngineDuo || plan.engine == kEngineQuad, "internal: not a multi-lane plan");
+    AB_CHECK(ctx, plan.engine == kEnginePair || plan.engine == kEngineLanes, "internal: not a multi-lane plan");
     const int H = plan.h;  // samples per lane of THIS file's kernel (129 .. 512 frames)
     constexpr size_t kTab = 1024;  // [0, kTab): the fast pass's table (frames, then the +inf plane); [kTab, kTab + 512): this file's kernel's
     void *ws = nullptr;
@@ -358,12 +358,11 @@ int ab_stack_pair_device(ab_ctx *ctx, const StackPlan &plan, const float *const 
         AB_HIP(ctx, hipGetLastError());
         return AB_OK;
     }
-    // the lists (the fast pass's waves: 32 pixels each with two lanes per pixel, 16 / 8 with four / eight and the grid a multiple of 8).
+    // the lists (the fast pass's waves: 32 / 16 / 8 pixels each with two / four / eight lanes per pixel).
     // Always cleared (16 KB, in stream order): a call that failed between the two passes would not have left the counters at zero
-    const int64_t px_wave = 64 / plan.lanes;
-    const int64_t waves = plan.engine == kEngineQuad ? ((total + px_wave - 1) / px_wave + 7) / 8 * 8 : (total + 31) / 32;
+    const StackLanesGrid grid = ab_stack_lanes_grid(plan.lanes, total);
     ab_stack_lists lists;
-    AB_TRY(ab_stack_lists_setup(ctx, AB_WS_STACK_PAIR_LISTS, waves, px_wave, true, &lists));
+    AB_TRY(ab_stack_lists_setup(ctx, AB_WS_STACK_PAIR_LISTS, grid.waves, grid.px_wave, true, &lists));
     a.list_count = lists.count;
     a.list_ticket = lists.ticket;
     a.list = lists.list;
@@ -371,10 +370,7 @@ int ab_stack_pair_device(ab_ctx *ctx, const StackPlan &plan, const float *const 
     PairArgs f = a;
     f.p = (const float *const *)ws;
     f.half = plan.r;
-    if (plan.engine == kEngineQuad)
-        AB_TRY(ab_stack_quad_launch(ctx, plan.lanes, plan.r, f));
-    else
-        AB_TRY(ab_stack_duo_launch(ctx, plan.r, f));
+    AB_TRY(ab_stack_lanes_launch(ctx, plan.lanes, plan.r, f));
     AB_TRY(ab_stack_lists_trace(ctx, lists, total));
     if (plan.list == kListWide16)  // the wave-per-pixel kernel walks the lists
         return ab_stack_wide_list_device(ctx, (const float *const *)ws, n, rows, cols, cfg, out_dev, median_only, a.list_count, a.list, lists.cap);

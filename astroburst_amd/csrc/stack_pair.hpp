@@ -1,6 +1,6 @@
-// Shared by the multi-lane stacking kernels (stack_pair.hip: two lanes per pixel, the oracle's arithmetic word for word; stack_duo.hip
-// and stack_quad.hip: two, four or eight lanes per pixel, the fast engine's running sums): H samples per lane, lanes 2k and 2k + 1
-// share pixel k of the wave's 32.
+// Shared by the multi-lane stacking kernels (stack_pair.hip: two lanes per pixel, the oracle's arithmetic word for word; stack_lanes.hip:
+// two, four or eight lanes per pixel, the fast engine's running sums): H samples per lane, the lanes of a pixel adjacent in the wave
+// (lanes 2k and 2k + 1 share pixel k of the wave's 32; four or eight lanes pixel k of 16 or 8).
 #pragma once
 #include "stack_shared.hpp"
 
@@ -50,16 +50,29 @@ struct PairArgs {
     int walk_lists;
 };
 
-// the partner lane's value (lanes 2k <-> 2k+1): DPP quad_perm [1,0,3,2]
-__device__ __forceinline__ float swapf(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xf, 0xf, false));
+// another lane's value through DPP: quad_perm, row_half_mirror or row_shl by a compile-time control word
+template <int CTRL>
+__device__ __forceinline__ int dppi(int x) {
+    return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xf, 0xf, false);
 }
-__device__ __forceinline__ int swapi(int x) { return __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xf, 0xf, false); }
-__device__ __forceinline__ double swapd(double x) {
+template <int CTRL>
+__device__ __forceinline__ float dppf(float x) {
+    return __builtin_bit_cast(float, dppi<CTRL>(__builtin_bit_cast(int, x)));
+}
+template <int CTRL>
+__device__ __forceinline__ double dppd(double x) {
     const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-    const unsigned int lo = (unsigned int)swapi((int)(unsigned int)u), hi = (unsigned int)swapi((int)(unsigned int)(u >> 32));
+    const unsigned int lo = (unsigned int)dppi<CTRL>((int)(unsigned int)u), hi = (unsigned int)dppi<CTRL>((int)(unsigned int)(u >> 32));
     return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
+constexpr int kSwap1 = 0xB1;        // quad_perm [1,0,3,2]: lane q ^ 1
+constexpr int kSwap2 = 0x4E;        // quad_perm [2,3,0,1]: lane q ^ 2
+constexpr int kRev = 0x1B;          // quad_perm [3,2,1,0]: lane q ^ 3
+constexpr int kHalfMirror = 0x141;  // row_half_mirror: lane 7 - i of every 8
+// the partner lane's value (lanes 2k <-> 2k+1)
+__device__ __forceinline__ float swapf(float x) { return dppf<kSwap1>(x); }
+__device__ __forceinline__ int swapi(int x) { return dppi<kSwap1>(x); }
+__device__ __forceinline__ double swapd(double x) { return dppd<kSwap1>(x); }
 
 // The network's min / max are inline assembly, and the compiler's hazard recogniser does not see a VALU write inside an asm
 // statement: a DPP read of such a register within two wait states returns the OLD value.  Every sample therefore passes through
@@ -110,26 +123,36 @@ __device__ __forceinline__ void bitonic_merge(float (&v)[H]) {
     half_cleaner<H, 1>(v);
 }
 
-// One cross step -- v[i] against the partner's v[H - 1 - i] -- leaves the H smallest of the pair's 2H sorted samples in the even
-// lane and the H largest in the odd lane, each a bitonic sequence.
-// (An exchange keeps v_med3(x, partner, -inf) = the minimum in the even lane, v_med3(x, partner, +inf) = the maximum in the odd
-// lane: one instruction by a per-lane constant instead of min, max and a select.)
-template <int H>
-__device__ __forceinline__ void cross_step(float (&v)[H], bool odd) {
-    const float sel = odd ? __builtin_inff() : -__builtin_inff();
+// One cross step -- v[i] against the partner lane's v[H - 1 - i] -- leaves the H smallest of two lanes' 2H sorted samples in the one
+// lane and the H largest in the other, each a bitonic sequence.  An exchange keeps v_med3(x, partner, sel): the minimum where sel = -inf,
+// the maximum where sel = +inf -- one instruction by a per-lane constant instead of min, max and a select.
+template <int CTRL, int H>
+__device__ __forceinline__ void cross_rev(float (&v)[H], float sel) {
 #pragma unroll
     for (int i = 0; i < H / 2; ++i) {
-        const float t1 = swapf(v[H - 1 - i]), t2 = swapf(v[i]);
+        const float t1 = dppf<CTRL>(v[H - 1 - i]), t2 = dppf<CTRL>(v[i]);
         const float a = ab_v_med3(v[i], t1, sel), b = ab_v_med3(v[H - 1 - i], t2, sel);
         v[i] = a;
         v[H - 1 - i] = b;
     }
 }
+// v[i] against the partner lane's v[i]: the half-cleaner stage of distance H of a bitonic merge over two lanes
+template <int CTRL, int H>
+__device__ __forceinline__ void cross_same(float (&v)[H], float sel) {
+#pragma unroll
+    for (int i = 0; i < H; ++i) {
+        const float t = dppf<CTRL>(v[i]);
+        v[i] = ab_v_med3(v[i], t, sel);
+    }
+}
+// the pair's cross step: the smaller half to the even lane, the larger to the odd lane
+template <int H>
+__device__ __forceinline__ void cross_step(float (&v)[H], bool odd) {
+    cross_rev<kSwap1>(v, odd ? __builtin_inff() : -__builtin_inff());
+}
 
 }  // namespace abpair
 
-// stack_duo.hip: the fast pass of a 129 .. 256-frame stack (128 samples per lane, class R); the arguments' table holds 2 R pointers
-int ab_stack_duo_launch(ab_ctx *ctx, int R, const abpair::PairArgs &args);
-// stack_quad.hip: the fast pass of a 257 .. 512-frame (L = 4 lanes per pixel) or 513 .. 1024-frame (L = 8) stack, 128 samples per lane
-// (class R of frames per lane); the table holds L R pointers
-int ab_stack_quad_launch(ab_ctx *ctx, int L, int R, const abpair::PairArgs &args);
+// stack_lanes.hip: the fast pass of a 129 .. 1024-frame stack on L = 2, 4 or 8 lanes per pixel (129 .. 256, 257 .. 512, 513 .. 1024 frames),
+// 128 samples per lane (class R of frames per lane); the arguments' table holds L R pointers
+int ab_stack_lanes_launch(ab_ctx *ctx, int L, int R, const abpair::PairArgs &args);

@@ -10,9 +10,9 @@
 //   2 .. 64      n < np, np >= 8, contiguous, < 2^30 px     one plane of +inf pads the table up to np: single-pass DIRECT kernel
 //   2 .. 64      otherwise                                  launch_stack<PARTIAL, EXACT, STAGE>, DIRECT iff n == np, contiguous, < 2^30 px
 //   65 .. 128    plain, not exact                           NP = 128 DIRECT (pads up to 128): two-pass when n == 128 and not the median
-//   129 .. 256   plain, default or median                   stack_duo_fast_kernel<128, R>, then stack_pair_kernel<128> in list mode
-//   257 .. 512   plain, default or median                   stack_quad_fast_kernel<4, R>, then stack_pair_kernel<256> in list mode
-//   513 .. 1024  plain, default or median                   stack_quad_fast_kernel<8, R>, then stack_wide_list_kernel<16>
+//   129 .. 256   plain, default or median                   stack_lanes_fast_kernel<2, R>, then stack_pair_kernel<128> in list mode
+//   257 .. 512   plain, default or median                   stack_lanes_fast_kernel<4, R>, then stack_pair_kernel<256> in list mode
+//   513 .. 1024  plain, default or median                   stack_lanes_fast_kernel<8, R>, then stack_wide_list_kernel<16>
 //   129 .. 512   plain, exact                               stack_pair_kernel<128 or 256> over all pixels
 //   65 .. 4096   everything else                            stack_wide_*: K = 2, 4, 8, 16, 32, 64 registers per lane by n
 //   > deep_from  everything that is not the NP = 128 route  stack_deep_kernel
@@ -32,8 +32,7 @@ enum StackEngine {
     kEngineSingle,  // stack_sigma_clip.hip: stack_single_kernel
     kEngineLane,    // stack_sigma_clip.hip: one lane per pixel, NP = 2 .. 128 samples in registers
     kEnginePair,    // stack_pair.hip over all pixels: two lanes per pixel, the oracle's arithmetic
-    kEngineDuo,     // stack_duo.hip's fast pass (two lanes per pixel), then a list pass
-    kEngineQuad,    // stack_quad.hip's fast pass (four or eight lanes per pixel), then a list pass
+    kEngineLanes,   // stack_lanes.hip's fast pass (`lanes` = two, four or eight lanes per pixel), then a list pass
     kEngineWide,    // stack_wide.hip: one wave per pixel
     kEngineDeep,    // stack_deep.hip: one workgroup per pixel
 };
@@ -50,9 +49,9 @@ struct StackPlan {
     int engine;    // StackEngine
     int lanes;     // lanes per pixel: 1, 2, 4, 8; 64 for the wave-per-pixel engine; 0 for the workgroup-per-pixel engine
     int np;        // kEngineLane: samples per lane (NP)
-    int h;         // kEnginePair / Duo / Quad: samples per lane of stack_pair.hip's kernel (H)
+    int h;         // kEnginePair / Lanes: samples per lane of stack_pair.hip's kernel (H)
     int k;         // kEngineWide: registers per lane (K)
-    int r;         // kEnginePair / Duo / Quad: frames per lane in the pointer table (the class R of a fast pass, H for the exact kernel)
+    int r;         // kEnginePair / Lanes: frames per lane in the pointer table (the class R of a fast pass, H for the exact kernel)
     bool pad_inf;  // a plane of +inf stands in for the frames the table is short of
     bool direct;   // kEngineLane: the DIRECT gather (all np slots filled, one row stride, byte offsets fit 32 bits)
     bool two_pass; // a fast pass over every pixel, then `list` over the pixels it handed over
@@ -99,8 +98,8 @@ inline StackPlan ab_stack_plan(size_t n, int64_t total, bool contiguous, bool pa
         return p;
     }
     if (plain && n > 128 && n <= 1024 && !exact) {  // (the median combine too: a pixel with every sample finite needs the sort and one register)
+        p.engine = kEngineLanes;
         p.lanes = n > 512 ? 8 : (n > 256 ? 4 : 2);
-        p.engine = p.lanes == 2 ? kEngineDuo : kEngineQuad;
         p.h = n > 256 ? 256 : 128;
         p.r = (int)(((n + (size_t)p.lanes - 1) / (size_t)p.lanes + 15) / 16) * 16;
         p.pad_inf = true;
@@ -124,4 +123,15 @@ inline StackPlan ab_stack_plan(size_t n, int64_t total, bool contiguous, bool pa
     // the tree sums: the default engine here; the partial sums of the sharded estimator and the exact engine keep the ascending chain
     p.tree = !exact && !partial;
     return p;
+}
+
+// The grid of kEngineLanes' fast pass: one wave per 64 / lanes pixels, the wave count a multiple of 8 (the kernel deals neighbouring
+// pixel groups to the workgroup ids of one XCD).  The launch takes its grid from here and the list set-up its capacity.
+struct StackLanesGrid {
+    int64_t waves;
+    int64_t px_wave;  // pixels per wave
+};
+inline StackLanesGrid ab_stack_lanes_grid(int lanes, int64_t total) {
+    const int64_t px_wave = 64 / lanes;
+    return {((total + px_wave - 1) / px_wave + 7) / 8 * 8, px_wave};
 }

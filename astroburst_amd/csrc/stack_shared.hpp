@@ -1,5 +1,5 @@
-// Device helpers the stacking engines share (stack_sigma_clip.hip and, through stack_pair.hpp, stack_pair.hip, stack_duo.hip and
-// stack_quad.hip): one copy each, all of them inlined into the kernels that use them.
+// Device helpers the stacking engines share (stack_sigma_clip.hip and, through stack_pair.hpp, stack_pair.hip and
+// stack_lanes.hip): one copy each, all of them inlined into the kernels that use them.
 #pragma once
 #include "ab_common.hpp"
 

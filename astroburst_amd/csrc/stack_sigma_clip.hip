@@ -1296,8 +1296,7 @@ int ab_stack_device(ab_ctx *ctx, const float *const *dplanes, const int64_t *ld,
                 AB_TRY(partial ? (launch_stack<true, false>(ctx, plan, args)) : (launch_stack<false, false>(ctx, plan, args)));
             break;
         case kEnginePair:
-        case kEngineDuo:
-        case kEngineQuad:
+        case kEngineLanes:
             AB_TRY(ab_stack_pair_device(ctx, plan, dplanes, n, rows, cols, cfg, out_dev, median_only));
             break;
         case kEngineWide:

@@ -324,7 +324,7 @@ __global__ __launch_bounds__(64 * tile_waves<K>()) void stack_wide_tile_kernel(c
     if (lane == 0 && rej_total) atomicAdd(&a.rejected[(blockIdx.x * (unsigned int)kTileWaves + (unsigned int)wv) & (kRejSlots - 1)], rej_total);
 }
 
-// The pixels a multi-lane fast pass (stack_quad.hip, 513 .. 1024 frames) handed over: `slots` lists of up to `cap` pixel indices, one
+// The pixels a multi-lane fast pass (stack_lanes.hip, 513 .. 1024 frames) handed over: `slots` lists of up to `cap` pixel indices, one
 // workgroup per list, a wave per pixel, the same wide_pixel (the oracle's ascending sums).  Leaves its list empty.
 template <int K>
 __global__ __launch_bounds__(256) void stack_wide_list_kernel(const WideArgs a, unsigned int *__restrict__ list_count, const int *__restrict__ list,

@@ -184,8 +184,8 @@ def clean_frames(n, shape, seed, every=11, rate=0.02):
                                257, 258, 263, 264, 265, 266, 300, 319, 320, 321, 322, 383, 384, 385, 386, 391, 392, 393, 447, 448, 449, 511, 512,
                                513, 514, 520, 521, 639, 640, 641, 648, 649, 767, 768, 769, 776, 777, 895, 896, 897, 904, 905, 1000, 1023, 1024])
 def test_two_lane_fast_pass(engine, oracle, n):
-    """Round 6: 129 .. 512 frames with every sample finite -- the fast passes csrc/stack_duo.hip (129 .. 256: two
-    lanes per pixel, 128 samples each) and csrc/stack_quad.hip (257 .. 512: four lanes per pixel; 513 .. 1024: eight), frame-count classes of 32 / 64,
+    """Round 6: 129 .. 512 frames with every sample finite -- the fast pass csrc/stack_lanes.hip (129 .. 256: two
+    lanes per pixel, 128 samples each; 257 .. 512: four lanes per pixel; 513 .. 1024: eight), frame-count classes of 32 / 64,
     the median / MAD instance chosen by n / 2, eight samples per end, running moments -- + stack_pair.hip's list pass for what they
     hand over.  Both sides of every class boundary, odd and even counts, the counts whose top lane holds at most eight samples (the
     high walk goes on into the lane below), a pixel count that leaves the last wave partly filled; settings that clip nothing, a
@@ -203,6 +203,47 @@ def test_two_lane_fast_pass(engine, oracle, n):
         assert_stack_parity(got, want, rej, wrej, exact)
     # the median combine takes the same fast pass (an order statistic: bit for bit on either engine)
     assert np.array_equal(ctx.median_combine(fr), oracle.median_combine(fr), equal_nan=True)
+
+
+CROSS_LANE_SETTINGS = ((6.0, 6.0, 5), (3.0, 3.0, 1), (3.0, 3.0, 5), (3.0, 3.0, 0))
+_cross_lane_cases = {}
+
+
+def cross_lane_case(oracle, n):
+    """11 x 13 frames of normal(500, 12); pixel (i, j), i, j = 0 .. 9, has j samples raised and i samples lowered by 300 + k (k = the
+    frame's index: no ties) on frames a seeded permutation draws.  The frames and the oracle's answers, computed once per n."""
+    if n not in _cross_lane_cases:
+        rng = np.random.default_rng(n)
+        cube = rng.normal(500.0, 12.0, (n, 11, 13)).astype(np.float32)
+        for i in range(10):
+            for j in range(10):
+                ks = rng.permutation(n)[:i + j]
+                for k in ks[:j]:
+                    cube[k, i, j] += np.float32(300 + k)
+                for k in ks[j:]:
+                    cube[k, i, j] -= np.float32(300 + k)
+        fr = [cube[k] for k in range(n)]
+        want = [oracle.stack_images(fr, sl, sh, it) for sl, sh, it in CROSS_LANE_SETTINGS]
+        _cross_lane_cases[n] = (fr, want, oracle.median_combine(fr))
+    return _cross_lane_cases[n]
+
+
+@pytest.mark.parametrize("n", [131, 136, 137, 259, 264, 265, 387, 515, 520, 521, 643, 771, 899, 1024])
+def test_multi_lane_walks_cross_lane_boundaries(engine, oracle, n):
+    """csrc/stack_lanes.hip's lane-role predicates: the high walk that goes on from the lane holding rank n - 1 into the lane below it
+    (its `ct <= 1` branch, `hi2_lane`, the `lb -= ch_own` bookkeeping in two lanes at once), which clean_frames' 2 % of outliers in
+    every 11th frame almost never reaches.  The counts whose top lane holds 3, 8 or 9 samples for each of L = 2, 4, 8 and for top lanes
+    1, 2, 4, 5, 6, 7, and the full 1024; 143 pixels, so the last wave is partly filled at every lane count; 0 .. 9 planted samples at
+    each end in every combination (eight is the walk's limit, nine goes to the list pass).  (6, 6, 5) rejects the 900 planted samples
+    and nothing else -- a guard on the fixture."""
+    ctx, exact = engine
+    fr, want, wmed = cross_lane_case(oracle, n)
+    for (sl, sh, it), (wimg, wrej) in zip(CROSS_LANE_SETTINGS, want):
+        if (sl, sh, it) == (6.0, 6.0, 5):
+            assert wrej == 900
+        got, rej = ctx.stack_sigma_clip(fr, sl, sh, it)
+        assert_stack_parity(got, wimg, rej, wrej, exact)
+    assert np.array_equal(ctx.median_combine(fr), wmed, equal_nan=True)
 
 
 @pytest.mark.parametrize("n", [150, 256, 300, 512, 700, 1024])
@@ -299,7 +340,7 @@ def test_two_lanes_per_pixel_stack(engine, oracle, n):
         for sl, sh, it in ((3.0, 3.0, 5), (2.0, 2.5, 3), (1.0, 1.0, 1), (3.0, 3.0, 0), (0.5, 0.5, 8)):
             want, wrej = oracle.stack_images(frames, sl, sh, it)
             got, rej = ctx.stack_sigma_clip(frames, sl, sh, it)
-            # (the default engine: stack_duo.hip's fast pass under the fast contract, this file's kernel for the pixels it hands over)
+            # (the default engine: stack_lanes.hip's fast pass under the fast contract, this file's kernel for the pixels it hands over)
             assert_stack_parity(got, want, rej, wrej, exact)
         assert np.array_equal(ctx.median_combine(frames), oracle.median_combine(frames), equal_nan=True), name
 

@@ -18,7 +18,16 @@ CSRC = os.path.join(ROOT, "astroburst_amd", "csrc")
 HARNESS = r"""
 #include "stack_plan.hpp"
 #include <cstdio>
-int main() {
+#include <cstring>
+int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "grid")) {  // lanes total -> the fast pass's wave count and pixels per wave
+        int lanes; long long total;
+        while (scanf("%d %lld", &lanes, &total) == 2) {
+            const StackLanesGrid g = ab_stack_lanes_grid(lanes, total);
+            printf("%lld %lld\n", (long long)g.waves, (long long)g.px_wave);
+        }
+        return 0;
+    }
     unsigned long n; long long total; int contiguous, partial, median, exact, deep_from, aligned16;
     while (scanf("%lu %lld %d %d %d %d %d %d", &n, &total, &contiguous, &partial, &median, &exact, &deep_from, &aligned16) == 8) {
         const StackPlan p = ab_stack_plan(n, total, contiguous, partial, median, exact, deep_from, aligned16);
@@ -29,7 +38,7 @@ int main() {
 }
 """
 # the enumerators of stack_plan.hpp, in order
-SINGLE, LANE, PAIR, DUO, QUAD, WIDE, DEEP = range(7)
+SINGLE, LANE, PAIR, LANES, WIDE, DEEP = range(6)
 NO_LIST, GENERAL, PAIR128, PAIR256, WIDE16 = range(5)
 SCALAR, QUAD4, TILED = range(3)
 FIELDS = ("engine", "lanes", "np", "h", "k", "r", "pad_inf", "direct", "two_pass", "list", "gather", "tree")
@@ -49,11 +58,11 @@ def lane(np, pad=False, direct=True, two=False):
 
 
 def duo(r):
-    return row(DUO, lanes=2, h=128, r=r, pad_inf=1, two_pass=1, list=PAIR128)
+    return row(LANES, lanes=2, h=128, r=r, pad_inf=1, two_pass=1, list=PAIR128)
 
 
 def quad(lanes, r):
-    return row(QUAD, lanes=lanes, h=256, r=r, pad_inf=1, two_pass=1, list=PAIR256 if lanes == 4 else WIDE16)
+    return row(LANES, lanes=lanes, h=256, r=r, pad_inf=1, two_pass=1, list=PAIR256 if lanes == 4 else WIDE16)
 
 
 def pair(h):
@@ -155,9 +164,9 @@ def planner(tmp_path_factory):
     exe = os.path.join(tmp, "plan_harness")
     subprocess.run([cxx, "-std=c++17", "-Wall", "-Werror", "-I", CSRC, src, "-o", exe], check=True)
 
-    def plan(cases):
+    def plan(cases, *mode):
         text = "".join(" ".join(str(int(x)) for x in c) + "\n" for c in cases)
-        out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
+        out = subprocess.run([exe, *mode], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
         return [tuple(int(x) for x in line.split()) for line in out if line]
     return plan
 
@@ -192,3 +201,18 @@ def test_lowered_deep_threshold_alignment_and_large_planes(planner):
     got = planner([c for c, _ in EXTRA])
     wrong = {c: explain(g, w) for (c, w), g in zip(EXTRA, got) if g != w}
     assert len(got) == len(EXTRA) and not wrong, f"field -> (planned, expected): {wrong}"
+
+
+# (lanes, total) -> (waves, pixels per wave) of the multi-lane fast pass: one wave per 64 / lanes pixels, the wave count rounded up to a
+# multiple of 8 (the kernel deals neighbouring pixel groups to the workgroup ids of one XCD).  Written out, not computed.
+LANES_GRID = {
+    (2, 1): (8, 32), (2, 31): (8, 32), (2, 32): (8, 32), (2, 33): (8, 32), (2, 4100): (136, 32), (2, 1 << 24): (524288, 32),
+    (4, 1): (8, 16), (4, 31): (8, 16), (4, 32): (8, 16), (4, 33): (8, 16), (4, 4100): (264, 16), (4, 1 << 24): (1048576, 16),
+    (8, 1): (8, 8), (8, 31): (8, 8), (8, 32): (8, 8), (8, 33): (8, 8), (8, 4100): (520, 8), (8, 1 << 24): (2097152, 8),
+}
+
+
+def test_the_fast_pass_grid(planner):
+    """ab_stack_lanes_grid: the one place the launch takes its grid from and the list set-up its capacity"""
+    got = planner(list(LANES_GRID), "grid")
+    assert dict(zip(LANES_GRID, got)) == LANES_GRID
