@@ -243,6 +243,35 @@ __device__ __forceinline__ double catmull_weight_fused(double f) {
     return cr_outer_fused(fabs(f - 2.0));
 }
 
+// a wave-uniform pointer into global memory pinned to scalar registers: the address `scalar base + 32-bit lane offset` is then formed
+// by the load or store itself, where the compiler would otherwise chain 64-bit vector adds from row to row.  (The pointer type names
+// the global address space because the empty asm hides where the pointer came from.)
+typedef __attribute__((address_space(1))) char *global_bytes;
+__device__ __forceinline__ global_bytes scalar_base(const void *p) {
+    global_bytes g = (global_bytes)p;
+    asm("" : "+s"(g));
+    return g;
+}
+__device__ __forceinline__ float load_at(global_bytes base, unsigned byte_off, int i) {
+    return ((const __attribute__((address_space(1))) float *)(base + byte_off))[i];
+}
+__device__ __forceinline__ void store_at(global_bytes base, unsigned byte_off, float v) {
+    *(__attribute__((address_space(1))) float *)(base + byte_off) = v;
+}
+
+// the lane mask of one integer compare, straight from the instruction (a ballot of a bool that is an `&` of compares costs a select
+// and a further compare); every lane of the workgroup is active where these are used
+__device__ __forceinline__ unsigned long long lanes_eq(int a, int b) {
+    unsigned long long m;
+    asm volatile("v_cmp_eq_u32_e64 %0, %1, %2" : "=s"(m) : "v"(a), "v"(b));
+    return m;
+}
+__device__ __forceinline__ unsigned long long lanes_below(unsigned a, unsigned bound) {  // a < bound, bound wave-uniform
+    unsigned long long m;
+    asm volatile("v_cmp_gt_u32_e64 %0, %1, %2" : "=s"(m) : "s"(bound), "v"(a));
+    return m;
+}
+
 // warp_kernel for transforms that are close to a translation (|d - 1| and |b| <= 1/64: ab_warp_rows_device decides): one lane owns
 // one output column and K consecutive output rows.  The pixel below almost always samples the same four source columns and three of
 // the same four source rows, so where that holds for a whole wave the K footprints are walked as ONE column strip of K + 3 source
@@ -251,7 +280,19 @@ __device__ __forceinline__ double catmull_weight_fused(double f) {
 // A wave that cannot share -- frame borders, a column crossing inside a group, a ragged last group or last piece -- runs the
 // per-pixel body for each of its K rows, at the per-pixel kernel's cost.  Groups are aligned to the band's first row (row0), not to
 // the image; `nrows` is the band's height (the grid has ceil(nrows / K) rows of workgroups).
-template <int K>
+//
+// The sharing decision comes FIRST and on truncated coordinates (LABNOTES 37): ix, iy are v_cvt_i32_f64 of sx, sy themselves (round
+// toward zero, saturating), and a lane shares when
+//     (unsigned)(ix[0] - 1) < src_cols - 3  and  (unsigned)(iy[0] - 1) < src_rows - K - 2   (bounds clamped at 0)
+//     ix[k] == ix[0]  and  iy[k] == iy[0] + k  for k > 0,   its column is live,   and (scalar) the group's K rows are in the band.
+// A coordinate below 1 truncates to at most 0 and fails the unsigned compare, a saturated one fails it too, so where the predicate
+// holds every coordinate of the group is >= 1 and truncation IS the floor: the predicate marks exactly the waves for which the former
+// one (live, inside, interior, equal floor(sx), consecutive floor(sy)) held.  There floor(s) <= s < 2 floor(s), so s - floor(s) is
+// exact and below 1: it is what v_fract_f64 returns, whose clamp never acts.  The floors, `in`, `interior` and the floor-based
+// fractions are needed by the fallback body alone and are computed there.
+// OFF32: the byte offset of a source tap fits 32 bits (src_rows * src_cols <= 2^30: the host decides), so a row's address is a scalar
+// base, advanced by the wave-uniform stride, plus one per-lane 32-bit offset.
+template <int K, bool OFF32>
 __global__ __launch_bounds__(256) void warp_kernel_shared(const float *__restrict__ src, int src_rows, int src_cols, double a, double b,
                                                           double tx, double c, double d, double ty, int out_rows, int out_cols,
                                                           float *__restrict__ out, int row0, int nrows) {
@@ -259,42 +300,52 @@ __global__ __launch_bounds__(256) void warp_kernel_shared(const float *__restric
     xcd_band_piece(piece_x, piece_y);
     const int x = piece_x * 256 + threadIdx.x;
     const int yb = piece_y * K;  // the group's first row within the band
-    const bool col_live = x < out_cols;
     const double xf = (double)x;
     const double axf = a * xf, cxf = c * xf;  // (the same correctly rounded products for each of the K rows)
+    double sx[K], sy[K];
     int ix[K], iy[K];
-    double frx[K], fry[K];
-    bool in[K], live[K];
-    bool share = true;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const double yf = (double)(yb + k + row0);
-        const double sx = axf + b * yf + tx;
-        const double sy = cxf + d * yf + ty;
-        const double fx = floor(sx), fy = floor(sy);
-        asm("v_cvt_i32_f64 %0, %1" : "=v"(ix[k]) : "v"(fx));
-        asm("v_cvt_i32_f64 %0, %1" : "=v"(iy[k]) : "v"(fy));
-        live[k] = col_live && yb + k < nrows;
-        in[k] = live[k] && (unsigned)ix[k] < (unsigned)(src_cols - 1) && (unsigned)iy[k] < (unsigned)(src_rows - 1);
-        frx[k] = sx - fx;
-        fry[k] = sy - fy;
-        const bool interior = ix[k] >= 1 && ix[k] + 2 < src_cols && iy[k] >= 1 && iy[k] + 2 < src_rows;
-        share = share && in[k] && interior && ix[k] == ix[0] && iy[k] == iy[0] + k;
+        sx[k] = axf + b * yf + tx;
+        sy[k] = cxf + d * yf + ty;
+        asm("v_cvt_i32_f64 %0, %1" : "=v"(ix[k]) : "v"(sx[k]));  // (truncating, saturating; see above)
+        asm("v_cvt_i32_f64 %0, %1" : "=v"(iy[k]) : "v"(sy[k]));
     }
-    float r[K];
+    const unsigned col_bound = (unsigned)max(src_cols - 3, 0), row_bound = (unsigned)max(src_rows - K - 2, 0);  // (scalar)
+    // (lane masks and scalar `&`: no exec-mask region belongs in this prologue)
+    unsigned long long share = lanes_below((unsigned)x, (unsigned)out_cols) & lanes_below((unsigned)ix[0] - 1u, col_bound) &
+                               lanes_below((unsigned)iy[0] - 1u, row_bound);
+#pragma unroll
+    for (int k = 1; k < K; ++k) share &= lanes_eq(ix[k], ix[0]) & lanes_eq(iy[k], (int)((unsigned)iy[0] + k));  // (a saturated iy[0] wraps)
+    float *const out_row = out + (size_t)yb * out_cols;  // (scalar; the K stores add a wave-uniform stride and the lane's x to it)
     // THE INVARIANT of the shared path: it loads exactly the union of the taps the K per-pixel samplers would load -- columns
     // ix[0] - 1 .. ix[0] + 2 of rows iy[0] - 1 .. iy[0] + K + 1 -- and forms no other address.  Every pixel of the group is live, inside
     // and interior with ix[k] = ix[0] and iy[k] = iy[0] + k, so that rectangle IS the union of the K 4 x 4 footprints; nothing is
     // loaded for a pixel that would not sample.  ab_warp_image_rows_from_band hands this kernel a base pointer moved back by the
     // band's first row and only warp_source_rows' exact hull of the sampling pixels' footprints behind it: a row read beyond that
     // union is a memory fault.
-    if (__all(share)) {
-        const float *p = src + (iy[0] - 1) * src_cols + (ix[0] - 1);
-        double wx[K][4], val[K];
+    if (yb + K - 1 < nrows && share == __builtin_amdgcn_ballot_w64(true)) {  // (every lane of the wave)
+        const float *p = nullptr;
+        unsigned off = 0;
+        if constexpr (OFF32) off = (((unsigned)iy[0] - 1u) * (unsigned)src_cols + ((unsigned)ix[0] - 1u)) * 4u;
+        else p = src + (iy[0] - 1) * src_cols + (ix[0] - 1);
+        double wx[K][4], val[K], frx[K], fry[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            frx[k] = __builtin_amdgcn_fract(sx[k]);
+            fry[k] = __builtin_amdgcn_fract(sy[k]);
+        }
 #pragma unroll
         for (int s = 0; s < K + 3; ++s) {
-            const float *row = p + s * src_cols;
-            const double t0 = (double)row[0], t1 = (double)row[1], t2 = (double)row[2], t3 = (double)row[3];
+            double t0, t1, t2, t3;
+            if constexpr (OFF32) {
+                const global_bytes row = scalar_base(src + (size_t)s * (unsigned)src_cols);
+                t0 = (double)load_at(row, off, 0), t1 = (double)load_at(row, off, 1), t2 = (double)load_at(row, off, 2), t3 = (double)load_at(row, off, 3);
+            } else {
+                const float *row = p + s * src_cols;
+                t0 = (double)row[0], t1 = (double)row[1], t2 = (double)row[2], t3 = (double)row[3];
+            }
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 const int j = s - k;  // source row s is tap row j of pixel k
@@ -313,34 +364,51 @@ __global__ __launch_bounds__(256) void warp_kernel_shared(const float *__restric
             }
         }
 #pragma unroll
-        for (int k = 0; k < K; ++k) r[k] = (float)val[k];
+        for (int k = 0; k < K; ++k)  // (every pixel of a sharing wave is live)
+            store_at(scalar_base(out_row + (size_t)k * (unsigned)out_cols), (unsigned)x * 4u, (float)val[k]);
     } else {  // the per-pixel body, row by row
 #pragma unroll
         for (int k = 0; k < K; ++k) {
+            const double fx = floor(sx[k]), fy = floor(sy[k]);
+            int jx, jy;
+            asm("v_cvt_i32_f64 %0, %1" : "=v"(jx) : "v"(fx));
+            asm("v_cvt_i32_f64 %0, %1" : "=v"(jy) : "v"(fy));
+            const bool live = x < out_cols && yb + k < nrows;
+            const bool in = live && (unsigned)jx < (unsigned)(src_cols - 1) && (unsigned)jy < (unsigned)(src_rows - 1);
             double wx0, wx1, wx2, wx3, wy0, wy1, wy2, wy3;
-            catmull_weights_fused(frx[k], wx0, wx1, wx2, wx3);  // (of no consequence where `in` is false)
-            catmull_weights_fused(fry[k], wy0, wy1, wy2, wy3);
-            const bool interior = ix[k] >= 1 && ix[k] + 2 < src_cols && iy[k] >= 1 && iy[k] + 2 < src_rows;
-            r[k] = 0.0f;
-            if (__all(interior || !in[k])) {
-                if (in[k]) r[k] = bicubic_taps_interior(src, src_cols, ix[k], iy[k], wx0, wx1, wx2, wx3, wy0, wy1, wy2, wy3);
-            } else if (in[k]) {
-                r[k] = bicubic_taps(src, src_rows, src_cols, src_cols, ix[k], iy[k], wx0, wx1, wx2, wx3, wy0, wy1, wy2, wy3);
+            catmull_weights_fused(sx[k] - fx, wx0, wx1, wx2, wx3);  // (of no consequence where `in` is false)
+            catmull_weights_fused(sy[k] - fy, wy0, wy1, wy2, wy3);
+            const bool interior = jx >= 1 && jx + 2 < src_cols && jy >= 1 && jy + 2 < src_rows;
+            float r = 0.0f;
+            if (__all(interior || !in)) {
+                if (in) r = bicubic_taps_interior(src, src_cols, jx, jy, wx0, wx1, wx2, wx3, wy0, wy1, wy2, wy3);
+            } else if (in) {
+                r = bicubic_taps(src, src_rows, src_cols, src_cols, jx, jy, wx0, wx1, wx2, wx3, wy0, wy1, wy2, wy3);
             }
+            if (live) out_row[(size_t)k * out_cols + x] = r;
         }
     }
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-        if (live[k]) out[(size_t)(yb + k) * out_cols + x] = r[k];
 }
 
 template <int K>
 void launch_warp_shared(ab_ctx *ctx, unsigned lds, const float *src, int64_t src_rows, int64_t src_cols, const double t[6], int64_t out_rows,
                         int64_t out_cols, int64_t row0, int64_t nrows, float *out) {
     const dim3 grid((unsigned)((out_cols + 255) / 256), (unsigned)((nrows + K - 1) / K)), block(256);
-    hipLaunchKernelGGL(warp_kernel_shared<K>, grid, block, lds, ctx->stream, src, (int)src_rows, (int)src_cols, t[0], t[1], t[2], t[3], t[4],
-                       t[5], (int)out_rows, (int)out_cols, out, (int)row0, (int)nrows);
+    bool off32 = src_rows * src_cols <= (int64_t(1) << 30);  // every tap's byte offset fits 32 bits
+#ifdef AB_DEV_ABLATION  // AB_WARP_OFF64=1: the instance for sources above 2^30 pixels on every source (so that the small tests reach it)
+    static const bool off64 = ab_dev_env("AB_WARP_OFF64") && atoi(ab_dev_env("AB_WARP_OFF64")) != 0;
+    off32 = off32 && !off64;
+#endif
+    if (off32)
+        hipLaunchKernelGGL((warp_kernel_shared<K, true>), grid, block, lds, ctx->stream, src, (int)src_rows, (int)src_cols, t[0], t[1], t[2], t[3],
+                           t[4], t[5], (int)out_rows, (int)out_cols, out, (int)row0, (int)nrows);
+    else
+        hipLaunchKernelGGL((warp_kernel_shared<K, false>), grid, block, lds, ctx->stream, src, (int)src_rows, (int)src_cols, t[0], t[1], t[2], t[3],
+                           t[4], t[5], (int)out_rows, (int)out_cols, out, (int)row0, (int)nrows);
 }
+
+// a source too small for any group to share (the clamped bounds of warp_kernel_shared's predicate are then 0) keeps the per-pixel kernel
+inline bool warp_can_share(int64_t src_rows, int64_t src_cols, int K) { return src_cols >= 4 && src_rows >= K + 3; }
 
 // resample.rs:41-58: target pixel centres mapped onto the source grid
 __global__ __launch_bounds__(256) void resample_kernel(const float *__restrict__ src, int src_rows, int src_cols, double scale_y,
@@ -407,7 +475,7 @@ int ab_warp_device(ab_ctx *ctx, const float *src, int64_t src_rows, int64_t src_
 
 // rows [row0, row0 + nrows) of warp_image(src, t, out_rows, out_cols) into the contiguous nrows x out_cols plane `out`
 constexpr long kWarpLdsKB = 0;  // (see ab_warp_rows_device)
-constexpr int kWarpShareK = 3;  // output rows per lane of warp_kernel_shared (the K sweep: LABNOTES 33)
+constexpr int kWarpShareK = 3;  // output rows per lane of warp_kernel_shared (the K sweeps: LABNOTES 33 and 37)
 int ab_warp_rows_device(ab_ctx *ctx, const float *src, int64_t src_rows, int64_t src_cols, const double t[6], int64_t out_rows,
                         int64_t out_cols, int64_t row0, int64_t nrows, float *out) {
     AB_HIP(ctx, hipSetDevice(ctx->device));
@@ -452,6 +520,7 @@ int ab_warp_rows_device(ab_ctx *ctx, const float *src, int64_t src_rows, int64_t
     static const int share_env = ab_dev_env("AB_WARP_SHARE_K") ? atoi(ab_dev_env("AB_WARP_SHARE_K")) : kWarpShareK;
     if (share_k) share_k = share_env;
 #endif
+    if (!warp_can_share(src_rows, src_cols, share_k)) share_k = 0;
     switch (share_k) {
 #ifdef AB_DEV_ABLATION
     case 2: launch_warp_shared<2>(ctx, warp_lds, src, src_rows, src_cols, t, out_rows, out_cols, row0, nrows, out); break;
