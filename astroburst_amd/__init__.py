@@ -19,5 +19,6 @@ from .core import BackgroundStepResult  # noqa: F401
 from .core import ComposeRgbResult  # noqa: F401
 from .core import matches_from_votes, triangle_votes_host  # noqa: F401
 from .core import SynthFrames, synth_chacha_block, synth_config, synth_noise_params, synth_psf_type, synth_rng_f64, synth_star_field  # noqa: F401
+from .core import StackFrameParams, SubframeMetrics, stack_frame_params, stack_params_from_metrics  # noqa: F401
 
 __version__ = "0.2.0"

@@ -381,6 +381,14 @@ class SubframeMetricsC(C.Structure):  # subframe.rs:9-22
                 ("noise_ratio", C.c_double), ("weight", C.c_double), ("accepted", C.c_int32)]
 
 
+class StackFrameParamC(C.Structure):  # ab_stack_frame_param: one frame of ab_stack_weighted
+    _fields_ = [("weight", C.c_double), ("scale", C.c_float), ("offset", C.c_float)]
+
+
+STACK_MAX_ACTIVE = 64                                                # AB_STACK_MAX_ACTIVE
+STACK_NORM = {"none": 0, "additive": 1, "multiplicative": 2}         # ab_stack_norm
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     """hipcc --offload-arch=gfx950 every csrc/*.hip into astroburst_amd/libastroburst_hip.so."""
     cmd = ["make", "-C", CSRC, "-j8"] + (["-B"] if force else [])
@@ -518,6 +526,9 @@ def lib() -> C.CDLL:
     L.ab_analyze_subframes.argtypes = [vp, pp, C.c_size_t, C.POINTER(SubframeWeightConfigC), C.POINTER(SubframeMetricsC)]
     L.ab_normalize_subframe_weights.argtypes = [C.POINTER(SubframeMetricsC), C.c_size_t]
     L.ab_normalize_subframe_weights.restype = None
+    L.ab_stack_weighted.argtypes = [vp, pp, C.POINTER(StackFrameParamC), C.c_size_t, C.POINTER(StackConfig), pp, pp, C.POINTER(C.c_uint64)]
+    L.ab_stack_params_from_metrics.argtypes = [C.POINTER(SubframeMetricsC), C.c_size_t, C.c_int32, C.POINTER(StackFrameParamC),
+                                               C.POINTER(C.c_size_t)]
     i64p = C.POINTER(C.c_int64)
     u64p = C.POINTER(C.c_uint64)
     L.ab_batch_stack_config_default.argtypes = [C.POINTER(BatchStackConfigC)]

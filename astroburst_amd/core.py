@@ -632,6 +632,50 @@ class SubframeMetrics:  # subframe.rs:9-22 (file_path stays with the caller)
     accepted: bool
 
 
+class StackFrameParams(NamedTuple):
+    """ab_stack_frame_param of n frames, column by column: what stack_params_from_metrics returns and Context.stack_weighted takes"""
+    weights: np.ndarray    # f64 [n]; 0 = the frame takes no part
+    scales: np.ndarray     # f32 [n]
+    offsets: np.ndarray    # f32 [n]
+    reference: int         # the frame the others were normalised to
+
+
+def stack_params_from_metrics(metrics, normalize: str = "none") -> StackFrameParams:
+    """ab_stack_params_from_metrics: the weights of the accepted subframes and, with normalize = "additive" | "multiplicative", the
+    offsets or scales that bring every frame's background to the best frame's.  Host arithmetic in the library: no GPU, no context."""
+    if normalize not in _lib.STACK_NORM:
+        raise AstroBurstError(_lib.AB_ERR_INVALID, f"normalize must be one of {sorted(_lib.STACK_NORM)} (got {normalize!r})")
+    n = len(metrics)
+    ms = (_lib.SubframeMetricsC * max(n, 1))(*[
+        _lib.SubframeMetricsC(int(m.star_count), m.median_fwhm, m.median_eccentricity, m.median_snr, m.background_median, m.background_sigma,
+                              m.noise_ratio, m.weight, 1 if m.accepted else 0) for m in metrics])
+    out = (_lib.StackFrameParamC * max(n, 1))()
+    ref = C.c_size_t(0)
+    rc = _lib.lib().ab_stack_params_from_metrics(ms, n, _lib.STACK_NORM[normalize], out, C.byref(ref))
+    if rc != _lib.AB_OK:
+        raise AstroBurstError(rc, "ab_stack_params_from_metrics: no accepted frame of positive weight, or the best frame's background cannot "
+                                  "be normalised to")
+    return StackFrameParams(np.array([p.weight for p in out[:n]], np.float64), np.array([p.scale for p in out[:n]], np.float32),
+                            np.array([p.offset for p in out[:n]], np.float32), int(ref.value))
+
+
+def stack_frame_params(n: int, weights, scales=None, offsets=None):
+    """-> the ctypes array of n ab_stack_frame_param (scales default to 1, offsets to 0).  Raises what ab_stack_weighted would return for
+    them, before anything touches the device: a count that is not n, a negative or non-finite weight, a non-finite scale or offset."""
+    w = np.asarray(weights, np.float64).ravel()
+    with np.errstate(over="ignore"):  # (a value beyond f32 becomes inf and is refused below)
+        s = np.ones(n, np.float32) if scales is None else np.asarray(scales, np.float32).ravel()
+        o = np.zeros(n, np.float32) if offsets is None else np.asarray(offsets, np.float32).ravel()
+    for name, a in (("weights", w), ("scales", s), ("offsets", o)):
+        if a.size != n:
+            raise AstroBurstError(_lib.AB_ERR_INVALID, f"{a.size} {name} for {n} frames")
+    if not (np.isfinite(w).all() and (w >= 0).all()):
+        raise AstroBurstError(_lib.AB_ERR_INVALID, "a frame has a negative or non-finite weight")
+    if not (np.isfinite(s).all() and np.isfinite(o).all()):
+        raise AstroBurstError(_lib.AB_ERR_INVALID, "a frame has a non-finite scale or offset")
+    return (_lib.StackFrameParamC * max(n, 1))(*[_lib.StackFrameParamC(float(w[i]), float(s[i]), float(o[i])) for i in range(n)])
+
+
 AFFINE_METHODS = ("affine", "rigid", "phase_correlation", "identity")
 
 
@@ -1106,6 +1150,36 @@ class Context:
         self._check(self._L.ab_stack_sigma_clip(self._h, planes, n, C.byref(cfg), C.byref(po),
                                                 C.byref(rej) if want_rejected else None))
         return out, (int(rej.value) if want_rejected else None)
+
+    def stack_weighted(self, frames, weights, scales=None, offsets=None, sigma_low=3.0, sigma_high=3.0, max_iterations=5, out=None,
+                       want_weight=False, want_rejected=True):
+        """ab_stack_weighted: every frame normalised (p * scale + offset), sigma_clip_combine's rejection on the normalised samples,
+        then the mean of the survivors weighted per frame.  A frame of weight 0 takes no part; at most 64 frames of weight > 0.
+        -> (image, rejected), or (image, weight_plane, rejected) with want_weight; want_rejected=False keeps the call asynchronous
+        (fetch the count with last_rejected())."""
+        if len(frames) == 0:
+            raise AstroBurstError(_lib.AB_ERR_INVALID, "No images to stack")
+        params = stack_frame_params(len(frames), weights, scales, offsets)
+        keep = []
+        planes, n = self._plane_array(frames, keep)
+        if isinstance(frames, PlaneList):
+            rows, cols = frames.rows, frames.cols
+        else:
+            rows = min(p.rows for p in planes)
+            cols = min(p.cols for p in planes)
+        if out is None:
+            out = self._new_like(frames[0], rows, cols)
+        po = self._plane(out, keep) if _is_torch(out) else Plane(C.c_void_p(out.ctypes.data), rows, cols, 0)
+        wplane, pw = None, None
+        if want_weight:
+            wplane = self._new_like(out, rows, cols)
+            pw = self._plane(wplane, keep) if _is_torch(wplane) else Plane(C.c_void_p(wplane.ctypes.data), rows, cols, 0)
+        cfg = StackConfig(sigma_low, sigma_high, max_iterations, 0)
+        rej = C.c_uint64(0)
+        self._check(self._L.ab_stack_weighted(self._h, planes, params, n, C.byref(cfg), C.byref(po), C.byref(pw) if want_weight else None,
+                                              C.byref(rej) if want_rejected else None))
+        rejected = int(rej.value) if want_rejected else None
+        return (out, wplane, rejected) if want_weight else (out, rejected)
 
     def last_rejected(self) -> int:
         rej = C.c_uint64(0)

@@ -4,7 +4,8 @@
 // wizard_background.hip and compose_step.hip; crop.hip takes fits31 and the scope only (it words its messages by plane number).  The
 // scope only, with checks worded by themselves: spcc.hip, color.hip, extras.hip, stf.hip, fits.hip, resample.hip, background.hip,
 // subframe.hip, phase_corr.hip, psf.hip, deconv.hip, wavelet.hip, spectrum.hip, synth.hip, drizzle.hip; preview.hip and cube.hip take
-// block_minmax too (preview.hip's four-pixel groups of a sweep are its Groups, not a Span).  Not included by the benchmark's path
+// block_minmax too (preview.hip's four-pixel groups of a sweep are its Groups, not a Span); stack_weighted.hip takes the scope and
+// device_span / overlap_check (its other checks are worded like stack_sigma_clip.hip's).  Not included by the benchmark's path
 // and the multi-rank code (stats, detect, affine, batch_pipeline, stack_*, sharded, comm), whose plumbing is workspaces and child contexts.
 //   checks      fits31, plane_check, same_dims_check, out_planes_check, preview_of
 //   overlap     overlap_check over Spans.  Two forms of a span, kept apart because the entry points answer differently today:

@@ -100,7 +100,7 @@ __device__ __forceinline__ float lane_on(float x) {
 
 // median (combine.rs:38-40) and MAD (combine.rs:42-46) of a group of L lanes that holds n finite samples, n / 2 = M: rank r in lane
 // r >> 7, register r & 127.  MAD = the (M + 1)-th smallest deviation = min over the windows [p, p + M] of sorted samples that contain
-// the median of the larger end deviation, max(med - V[p], V[p + M] - med): p = 0 .. n - 1 - M (stack_sigma_clip.hip: med_mad_at).  The
+// the median of the larger end deviation, max(med - V[p], V[p + M] - med): p = 0 .. n - 1 - M (stack_clip.hpp: med_mad_at).  The
 // window p belongs to the lane that holds V[p] (lanes below M >> 7: every register; lane M >> 7: registers below M & 127); its high end
 // is register (i + M) & 127 of the lane (M >> 7) or (M >> 7) + 1 places on.
 template <int L, int M>

@@ -85,7 +85,7 @@ __device__ __forceinline__ double ranked_sum_any(const float (&x)[K], int a, int
 // finite); returns the rejected-sample count and writes the outputs from lane 0
 // `row` (nullable): 64 K floats of LDS that belong to this wave alone (the staged pixel's row, already consumed).  With it the MAD
 // needs no second sort: among SORTED samples the deviations left and right of the median are two sorted runs, and the m-th smallest
-// of their merge is min over p = 0 .. m of max(med - x[p], x[p + m] - med) (x[>= n] = +inf) -- stack_sigma_clip.hip's med_mad_at,
+// of their merge is min over p = 0 .. m of max(med - x[p], x[p + m] - med) (x[>= n] = +inf) -- stack_clip.hpp's med_mad_at,
 // evaluated here by the whole wave at once: the sorted samples go to the row, every lane reads its elements' partners p + m back.
 template <int K, bool TREE = false>
 __device__ __forceinline__ uint32_t wide_pixel(const WideArgs &a, int64_t g, float (&x)[K], int fin, int lane, float *row = nullptr) {

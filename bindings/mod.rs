@@ -2631,6 +2631,72 @@ pub fn analyze_subframes<P: PlaneSrc>(hip: &Hip, images: &[P], file_paths: &[Str
     Ok(ms.iter().zip(file_paths).map(|(m, p)| subframe_metrics(m, p)).collect())
 }
 
+// ---- the weighted, normalised stack: the consumer of the subframe scores (no counterpart in the reference: combine.rs:14-92 ends in an unweighted mean) ----
+/// one frame of `stack_weighted_into`: ab_stack_frame_param, field for field
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct StackFrameParam {
+    /// >= 0; a frame of weight 0 takes part in nothing
+    pub weight: f64,
+    pub scale: f32,
+    pub offset: f32,
+}
+// (the wrappers hand a `*const StackFrameParam` to the library as a `*const sys::ab_stack_frame_param`: same size, alignment and offsets)
+const _: () = {
+    assert!(std::mem::size_of::<StackFrameParam>() == std::mem::size_of::<sys::ab_stack_frame_param>());
+    assert!(std::mem::align_of::<StackFrameParam>() == std::mem::align_of::<sys::ab_stack_frame_param>());
+    assert!(std::mem::offset_of!(StackFrameParam, weight) == std::mem::offset_of!(sys::ab_stack_frame_param, weight));
+    assert!(std::mem::offset_of!(StackFrameParam, scale) == std::mem::offset_of!(sys::ab_stack_frame_param, scale));
+    assert!(std::mem::offset_of!(StackFrameParam, offset) == std::mem::offset_of!(sys::ab_stack_frame_param, offset));
+};
+/// how `stack_params_from_metrics` brings the frames' backgrounds to the best frame's (ab_stack_norm)
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum StackNormalize {
+    None = 0,
+    Additive = 1,
+    Multiplicative = 2,
+}
+/// the weights of the accepted subframes and the offsets / scales that normalise them; -> (one parameter per frame, index of the reference
+/// frame).  Host arithmetic only.
+pub fn stack_params_from_metrics(metrics: &[SubframeMetrics], normalize: StackNormalize) -> Result<(Vec<StackFrameParam>, usize)> {
+    let ms: Vec<sys::ab_subframe_metrics> = metrics
+        .iter()
+        .map(|m| sys::ab_subframe_metrics {
+            star_count: m.star_count as u64,
+            median_fwhm: m.median_fwhm,
+            median_eccentricity: m.median_eccentricity,
+            median_snr: m.median_snr,
+            background_median: m.background_median,
+            background_sigma: m.background_sigma,
+            noise_ratio: m.noise_ratio,
+            weight: m.weight,
+            accepted: m.accepted as i32,
+        })
+        .collect();
+    let mut out = vec![StackFrameParam { weight: 0.0, scale: 1.0, offset: 0.0 }; metrics.len()];
+    let mut reference = 0usize;
+    let rc = unsafe { sys::ab_stack_params_from_metrics(ms.as_ptr(), ms.len(), normalize as i32, out.as_mut_ptr() as *mut sys::ab_stack_frame_param, &mut reference) };
+    if rc != 0 {
+        bail!("No accepted subframe of positive weight to stack, or the best frame's background cannot be normalised to");
+    }
+    Ok((out, reference))
+}
+/// every frame normalised (p * scale + offset), sigma_clip_combine's rejection on the normalised samples, the survivors' mean weighted
+/// per frame; at most 64 frames of weight > 0.  `out_weight`: the per-pixel sum of the surviving weights.  Returns the rejected count.
+pub fn stack_weighted_into<P: PlaneSrc, D: PlaneDst>(hip: &Hip, frames: &[P], params: &[StackFrameParam], config: &StackConfig, out: &mut D, out_weight: Option<&mut D>) -> Result<u64> {
+    if frames.len() != params.len() {
+        bail!("{} parameters for {} frames", params.len(), frames.len());
+    }
+    let planes: Vec<_> = frames.iter().map(|f| f.ab()).collect();
+    let mut rejected = 0u64;
+    let mut pw = out_weight.map(|w| w.ab_mut());
+    let pw_ptr = pw.as_mut().map_or(std::ptr::null_mut(), |p| p as *mut sys::ab_plane_mut);
+    hip.check(unsafe {
+        sys::ab_stack_weighted(hip.ctx, planes.as_ptr(), params.as_ptr() as *const sys::ab_stack_frame_param, planes.len(), &stack_cfg(config), &mut out.ab_mut(), pw_ptr, &mut rejected)
+    })?;
+    Ok(rejected)
+}
+
 // ---- f4  cmd/helpers.rs render_rgb_preview, infra/ipc.rs, infra/tiles.rs -----------------------------------------------------------------------------------------------------
 /// preview dims of render_rgb_preview (cmd/helpers.rs:204-230)
 pub fn preview_dims(rows: usize, cols: usize, max_dim: usize) -> (usize, usize) {

@@ -678,6 +678,53 @@ AB_API int ab_analyze_subframes(ab_ctx *ctx, const ab_plane *images, size_t n, c
                                 ab_subframe_metrics *out);
 AB_API void ab_normalize_subframe_weights(ab_subframe_metrics *metrics, size_t n);  /* normalize_weights, :148-159 */
 
+/* ---- the weighted, normalised sigma-clip stack: what consumes the subframe scores ------------------------------------ */
+/* The reference has no weighted stack (core/stacking/combine.rs:14-92 ends in an unweighted mean of the survivors); this definition
+ * is the library's own, built so that the rejection is exactly the reference's and only the final mean changes.
+ *   Active frames.  A frame takes part iff weight > 0.  A frame of weight 0 takes part in nothing -- not in the clipping, not in the
+ *     mean, not in the rejected count -- and its plane is never read.  A negative or non-finite weight, a non-finite scale or offset
+ *     -> AB_ERR_INVALID; no active frame -> AB_ERR_INVALID "No images to stack"; more than AB_STACK_MAX_ACTIVE (64) active frames ->
+ *     AB_ERR_UNSUPPORTED (a pixel's samples live in one lane's registers, twice; the engines for deeper stacks do not hand out the
+ *     surviving interval yet).  Any number of frames of weight 0 may sit between the active ones.
+ *   Samples.  s_f = p_f * scale_f + offset_f, an f32 multiply and then an f32 add (never fused); a frame with scale == 1 and
+ *     offset == 0 is read as it is (-0.0 stays -0.0).  Finiteness is judged on s_f: a sample the normalisation sends to +-inf is
+ *     dropped like a NaN (combine.rs:170-175).
+ *   Rejection.  sigma_clip_combine on the finite s_f of the active frames, with the library's documented ascending-order f64 sums in
+ *     iterations >= 1 and the correctly rounded sqrt: the arithmetic of ab_stack_sigma_clip under AB_STACK_EXACT=1.  The survivors
+ *     are an interval of the sorted samples and equal values share their fate: frame f survives iff s_f is finite and lies between
+ *     the smallest and the largest surviving value.
+ *   Result per pixel, m = number of finite samples.  m = 0: image 0.0, weight sum 0.  m = 1: that sample, that frame's weight.
+ *     Nothing survives: the reference's fallback (last_center if finite, else 0.0; combine.rs:85-88), weight sum 0.  Otherwise
+ *     image = (float)(sum w_f (double)s_f / sum w_f) over the surviving frames, both sums in f64 in ascending FRAME INDEX order, one
+ *     multiply and one add per frame, each rounded; weight plane = (float)sum w_f.  *out_rejected = the reference's count
+ *     (combine.rs:76-78) summed over the pixels.
+ * With all weights 1, scale 1 and offset 0 this is ab_stack_sigma_clip under AB_STACK_EXACT=1 but for the order of the final sum
+ * (frame order, not ascending value): identical whenever that sum is exact in f64.  cfg->align is ignored.
+ * planes: host or device, each at least out->rows x out->cols, read with its own row stride (the top-left crop, as
+ * ab_stack_sigma_clip).  out, out_weight (nullable; same dims as out): host or device; a device output may not overlap a device
+ * input or the other output; the output and every active plane hold fewer than 2^31 pixels (AB_ERR_INVALID).  The call records the events behind ab_stack_last_kernel_ms, and ab_stack_last_rejected answers after
+ * it; out_rejected == NULL keeps it asynchronous on the context's stream (device planes). */
+#define AB_STACK_MAX_ACTIVE 64
+typedef struct {
+    double weight; /* >= 0; 0 = the frame takes no part */
+    float scale;
+    float offset;
+} ab_stack_frame_param;
+AB_API int ab_stack_weighted(ab_ctx *ctx, const ab_plane *planes, const ab_stack_frame_param *params, size_t n,
+                             const ab_stack_config *cfg, ab_plane_mut *out, ab_plane_mut *out_weight, uint64_t *out_rejected);
+/* The parameters of ab_stack_weighted from the scores of ab_analyze_subframes (+ ab_normalize_subframe_weights).  Host-only
+ * arithmetic: no context, usable without a GPU.
+ *   weight_f = metrics[f].weight when metrics[f].accepted is set and the weight is finite and > 0, else 0.
+ *   The reference frame is the active frame of the largest weight, the lowest index on a tie (*out_reference, nullable).
+ *   AB_STACK_NORM_NONE: scale 1, offset 0; the backgrounds are not looked at.
+ *   AB_STACK_NORM_ADDITIVE: scale 1, offset = (float)(bg_ref - bg_f), bg = background_median.
+ *   AB_STACK_NORM_MULTIPLICATIVE: scale = (float)(bg_ref / bg_f), offset 0.
+ *   In the two normalising modes an active frame whose background_median is not finite (multiplicative: or <= 0) gets weight 0.
+ * AB_ERR_INVALID: a NULL metrics or out, an unknown mode, no active frame, or a reference frame whose own background fails that test. */
+typedef enum { AB_STACK_NORM_NONE = 0, AB_STACK_NORM_ADDITIVE = 1, AB_STACK_NORM_MULTIPLICATIVE = 2 } ab_stack_norm;
+AB_API int ab_stack_params_from_metrics(const ab_subframe_metrics *metrics, size_t n, int32_t normalize, ab_stack_frame_param *out,
+                                        size_t *out_reference);
+
 /* ---- preview / tile renderers up to the PNG encoder ---------------------------------------------- */
 /* preview size for max_dim (cmd/helpers.rs:283-290, infra/ipc.rs:100-103): the plane's own dims when both fit */
 AB_API int ab_preview_dims(int64_t rows, int64_t cols, int64_t max_dim, int64_t *out_rows, int64_t *out_cols);
